@@ -26,9 +26,16 @@ shard code either way:
   * under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (WORLD_SIZE set): one rank per
     GPU; torch.distributed (RCCL) is used for the barrier and the MAX-reduction of the elapsed time only.
 
-Rank 0 prints ONE JSON line: metric/value (whole-job units/s), roofline (algorithmic bytes per step / device time of a
-step, HIP events on the launch stream, with mean, min and median over the K steps) and, at N=1, the CPU baseline:
-the reference's own radix-4 functions (oracle/_ref) timed on this box's host cores by a pthread harness.
+Rank 0 prints ONE JSON line: metric/value (whole-job units/s), ms_per_step (host wall time of one timed step) and roofline
+(algorithmic bytes per step / device time of a step, HIP events on the launch stream, with mean, min and median over the K
+steps).  A plain run does only that: set up, W untimed steps, K timed steps, the line.
+
+  --full               also everything else the line can carry, after the timed region: the parity check of every shard
+                       against the oracle (on the first warm-up step), the memory probes, the same launch on other primes,
+                       the also_config* blocks and the CPU baseline -- the reference's own radix-4 functions (oracle/_ref)
+                       timed on this box's host cores by a pthread harness
+  --dump-outputs DIR   after the timed steps, what the last one left for its caller as DIR/<name>.npy (float64; a fixed,
+                       seeded sample of whole polynomials when the output is larger than DUMP_BYTES)
 """
 import argparse
 import ctypes as C
@@ -54,6 +61,8 @@ BYTES_PER_NTT = 16 * N       # one 8-byte read + one 8-byte write per coefficien
 METRIC = "batched forward NTTs/sec at N=2^14, 50-bit q; achieved HBM GB/s vs peak"
 TRAFFIC_DIR = os.path.join(ROOT, "profiles", "r06")
 TRAFFIC_JSON = os.path.join(TRAFFIC_DIR, "pmc_traffic.json")      # the headline launch (config 4); pmc_traffic_config{2,3,5}.json beside it
+DUMP_BYTES = 48 << 20        # --dump-outputs writes at most this many bytes (beyond: a seeded sample of whole polynomials)
+DUMP_SEED = 0xD0D0
 
 
 def file_sha256(path):
@@ -538,6 +547,35 @@ def run_steps(shards, steps, warmup, barrier, after_first_warmup=None):
     return elapsed, [s.kernel_ms(steps) for s in shards]
 
 
+def dump_outputs(outdir, shards, kind):
+    """--dump-outputs: what the last timed step left for its caller, as outdir/<name>.npy in float64 -- kind "fwd" and
+    "roundtrip": the slab transformed in place, `ntt_fwd` / `ntt_roundtrip` [poly][N]; "rns_product": the product c,
+    `rns_product` [limb][poly][N].  Residues below 2^53 are exact in float64; for a larger modulus the words go out as
+    <name>_hi and <name>_lo (upper and lower 32 bits).  Every polynomial of every shard this process drives when they fit in
+    DUMP_BYTES, otherwise the same seeded sample of whole polynomials of each shard (in index order) in every run."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    s0 = shards[0]
+    wide = max(s0.qs) >= 1 << 53
+    per_shard = max(1, DUMP_BYTES // (8 * s0.n * s0.limbs * (2 if wide else 1) * len(shards)))
+    parts = []
+    for s in shards:
+        which = np.arange(s.batch)
+        if s.batch > per_shard:
+            which = np.sort(np.random.default_rng(DUMP_SEED + s.index).choice(s.batch, per_shard, replace=False))
+        base = s.out if kind == "rns_product" else s.buf
+        parts.append(np.stack([s.polys(which.tolist(), base=base, limb=l).reshape(len(which), s.n) for l in range(s.limbs)]))
+    words = np.concatenate(parts, axis=1)
+    if kind != "rns_product":
+        words = words[0]
+    name = {"fwd": "ntt_fwd", "roundtrip": "ntt_roundtrip", "rns_product": "rns_product"}[kind]
+    if wide:
+        np.save(os.path.join(outdir, name + "_hi.npy"), (words >> np.uint64(32)).astype(np.float64))
+        np.save(os.path.join(outdir, name + "_lo.npy"), (words & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    else:
+        np.save(os.path.join(outdir, name + ".npy"), words.astype(np.float64))
+
+
 def side_forward(lib, shard, q, steps, label):
     """the same forward launch on another prime, same buffer, same batch, HIP events on the same stream, after the
     timed region.  Not the headline."""
@@ -794,7 +832,15 @@ def main():
                     help="another modulus for the chosen configuration's transforms (hex or decimal, prime with 2N | q - 1; single-prime "
                          "configs 2, 3, 4: the reference's bench walks its (q, N) cases the same way, tests/bench.c:58-140); the metric string says so")
     ap.add_argument("--also-steps", type=int, default=8, help="timed steps of each also_configN block (warm-ups covering >= 60 ms of work in front)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity check against the oracle, the memory probes, the other primes, the also_config* blocks and the "
+                         "CPU baseline (a plain run only times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64; beyond 48 MiB a seeded "
+                         "sample of whole polynomials)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -856,8 +902,8 @@ def main():
 
     # parity spot check on the benchmarked launches themselves (class Parity): first and last polynomial of EVERY shard --
     # every rank checks the shards it drives -- against the oracle after the first warm-up step.  A rank whose shard is wrong
-    # raises: under torch.distributed.run that ends the job non-zero, and no JSON line is printed.
-    check = not os.environ.get("NTT_BENCH_NOCHECK")   # (ablation builds compute garbage on purpose)
+    # raises: under torch.distributed.run that ends the job non-zero, and no JSON line is printed.  --full only.
+    check = args.full and not os.environ.get("NTT_BENCH_NOCHECK")   # (ablation builds compute garbage on purpose)
     pars = [Parity(w, s, batch) for s in shards]
     par = pars[0]
 
@@ -869,6 +915,8 @@ def main():
             p.capture()
     elapsed, kernel_ms = run_steps(shards, args.steps, max(args.warmup, 1 if check else 0), barrier,
                                    check_all if check else None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, shards, w.kind)
     on_gpu = dist is not None and dist.get_backend() == "nccl"
     elapsed = allreduce_max(dist, elapsed, device="cuda" if on_gpu else None)
     # shards whose first and last polynomial were compared with the oracle, summed over the ranks (= n_gpus when all did)
@@ -892,9 +940,10 @@ def main():
         if check and w.kind == "roundtrip":
             par.check_roundtrip_forward()
         # after the timed region, on shard 0's resident buffer
-        copy_gbs = None if args.headline_only else s0.copy_ceiling_gbs()
-        shape_gbs = None if args.headline_only else s0.shape_ceiling_gbs()
-        oop_gbs = None if args.headline_only else s0.out_of_place_copy_gbs()   # (last: it overwrites half of the buffer)
+        side = args.full and not args.headline_only
+        copy_gbs = s0.copy_ceiling_gbs() if side else None
+        shape_gbs = s0.shape_ceiling_gbs() if side else None
+        oop_gbs = s0.out_of_place_copy_gbs() if side else None   # (last: it overwrites half of the buffer)
         slow = max(range(len(shards)), key=lambda i: kernel_ms[i] if i < len(kernel_ms) else 0) if world == 1 else 0
         out = make_report(args, n_gpus, batch, elapsed, kernel_ms, s0.arith(), s0.hbm_passes(), n=n, copy_gbs=copy_gbs,
                           workload=w, step_ms=shards[slow].step_ms(), f64_class=s0.f64_class(), shape_gbs=shape_gbs, oop_gbs=oop_gbs,
@@ -905,7 +954,7 @@ def main():
         out["lib_sha256"] = file_sha256(lib.LIB_PATH)
         out["roofline"]["traffic_lib_sha256"] = traffic_lib_sha256()
         out["roofline"]["traffic_from_this_binary"] = out["roofline"]["traffic_lib_sha256"] == out["lib_sha256"]
-        if not args.headline_only:
+        if side:
             if w.config == 4 and n == N:
                 out["also_literal_50_bit_q"] = literal_50_bit(lib, s0, args.steps)
             if w.config == 3:
@@ -940,7 +989,7 @@ def main():
                             also_failed = True
         # north_star: the CPU baseline "timed on the host cores of the same box in the same run" -- on every line, N > 1 included
         # (rank 0, after the timed region; the other ranks wait at the closing barrier)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(w, lib, budget_s=args.cpu_budget_s)
         print(json.dumps(out), flush=True)
     barrier()

@@ -160,13 +160,21 @@ def test_parameter_helpers(lib, oracle, kat):
     assert lib.min_root(0x3fffffffe8001, 1 << 12) == 0     # composite modulus: refused, not searched forever
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/tests"), reason="reference tree only exists in the build container")
+@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libntt_ref.so")),
+                    reason="build() compiled no reference binaries into oracle/_ref: the reference sources were not there")
 def test_reference_drivers_compile_unchanged_against_our_headers(lib):
-    """SURVEY 8b 'drop in unchanged': the reference's own tests/main.c,
-    test_correctness.c and bench.c build against include/ + libntt_mi355x.so."""
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "dropin"], stdout=subprocess.DEVNULL)
+    """SURVEY 8b 'drop in unchanged': the reference's own tests/main.c, test_correctness.c and bench.c, compiled by build()
+    against include/ (oracle/Makefile `dropin`, beside oracle/_ref/libntt_ref.so), are linked to libntt_mi355x.so and take
+    every function they call from it or from the C library."""
+    out = subprocess.check_output(["nm", "-D", "--defined-only", lib.LIB_PATH], text=True)
+    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
     for exe in ("ntt-variants-dropin", "ntt-variants-bench-dropin"):
-        assert os.path.exists(os.path.join(ROOT, "oracle", "_ref", exe))
+        path = os.path.join(ROOT, "oracle", "_ref", exe)
+        assert os.path.exists(path), exe
+        assert "[libntt_mi355x.so]" in subprocess.check_output(["readelf", "-d", path], text=True), exe
+        undef = [l.split() for l in subprocess.check_output(["nm", "-D", "--undefined-only", path], text=True).splitlines()]
+        ours = {f[-1] for f in undef if f[0] == "U" and "@" not in f[-1]}      # (versioned names: the C library's)
+        assert ours and ours <= exported, (exe, ours - exported)
 
 
 @pytest.mark.parametrize("example", ["batched_product", "rns_chain_product", "pointer_batch", "rns_ciphertext_tensor"])

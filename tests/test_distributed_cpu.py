@@ -162,6 +162,55 @@ def test_eight_shards_every_one_parity_checked():
         bench.parity_all([_Par7(pars[7])])
 
 
+class _HostShard:
+    """test double for bench.GpuShard's output side: host arrays in place of device buffers, GpuShard.polys itself"""
+
+    class _Buf:
+        def __init__(self, words):
+            self.words = words
+
+        def download(self, cnt, offset):
+            return self.words[offset:offset + cnt].copy()
+
+    def __init__(self, index, batch, n, qs, seed):
+        self.index, self.batch, self.n, self.qs, self.limbs = index, batch, n, qs, len(qs)
+        self.slab, self.strides = batch * n, None
+        rng = np.random.default_rng(seed)
+        self.words = np.stack([rng.integers(0, q, batch * n, dtype=np.uint64) for q in qs])     # [limb][batch * N]
+        self.buf = self.out = self._Buf(self.words.ravel())
+
+    def polys(self, which, base=None, limb=0):
+        import bench
+        return bench.GpuShard.polys(self, which, base, limb)
+
+
+def test_dump_outputs_sample_and_wide_words(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every polynomial while they fit, beyond DUMP_BYTES the same seeded sample of whole polynomials of
+    every shard; float64 files, exact (moduli above 2^53 as upper and lower 32-bit halves); never more than DUMP_BYTES"""
+    import bench
+    n = 1 << 10
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 * n * 8)
+    shards = [_HostShard(i, 10, n, [Q], i) for i in range(2)]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), shards, "fwd")
+    assert os.listdir(tmp_path / "a") == ["ntt_fwd.npy"]
+    got = np.load(tmp_path / "a" / "ntt_fwd.npy")
+    assert got.dtype == np.float64 and got.shape == (4, n) and np.array_equal(got, np.load(tmp_path / "b" / "ntt_fwd.npy"))
+    expect = []
+    for s in shards:
+        rows = np.sort(np.random.default_rng(bench.DUMP_SEED + s.index).choice(s.batch, 2, replace=False))
+        expect.append(s.words[0].reshape(s.batch, n)[rows])
+    assert np.array_equal(got.astype(np.uint64), np.concatenate(expect))
+    # 60-bit moduli, two limbs, everything fits: [limb][poly][N] as hi / lo halves
+    monkeypatch.setattr(bench, "DUMP_BYTES", 48 << 20)
+    qs = [(1 << 60) - 93, (1 << 60) - 173]
+    s = _HostShard(0, 3, n, qs, 7)
+    bench.dump_outputs(str(tmp_path / "c"), [s], "rns_product")
+    hi, lo = (np.load(tmp_path / "c" / ("rns_product_%s.npy" % h)) for h in ("hi", "lo"))
+    assert sorted(os.listdir(tmp_path / "c")) == ["rns_product_hi.npy", "rns_product_lo.npy"] and hi.shape == (2, 3, n)
+    assert np.array_equal((hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64), s.words.reshape(2, 3, n))
+
+
 class _Par7:
     """parity of an already transformed shard against a tampered input: must fail"""
 

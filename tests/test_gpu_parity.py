@@ -682,7 +682,7 @@ def test_bench_two_ranks_folded_on_one_gpu():
     env = dict(os.environ, NTT_BENCH_DEVICE_MOD="1", NTT_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8192", "--cpu-budget-s", "1"]
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8192", "--cpu-budget-s", "1", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -702,7 +702,7 @@ def test_bench_single_process_two_shards_folded_on_one_gpu():
     env.pop("WORLD_SIZE", None)
     for scaling, per_gpu in (("weak", 4096), ("strong", None)):
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-               "--scaling", scaling, "--no-cpu-baseline"]
+               "--scaling", scaling, "--no-cpu-baseline", "--full"]
         if per_gpu:
             cmd += ["--batch", str(per_gpu)]
         else:
@@ -736,13 +736,15 @@ def test_bench_eight_shards_folded_on_one_gpu():
         assert out.returncode == 0, out.stderr[-3000:]
         return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     for cfg, batch in ((4, 8192), (2, 16384)):
-        one = run(["--gpus", "1", "--config", str(cfg), "--batch", str(8 * batch), "--steps", "10", "--warmup", "4", "--no-cpu-baseline", "--headline-only"])
-        d = run(["--gpus", "8", "--config", str(cfg), "--batch", str(batch), "--steps", "10", "--warmup", "4", "--cpu-budget-s", "1", "--headline-only"])
+        one = run(["--gpus", "1", "--config", str(cfg), "--batch", str(8 * batch), "--steps", "10", "--warmup", "4", "--no-cpu-baseline", "--headline-only",
+                   "--full"])
+        d = run(["--gpus", "8", "--config", str(cfg), "--batch", str(batch), "--steps", "10", "--warmup", "4", "--cpu-budget-s", "1", "--headline-only",
+                 "--full"])
         assert d["n_gpus"] == 8 and d["config"]["global_batch"] == 8 * batch and len(d["roofline"]["kernel_ms_per_gpu"]) == 8
         assert d["parity"]["shards_checked"] == 8 and d["parity"]["of"] == 8
         assert d["cpu_baseline"]["value"] > 0
         assert d["value"] > 0.8 * one["value"], (cfg, d["value"], one["value"])
-    d = run(["--gpus", "8", "--batch", "8192", "--steps", "5", "--warmup", "2", "--cpu-budget-s", "1", "--headline-only"], launcher=True,
+    d = run(["--gpus", "8", "--batch", "8192", "--steps", "5", "--warmup", "2", "--cpu-budget-s", "1", "--headline-only", "--full"], launcher=True,
             e=dict(env, NTT_BENCH_BACKEND="gloo"))
     assert d["n_gpus"] == 8 and d["parity"]["shards_checked"] == 8 and d["cpu_baseline"]["value"] > 0
     assert len(d["roofline"]["kernel_ms_per_gpu"]) == 8
@@ -768,11 +770,62 @@ def test_bench_with_another_modulus(q, config):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", str(config), "--q", q, "--steps", "2", "--warmup", "1", "--batch", "96",
-           "--no-cpu-baseline", "--headline-only"]
+           "--no-cpu-baseline", "--headline-only", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert "--q " + hex(int(q, 0)) in line["metric"] and line["parity"]["shards_checked"] == 1 and line["value"] > 0
+
+
+@pytest.mark.parametrize("config,batch", [(4, 512), (3, 8), (5, 4)])
+def test_bench_plain_run_dumps_what_its_last_step_computed(lib, oracle, tmp_path, config, batch):
+    """a plain `bench.py` run (no --full): the timed steps and the line only, --steps timed steps; --dump-outputs holds what the
+    last timed step left for its caller, equal to the oracle's result on the same device-generated inputs -- the forward slab after
+    W + K in-place transforms (a seeded sample of 384 of the 512 polynomials: 64 MiB do not fit), the round trip's slab (the input
+    again), the RNS product of the last step's operand pair"""
+    import json
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    steps, warmup = 3, 2
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", str(config), "--batch", str(batch), "--steps", str(steps),
+           "--warmup", str(warmup), "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads(out.stdout.strip().splitlines()[-1])
+    assert d["steps"] == steps and d["warmup"] == warmup and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["higher_is_better"] is True and d["dtype"] in ("f64", "u64") and d["unit"]
+    assert not [k for k in d if k.startswith("also_") or k == "cpu_baseline"] and d["roofline"]["inplace_rmw_probe"] is None
+    assert d["parity"]["shards_checked"] == 0
+    files = sorted(os.listdir(tmp_path))
+    assert sum(os.path.getsize(os.path.join(tmp_path, f)) for f in files) <= 64 << 20
+    w = bench.workload_for(config).resolve(lib)
+    n = w.n
+    if config == 5:
+        assert files == ["rns_product.npy"]
+        got = np.load(os.path.join(tmp_path, files[0]))
+        assert got.dtype == np.float64 and got.shape == (w.limbs, batch, n)
+        last = min(warmup, 2) + steps - 1               # operand sets: up to two for the warm-ups, then one per timed step
+        for l, (q, r) in enumerate(zip(w.qs, w.roots)):
+            a, b = (oracle.fill_uniform(batch * n, q, bench.SEED + 2 * last + k, l * batch * n) for k in (0, 1))
+            cx = oracle.ctx(n, q, r)
+            assert np.array_equal(got[l].astype(np.uint64).ravel(), cx.inv(oracle.pointwise(cx.fwd(a), cx.fwd(b), q))), l
+        return
+    name = "ntt_fwd" if config == 4 else "ntt_roundtrip"
+    assert files == [name + ".npy"]
+    got = np.load(os.path.join(tmp_path, files[0]))
+    rows = np.arange(batch)
+    if batch * n * 8 > bench.DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(batch, bench.DUMP_BYTES // (8 * n), replace=False))
+    assert got.dtype == np.float64 and got.shape == (len(rows), n)
+    a = oracle.fill_uniform(batch * n, w.qs[0], bench.SEED, 0).reshape(batch, n)[rows].ravel().copy()
+    if config == 4:
+        cx = oracle.ctx(n, w.qs[0], w.roots[0])
+        for _ in range(warmup + steps):
+            a = cx.fwd(a)
+    assert np.array_equal(got.astype(np.uint64).ravel(), a)
 
 
 def test_squaring_aliases_both_operands(lib, oracle):
@@ -1501,7 +1554,7 @@ def test_bench_rccl_control_plane_single_rank():
     env = dict(os.environ, NTT_BENCH_FORCE_DIST="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--batch", "8192", "--no-cpu-baseline"]
+           "--batch", "8192", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

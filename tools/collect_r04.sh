@@ -6,13 +6,13 @@
 #   stamp build; sweeps; RNS pipeline rows.
 out=$1; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-timeout 900 python3 bench.py > $out/bench_default.json 2> $out/bench_default.err
+timeout 900 python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 for c in 4 2 3 5; do
   st="--steps 20 --warmup 3"; [ $c = 5 ] && st="--steps 10 --warmup 2"
-  timeout 900 python3 bench.py --config $c $st --no-also > $out/bench_config$c.json 2> $out/bench_config$c.err
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt$c -- python3 bench.py --config $c $st --no-cpu-baseline --headline-only > $out/bench_config${c}_under_rocprofv3.json 2> $out/kt$c.log
+  timeout 900 python3 bench.py --full --config $c $st --no-also > $out/bench_config$c.json 2> $out/bench_config$c.err
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt$c -- python3 bench.py --full --config $c $st --no-cpu-baseline --headline-only > $out/bench_config${c}_under_rocprofv3.json 2> $out/kt$c.log
   for ctr in FETCH_SIZE WRITE_SIZE; do
-    timeout 900 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $out/pmc$c/$ctr -- python3 bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline --headline-only > $out/pmc${c}_$ctr.log 2>&1
+    timeout 900 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $out/pmc$c/$ctr -- python3 bench.py --full --config $c --steps 3 --warmup 1 --no-cpu-baseline --headline-only > $out/pmc${c}_$ctr.log 2>&1
   done
 done
 python3 tools/pmc_kernels.py $out > $out/pmc_per_kernel.txt 2>&1
@@ -26,7 +26,7 @@ python3 tools/pmc_dot.py $out > $out/pmc_dot_per_kernel.txt 2>&1
 timeout 900 python3 tools/domain_bench.py --logn 8 10 12 13 14 15 16 17 --k 1 2 3 8 > $out/domain_bench.txt 2>&1
 timeout 600 python3 tools/domain_bench.py --logn 12 14 16 --k 1 3 --bits 51 52 60 --no-broadcast > $out/domain_bench_moduli.txt 2>&1
 # sustained headline: 400 back-to-back steps (about 3 s), rocm-smi power / clocks beside it; in-kernel clock from the stamp build
-bash tools/exp_smi.sh $out/sustained python3 bench.py --steps 400 --warmup 5 --no-cpu-baseline --headline-only
+bash tools/exp_smi.sh $out/sustained python3 bench.py --full --steps 400 --warmup 5 --no-cpu-baseline --headline-only
 mv $out/sustained.log $out/bench_config4_sustained.json; mv $out/sustained.smi $out/rocm_smi_power_clock_during_sustained_bench.txt
 if [ -f build/libntt_stamps.so ]; then NTT_LIB=build/libntt_stamps.so timeout 300 python3 tools/stamps.py > $out/phase_stamps_and_clock.txt 2>&1; fi
 timeout 600 python3 tools/sweep.py --logn 8 9 10 11 12 13 14 15 16 17 --ops fwd inv --qs 0x80000001c0001 --bytes 16e9 > $out/sweep_sizes.txt 2>&1
