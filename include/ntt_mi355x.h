@@ -115,7 +115,8 @@ typedef enum ntt_option {
                           * and the two halves go through the 2^14-point block stages one after the other: 16N bytes cross HBM, where the
                           * two-pass forms move 24N..32N across the fabric (measured forward 0.43 -> see profiles/r06/onepass_2p15.txt);
                           * 0 = the two-pass forms (XCD-local launch / per-pass launches); -1 (default) = one pass when the batch gives
-                          * every second CU a polynomial (measured crossover: 64..96 polynomials).  Calls that ask for lazy outputs get canonical words from it
+                          * every second CU a polynomial (measured crossover: 64..96 polynomials) and neither NTT_OPT_XCD_LOCAL 1 nor
+                          * NTT_OPT_BLOCK_LOG is set (explicit options win).  Calls that ask for lazy outputs get canonical words from it
                           * (inside the lazy ranges).  Results are identical. */
   NTT_OPT_FUSED_PRODUCT = 5 /* N = 2^8..2^17, FP64: 1 (default) = ntt_negacyclic_mul_batch as ONE launch that takes both
                           * operands through the forward stages, multiplies in registers and runs the inverse: 24N bytes up to

@@ -317,7 +317,7 @@ static int fwd_mul(const ntt_plan *p, uint64_t *d_c, uint64_t *d_a, const uint64
   /* N = 2^15, FP64 policies: the one-pass transform with the product at its output (onepass_mul_kernel) -- a is left as it was.
    * Same choice as the plain transform's (NTT_OPT_ONE_PASS; -1: batches that give every second CU a polynomial). */
   if(p->m == kFusedMax + 1 && p->arith == NTT_ARITH_F64 && !p->generic && ls.n <= kMaxLimbs && !ls.ptab &&
-     (p->one_pass == 1 || (p->one_pass < 0 && 2 * batch * (uint64_t)ls.n >= (uint64_t)p->num_cus))) {
+     one_pass_pays(p, batch * (uint64_t)ls.n)) {
     MulArgs ma{};
     ma.a             = d_a;
     ma.b             = d_bhat;
@@ -1026,7 +1026,7 @@ extern "C" int ntt_rns_inv_dot_dev_ptrs(int nlimbs, ntt_plan *const *plans, cons
 static bool ptrs_one_pass_mul(const ntt_plan *p, uint64_t count)
 {
   return p->m == kFusedMax + 1 && p->arith == NTT_ARITH_F64 && !p->generic && dot_kernel_applies(p) &&
-         (p->one_pass == 1 || (p->one_pass < 0 && 2 * count >= (uint64_t)p->num_cus));
+         one_pass_pays(p, count);
 }
 
 /* c^ = fwd(a) (.) b^ (+ c^): a is transformed in place first (scratch, as for plans without the fused kernel) */

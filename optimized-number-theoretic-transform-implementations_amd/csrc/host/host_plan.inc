@@ -164,12 +164,22 @@ struct ntt_plan {
   int              fused_product = 1; /* N = 2^8..2^17, FP64: ntt_negacyclic_mul_batch through the fused product kernels (0: four-launch
                                        * chain; 2: as 1, but a's forward transform always as a launch of its own) */
   int              one_pass   = -1;    /* 2^15, FP64 policies: the transform in ONE pass, the polynomial in the registers of one workgroup
-                                        * (onepass_kernel): 1 on, 0 off, -1 = batches that give every CU a polynomial */
+                                        * (onepass_kernel): 1 on, 0 off, -1 = batches that give every second CU a polynomial, unless
+                                        * xcd_local or block_log is set explicitly (one_pass_pays) */
   int              two_phase  = -1;    /* 2^16, 2^17: both passes of a polynomial inside one workgroup (twophase_kernel):
                                         * 1 on, 0 off, -1 where it measured faster (forward 2^16, scheduled FP64 policy: +3 %) */
 };
 
 static bool is_pow2(uint64_t n) { return n && !(n & (n - 1)); }
+
+/* N = 2^15, FP64 policies: whether a call over `polys` polynomials (batch x limbs) takes the one-pass kernels (onepass_kernel,
+ * onepass_mul_kernel).  NTT_OPT_ONE_PASS 1 / 0 decides; the automatic choice (-1) wants a polynomial for every second CU and yields to
+ * an explicit NTT_OPT_XCD_LOCAL 1 or NTT_OPT_BLOCK_LOG, which ask for the two-pass forms. */
+static bool one_pass_pays(const ntt_plan *p, uint64_t polys)
+{
+  if(p->one_pass >= 0) return p->one_pass == 1;
+  return p->xcd_local != 1 && p->block_log == 0 && 2 * polys >= (uint64_t)p->num_cus;
+}
 static bool h_is_prime(uint64_t n); /* deterministic Miller-Rabin (below) */
 
 /* headroom class of ArithU64X for q (ntt_arith.h): B = 8 * 2^K multiples of q below 2^64; -1 = not served (reduce_any
@@ -499,7 +509,8 @@ extern "C" int ntt_plan_info(const ntt_plan *p, uint64_t info[8])
                       p->m <= kTeamBlock + 5 && p->xcd_local != 0;
     const bool tp     = f64big && p->m >= kFusedMax + 2 && p->m <= kFusedMax + 3 &&
                     (p->two_phase == 1 || (p->two_phase < 0 && p->m == kFusedMax + 2 && p->kcls != kWideClass));
-    const bool op     = f64big && p->m == kFusedMax + 1 && p->one_pass != 0; /* 2^15: one pass, the polynomial in registers */
+    /* 2^15: one pass, the polynomial in registers -- for a batch that fills the chip, unless explicit options ask for two passes */
+    const bool op     = f64big && p->m == kFusedMax + 1 && one_pass_pays(p, (uint64_t)p->num_cus);
     info[5] = (team || tp || op) ? 1u : (uint64_t)make_passes(p->m, p->generic).n;
   }
   info[6] = (uint64_t)p->device;

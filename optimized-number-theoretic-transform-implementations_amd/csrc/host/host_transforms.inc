@@ -167,7 +167,7 @@ static int run_transform(const ntt_plan *p, uint64_t *d_a, uint64_t batch, bool 
    * kernel's canonical words: they satisfy the lazy contract ([0,4q) forward, [0,2q) inverse), and one pass with the final reduction
    * beats two passes without it. */
   if(p->m == kFusedMax + 1 && p->arith == NTT_ARITH_F64 && !p->generic && ls.n <= kMaxLimbs &&
-     (p->one_pass == 1 || (p->one_pass < 0 && 2 * batch * (uint64_t)ls.n >= (uint64_t)p->num_cus))) {
+     one_pass_pays(p, batch * (uint64_t)ls.n)) {
     PassArgs pa{};
     pa.a           = d_a;
     pa.limbs       = ls.d;

@@ -1,0 +1,87 @@
+"""GPU: every kernel instance the recipe table covers (tests/kernel_recipes.py) launched and checked word for word against
+the oracle; a kernel trace proves that the recipes launch every instance they claim; route precedence of explicit plan
+options over the automatic one-pass choice."""
+import csv
+import glob
+import os
+import subprocess
+import sys
+import tempfile
+
+import pytest
+
+import kernel_inventory
+import kernel_recipes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RECIPES_PY = os.path.join(ROOT, "tests", "kernel_recipes.py")
+
+_CASES = kernel_recipes.cases()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", _CASES, ids=[c.id for c in _CASES])
+def test_instance(lib, oracle, case):
+    case.run(lib, oracle)
+
+
+def _rocprofv3():
+    for exe in ("/opt/rocm/bin/rocprofv3",):
+        if os.path.exists(exe):
+            return exe
+    import shutil
+    exe = shutil.which("rocprofv3")
+    if not exe:
+        pytest.fail("rocprofv3 is not on this machine: the launch proof needs its kernel trace")
+    return exe
+
+
+def _traced(args, seconds):
+    """run `python3 tests/kernel_recipes.py ARGS` in a fresh child process under a kernel trace; the set of normalised kernel
+    names it launched"""
+    with tempfile.TemporaryDirectory() as d:
+        cmd = ["timeout", "-k", "10", str(seconds), _rocprofv3(), "--kernel-trace", "--output-format", "csv", "-d", d, "--",
+               sys.executable, RECIPES_PY] + list(args)
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True)
+        assert r.returncode == 0, "traced run failed (exit %d):\n%s\n%s" % (r.returncode, r.stdout[-4000:], r.stderr[-4000:])
+        names = set()
+        files = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
+        assert files, "the kernel trace wrote no CSV:\n" + r.stderr[-2000:]
+        for f in files:
+            with open(f, newline="") as fh:
+                for row in csv.DictReader(fh):
+                    names.add(row["Kernel_Name"])
+    mangled = sorted(n for n in names if n.startswith("_Z"))
+    keys = {kernel_inventory.normalise(n) for n in names if not n.startswith("_Z")}
+    keys |= {kernel_inventory.normalise(n) for n in kernel_inventory.demangle(mangled)}
+    return keys
+
+
+@pytest.mark.gpu
+def test_every_covered_instance_is_launched():
+    """the instances the recipes claim (every shipped instance outside tests/golden/uncovered_kernel_instances.txt) - launched -
+    allowlist = {}, and no allowlisted instance is launched"""
+    inv = kernel_inventory.instances()
+    launched = _traced([], 900)
+    # the trace's names normalise to the inventory's: the headline kernel (the block pass behind the recipes' 1-stage column
+    # passes) by name
+    assert "fused_kernel<ArithF64,14,false,0,false,false,false>" in inv
+    assert "fused_kernel<ArithF64,14,false,0,false,false,false>" in launched
+    covered = set(inv) - kernel_recipes.uncovered()
+    missing = sorted(covered - launched - set(kernel_recipes.ALLOWLIST))
+    assert not missing, "instances the recipes name but never launch: %s" % missing
+    stale = sorted(set(kernel_recipes.ALLOWLIST) & launched)
+    assert not stale, "allowlisted instances that were launched: %s" % stale
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("route,want,unwanted", [
+    ("transform", "team_kernel", "onepass_kernel"),
+    ("fwd_mul", "team_mul_kernel", "onepass_mul_kernel"),
+])
+def test_explicit_xcd_local_wins_over_the_automatic_one_pass_choice(route, want, unwanted):
+    """N = 2^15, 50-bit prime, NTT_OPT_XCD_LOCAL 1, 131 polynomials (2 x 131 >= the CU count: the automatic one-pass choice
+    would take it): the trace shows the XCD-local kernel and no one-pass kernel"""
+    fams = {kernel_inventory.parse(k).family for k in _traced(["--precedence", route], 300)}
+    assert want in fams, (route, sorted(f for f in fams if f))
+    assert unwanted not in fams, (route, sorted(f for f in fams if f))

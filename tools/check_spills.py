@@ -9,14 +9,32 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
+BUNDLE_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+
+
 def kernels_of(obj):
+    """kernels of an object file -- or of a linked library, whose .hip_fatbin holds one bundle per translation unit"""
+    out = []
     with tempfile.TemporaryDirectory() as d:
-        fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "dev.co")
+        fat = os.path.join(d, "fat.bin")
         subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat])
-        subprocess.check_call([LLVM + "/clang-offload-bundler", "--unbundle", "--type=o",
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat, "--output=" + co],
-                              stderr=subprocess.DEVNULL)
-        txt = subprocess.check_output([LLVM + "/llvm-readelf", "--notes", co], text=True)
+        with open(fat, "rb") as f:
+            blob = f.read()
+        starts = [m.start() for m in re.finditer(re.escape(BUNDLE_MAGIC), blob)]
+        if not starts:
+            raise RuntimeError("%s: no uncompressed offload bundle in .hip_fatbin (%d bytes)" % (obj, len(blob)))
+        for i, s in enumerate(starts):
+            one, co = os.path.join(d, "one.bin"), os.path.join(d, "dev.co")
+            with open(one, "wb") as f:
+                f.write(blob[s:starts[i + 1] if i + 1 < len(starts) else len(blob)])
+            subprocess.check_call([LLVM + "/clang-offload-bundler", "--unbundle", "--type=o",
+                                   "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + one, "--output=" + co],
+                                  stderr=subprocess.DEVNULL)
+            out += _kernels_of_notes(subprocess.check_output([LLVM + "/llvm-readelf", "--notes", co], text=True))
+    return out
+
+
+def _kernels_of_notes(txt):
     # amdhsa.kernels is a YAML list; every kernel entry starts with "  - .<first key>:" (keys are sorted, so
     # .group_segment_fixed_size precedes .name inside one entry)
     out, cur = [], None
