@@ -16,7 +16,9 @@ OBJS     = $(CSRC)/inst_f64k0.o $(CSRC)/inst_f64k1.o $(CSRC)/inst_f64k18.o $(CSR
            $(CSRC)/inst_u64.o $(CSRC)/inst_u64r4.o \
            $(CSRC)/inst_dot_f64k0.o $(CSRC)/inst_dot_f64k1.o $(CSRC)/inst_dot_f64k18.o $(CSRC)/inst_dot_f64w.o $(CSRC)/inst_dot_u64.o \
            $(CSRC)/inst_mul_f64k0.o $(CSRC)/inst_mul_f64k1.o $(CSRC)/inst_mul_f64k18.o $(CSRC)/inst_mul_f64w.o $(CSRC)/inst_mul_u64.o \
-           $(CSRC)/inst_team_f64k0.o $(CSRC)/inst_team_f64k1.o $(CSRC)/inst_team_f64k18.o $(CSRC)/inst_team_f64w.o $(CSRC)/ntt_host.o
+           $(CSRC)/inst_team_f64k0.o $(CSRC)/inst_team_f64k1.o $(CSRC)/inst_team_f64k18.o $(CSRC)/inst_team_f64w.o \
+           $(CSRC)/rescale_f64k0.o $(CSRC)/rescale_f64k1.o $(CSRC)/rescale_f64k18.o $(CSRC)/rescale_f64w.o $(CSRC)/rescale_coef.o \
+           $(CSRC)/ntt_host.o
 # the kernel translation units see the kernel headers only; the host layer also the public headers
 KHDRS    = $(wildcard $(CSRC)/*.h)
 HDRS     = $(KHDRS) $(wildcard $(CSRC)/host/*.inc) $(wildcard include/*.h) $(wildcard include/internal/*.h)

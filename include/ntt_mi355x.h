@@ -118,6 +118,10 @@ typedef enum ntt_option {
                           * every second CU a polynomial (measured crossover: 64..96 polynomials) and neither NTT_OPT_XCD_LOCAL 1 nor
                           * NTT_OPT_BLOCK_LOG is set (explicit options win).  Calls that ask for lazy outputs get canonical words from it
                           * (inside the lazy ranges).  Results are identical. */
+  NTT_OPT_RESCALE_FUSED = 17, /* ntt_rns_rescale_batch in the NTT domain: 1 (default) = one forward-transform launch per run of
+                          * kept limbs with the rescale in its prologue and epilogue where it is built (FP64 policies, N = 2^6..2^14);
+                          * 0 = inverse, element-wise kernel and forward transform around every run.  Read from plans[0]; results
+                          * are identical */
   NTT_OPT_FUSED_PRODUCT = 5 /* N = 2^8..2^17, FP64: 1 (default) = ntt_negacyclic_mul_batch as ONE launch that takes both
                           * operands through the forward stages, multiplies in registers and runs the inverse: 24N bytes up to
                           * 2^14; from 2^23 coefficients per operand of N >= 2^15 on likewise one launch (all limbs of an RNS set
@@ -284,6 +288,27 @@ NTT_API int ntt_rns_mul_transformed_batch(int nlimbs, ntt_plan *const *plans, ui
                                           uint64_t batch, unsigned flags, void *stream);
 NTT_API int ntt_rns_fwd_mul_batch(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, uint64_t *d_a, const uint64_t *d_bhat,
                                   uint64_t batch, unsigned flags, void *stream);
+
+/* ---- RNS rescale (modulus drop; the CKKS step after every multiplication).  An RNS polynomial of nlimbs = L+1 limbs with
+ * primes q_0 .. q_L (plans[l], same N and device) holds x in [0, Q), Q = q_0 * ... * q_L.  After the call limbs 0 .. L-1 hold
+ * y = round(x / q_L) mod Q / q_L (q_L is odd: no ties), or floor(x / q_L) with NTT_RESCALE_FLOOR, in the domain they came in;
+ * for a centred x the result is the same modulo Q / q_L.  Limb l is (c_l - u_l) * q_L^-1 mod q_l with t = limb L's
+ * coefficients and u_l = ((t + h) mod q_L) mod q_l - (h mod q_l), h = (q_L - 1) / 2 (floor: u_l = t mod q_l); in the NTT
+ * domain c_l^ - fwd(u_l).  In place, canonical inputs and outputs, the layouts of the RNS forms ([limb][batch][N]; _strided:
+ * any strides the forms above accept).  The dropped limb's slot: after an NTT_RESCALE_TRANSFORMED call it holds t (its
+ * inverse transform), after a coefficient call it is unchanged.  Coefficients: one launch per 16 kept limbs, 8N(2L+1) bytes.
+ * NTT domain: the inverse of limb L, then per run of compatible kept limbs one forward-transform launch that reduces t in its
+ * prologue and subtracts and scales in its epilogue (FP64 policies, N = 2^6..2^14: 8N(2L+3) bytes in all, against 8N(6L+3)
+ * for inverse + element-wise + forward), else that sandwich for the run (NTT_OPT_RESCALE_FUSED).  NTT_ERR_ARG, nothing
+ * written: nlimbs < 2, plans that differ in N or device, q_L equal to a kept prime, overlapping strides, an unknown flag, a
+ * missing table (the inverse of plans[L], the forward tables of the kept limbs, the inverse tables where the sandwich
+ * serves).  Allocates nothing, does not synchronise the host, issues no memset: capturable. ---- */
+enum { NTT_RESCALE_TRANSFORMED = 1, /* operands in the NTT domain (bit-reversed, as ntt_fwd_batch leaves them) */
+       NTT_RESCALE_FLOOR       = 2  /* floor(x / q_L) instead of round(x / q_L) */ };
+NTT_API int ntt_rns_rescale_batch(int nlimbs, ntt_plan *const *plans, uint64_t *d_a, uint64_t batch, unsigned flags,
+                                  void *stream);
+NTT_API int ntt_rns_rescale_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_a, uint64_t limb_stride,
+                                          uint64_t poly_stride, uint64_t batch, unsigned flags, void *stream);
 
 /* ---- caller-native layouts (round 5).  The entry points above take RNS operands as [limb][batch][N].  SURVEY 8(d) config 5
  * -- and every FHE library -- keeps a polynomial's limbs side by side: [batch][prime][N].  The *_strided forms take the two

@@ -43,6 +43,8 @@ MUL_LAZY_IN, MUL_B_BROADCAST, MUL_ACCUMULATE = 1, 2, 4
 OPT_MAX_GRID, OPT_CHUNK_MIB, OPT_F64_CLASS, OPT_TWO_PHASE, OPT_FUSED_PRODUCT, OPT_BLOCK_LOG = 1, 2, 3, 4, 5, 6
 OPT_XCD_LOCAL, OPT_XCD_LOCAL_LAG, OPT_XCD_LOCAL_WGS_PER_CU, OPT_INT_WIDE, OPT_BLOCK_OVERSUB = 7, 8, 9, 10, 11
 OPT_RNS_LAUNCH, OPT_DOT_FUSED, OPT_MAX_BATCH_HINT, OPT_CTL_ALLOCATIONS, OPT_ONE_PASS = 12, 13, 14, 15, 16
+OPT_RESCALE_FUSED = 17
+RESCALE_TRANSFORMED, RESCALE_FLOOR = 1, 2
 
 #: every symbol include/ntt_mi355x.h and the reference-named headers declare
 EXPORTED_SYMBOLS = [
@@ -54,7 +56,8 @@ EXPORTED_SYMBOLS = [
     "ntt_rns_negacyclic_mul_batch", "ntt_inv_product_batch", "ntt_inv_dot_batch", "ntt_mul_transformed_batch",
     "ntt_rns_inv_dot_batch", "ntt_rns_mul_transformed_batch", "ntt_fwd_mul_batch", "ntt_rns_fwd_mul_batch",
     "ntt_rns_fwd_batch_strided", "ntt_rns_inv_batch_strided", "ntt_rns_negacyclic_mul_batch_strided", "ntt_rns_inv_dot_batch_strided",
-    "ntt_rns_mul_transformed_batch_strided", "ntt_rns_fwd_mul_batch_strided", "ntt_transform_batch_strided", "ntt_transform_ptrs", "ntt_rns_transform_ptrs", "ntt_transform_dev_ptrs", "ntt_rns_transform_dev_ptrs", "ntt_inv_dot_dev_ptrs", "ntt_fwd_mul_dev_ptrs", "ntt_negacyclic_mul_dev_ptrs",
+    "ntt_rns_mul_transformed_batch_strided", "ntt_rns_fwd_mul_batch_strided", "ntt_rns_rescale_batch", "ntt_rns_rescale_batch_strided",
+    "ntt_transform_batch_strided", "ntt_transform_ptrs", "ntt_rns_transform_ptrs", "ntt_transform_dev_ptrs", "ntt_rns_transform_dev_ptrs", "ntt_inv_dot_dev_ptrs", "ntt_fwd_mul_dev_ptrs", "ntt_negacyclic_mul_dev_ptrs",
     "ntt_rns_inv_dot_dev_ptrs", "ntt_rns_fwd_mul_dev_ptrs", "ntt_rns_negacyclic_mul_dev_ptrs", "ntt_dev_malloc", "ntt_dev_free", "ntt_dev_mem_info",
     "ntt_h2d", "ntt_d2h", "ntt_stream_create", "ntt_stream_destroy", "ntt_stream_sync",
     "ntt_event_create", "ntt_event_destroy", "ntt_event_record", "ntt_event_elapsed_ms",
@@ -128,6 +131,8 @@ _sig("ntt_rns_inv_dot_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP,
 _sig("ntt_rns_mul_transformed_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint64,
      C.c_uint, VOIDP)
 _sig("ntt_rns_fwd_mul_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_rescale_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_rescale_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_transform_batch_strided", C.c_int, VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_transform_ptrs", C.c_int, VOIDP, C.POINTER(VOIDP), C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_transform_ptrs", C.c_int, C.c_int, C.POINTER(VOIDP), C.POINTER(VOIDP), C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
@@ -508,6 +513,13 @@ def rns_mul_transformed(plans, dc, da, dbhat, batch, flags=0, stream=None, layou
         _check(_lib.ntt_rns_mul_transformed_batch_strided(len(plans), _plan_array(plans), dc, da, dbhat, layout[0], layout[1], batch, flags, stream))
     else:
         _check(_lib.ntt_rns_mul_transformed_batch(len(plans), _plan_array(plans), dc, da, dbhat, batch, flags, stream))
+
+
+def rns_rescale(plans, dptr, batch, flags=0, stream=None, layout=None):
+    """drop the last prime of plans (in place): limbs 0 .. L-1 become round(x / q_L) (RESCALE_FLOOR: floor), in the NTT domain with
+    RESCALE_TRANSFORMED; limbs laid out [limb][batch][N], layout = (limb_stride, poly_stride) in words for any other placement"""
+    if layout: _check(_lib.ntt_rns_rescale_batch_strided(len(plans), _plan_array(plans), dptr, layout[0], layout[1], batch, flags, stream))
+    else: _check(_lib.ntt_rns_rescale_batch(len(plans), _plan_array(plans), dptr, batch, flags, stream))
 
 
 def batch_multi(plans, dptrs, batches, inverse=False):
