@@ -121,7 +121,7 @@ typedef enum ntt_option {
   NTT_OPT_RESCALE_FUSED = 17, /* ntt_rns_rescale_batch in the NTT domain: 1 (default) = one forward-transform launch per run of
                           * kept limbs with the rescale in its prologue and epilogue where it is built (FP64 policies, N = 2^6..2^14);
                           * 0 = inverse, element-wise kernel and forward transform around every run.  Read from plans[0]; results
-                          * are identical */
+                          * are identical.  The same switch selects the route of ntt_rns_mod_down_batch in the NTT domain */
   NTT_OPT_FUSED_PRODUCT = 5 /* N = 2^8..2^17, FP64: 1 (default) = ntt_negacyclic_mul_batch as ONE launch that takes both
                           * operands through the forward stages, multiplies in registers and runs the inverse: 24N bytes up to
                           * 2^14; from 2^23 coefficients per operand of N >= 2^15 on likewise one launch (all limbs of an RNS set
@@ -309,6 +309,41 @@ NTT_API int ntt_rns_rescale_batch(int nlimbs, ntt_plan *const *plans, uint64_t *
                                   void *stream);
 NTT_API int ntt_rns_rescale_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_a, uint64_t limb_stride,
                                           uint64_t poly_stride, uint64_t batch, unsigned flags, void *stream);
+
+/* ---- RNS base conversion for hybrid key switching (relinearisation, rotation): ModUp and ModDown.  A basis B = {b_i} with
+ * product B, b^_i = B / b_i; fast base conversion (the HPS / BEHZ form, integer sums, bit-exact):
+ *     FastBConv_{B->p}(x) = ( sum_i [x_i * b^_i^-1]_{b_i} * b^_i ) mod p,
+ * which for x in [0, B) equals x + u B (mod p) for an integer 0 <= u < |B|.
+ * ModUp: the operand is one RNS polynomial set over the extended basis Q u P, plans[0 .. nlimbs-1] (same N and device), in the
+ * layouts of the RNS forms ([limb][batch][N]; _strided: any strides those accept).  Limbs [first, first + count), 1 <= count <= 16,
+ * are the digit (the source basis B); afterwards every other limb l holds FastBConv_{B->q_l} of the digit, the digit's limbs are
+ * unchanged.  Without NTT_MODUP_TRANSFORMED everything is in coefficients; with it everything comes and goes in the NTT domain:
+ * the digit's limbs are inverse-transformed in place and converted, then every limb is forward-transformed (the digit's limbs
+ * come back bit-identical: both transforms are exact bijections on canonical words).  In place on one operand because the
+ * destination limbs of an FHE library's ciphertext ([batch][limb][N]) sit below the digit, above it and in P -- no regular
+ * spacing.  Coefficients: one launch per 16 destination limbs, the digit read once per launch.
+ * ModDown: plans[0 .. nq-1] are the Q primes, plans[nq .. nq+np-1] the P primes, 1 <= np <= 16; with t_j the coefficients of P limb
+ * j and h = (P - 1) / 2 (0 with NTT_MODDOWN_FLOOR), Q limb l becomes ( c_l - FastBConv_{P->q_l}([t + h]_P) + [h]_{q_l} ) * P^-1 mod
+ * q_l -- in the NTT domain the subtrahend is the forward transform of that coefficient vector.  For x in [0, QP) that is
+ * round(x / P) - v (floor: floor(x / P) - v) mod Q with 0 <= v < np; with np = 1 it is exactly ntt_rns_rescale_batch with the same
+ * flags.  The P slots follow the rescale: after a TRANSFORMED call they hold their coefficients, after a coefficient call they are
+ * unchanged.  Coefficients: one launch per 16 Q limbs, the P limbs read once per launch (8N(2nq + np) bytes); NTT domain: the
+ * inverse of the P limbs, then per run of compatible Q limbs one forward-transform launch that forms the subtrahend in its
+ * prologue and subtracts and scales in its epilogue (FP64 policies, N = 2^6..2^14: 8N(2nq + 3np) bytes in all), else inverse,
+ * element-wise kernel and forward transform for the run (NTT_OPT_RESCALE_FUSED on plans[0]).
+ * All four: in place, canonical inputs and outputs.  NTT_ERR_ARG, nothing written: counts out of range, plans that differ in N or
+ * device, a prime that appears twice among the operand's plans, an unknown flag, overlapping strides, a table the route needs
+ * that a plan lacks.  Allocate nothing, do not synchronise the host, issue no memset: capturable. ---- */
+enum { NTT_MODUP_TRANSFORMED = 1 /* the operand in the NTT domain (bit-reversed, as ntt_fwd_batch leaves it) */ };
+enum { NTT_MODDOWN_TRANSFORMED = 1, NTT_MODDOWN_FLOOR = 2 }; /* the values of NTT_RESCALE_* on purpose */
+NTT_API int ntt_rns_mod_up_batch(int nlimbs, ntt_plan *const *plans, uint64_t *d_a, int first, int count, uint64_t batch,
+                                 unsigned flags, void *stream);
+NTT_API int ntt_rns_mod_up_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_a, int first, int count,
+                                         uint64_t limb_stride, uint64_t poly_stride, uint64_t batch, unsigned flags, void *stream);
+NTT_API int ntt_rns_mod_down_batch(int nq, int np, ntt_plan *const *plans, uint64_t *d_a, uint64_t batch, unsigned flags,
+                                   void *stream);
+NTT_API int ntt_rns_mod_down_batch_strided(int nq, int np, ntt_plan *const *plans, uint64_t *d_a, uint64_t limb_stride,
+                                           uint64_t poly_stride, uint64_t batch, unsigned flags, void *stream);
 
 /* ---- caller-native layouts (round 5).  The entry points above take RNS operands as [limb][batch][N].  SURVEY 8(d) config 5
  * -- and every FHE library -- keeps a polynomial's limbs side by side: [batch][prime][N].  The *_strided forms take the two

@@ -45,6 +45,8 @@ OPT_XCD_LOCAL, OPT_XCD_LOCAL_LAG, OPT_XCD_LOCAL_WGS_PER_CU, OPT_INT_WIDE, OPT_BL
 OPT_RNS_LAUNCH, OPT_DOT_FUSED, OPT_MAX_BATCH_HINT, OPT_CTL_ALLOCATIONS, OPT_ONE_PASS = 12, 13, 14, 15, 16
 OPT_RESCALE_FUSED = 17
 RESCALE_TRANSFORMED, RESCALE_FLOOR = 1, 2
+MODUP_TRANSFORMED = 1
+MODDOWN_TRANSFORMED, MODDOWN_FLOOR = 1, 2
 
 #: every symbol include/ntt_mi355x.h and the reference-named headers declare
 EXPORTED_SYMBOLS = [
@@ -57,6 +59,7 @@ EXPORTED_SYMBOLS = [
     "ntt_rns_inv_dot_batch", "ntt_rns_mul_transformed_batch", "ntt_fwd_mul_batch", "ntt_rns_fwd_mul_batch",
     "ntt_rns_fwd_batch_strided", "ntt_rns_inv_batch_strided", "ntt_rns_negacyclic_mul_batch_strided", "ntt_rns_inv_dot_batch_strided",
     "ntt_rns_mul_transformed_batch_strided", "ntt_rns_fwd_mul_batch_strided", "ntt_rns_rescale_batch", "ntt_rns_rescale_batch_strided",
+    "ntt_rns_mod_up_batch", "ntt_rns_mod_up_batch_strided", "ntt_rns_mod_down_batch", "ntt_rns_mod_down_batch_strided",
     "ntt_transform_batch_strided", "ntt_transform_ptrs", "ntt_rns_transform_ptrs", "ntt_transform_dev_ptrs", "ntt_rns_transform_dev_ptrs", "ntt_inv_dot_dev_ptrs", "ntt_fwd_mul_dev_ptrs", "ntt_negacyclic_mul_dev_ptrs",
     "ntt_rns_inv_dot_dev_ptrs", "ntt_rns_fwd_mul_dev_ptrs", "ntt_rns_negacyclic_mul_dev_ptrs", "ntt_dev_malloc", "ntt_dev_free", "ntt_dev_mem_info",
     "ntt_h2d", "ntt_d2h", "ntt_stream_create", "ntt_stream_destroy", "ntt_stream_sync",
@@ -133,6 +136,12 @@ _sig("ntt_rns_mul_transformed_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP)
 _sig("ntt_rns_fwd_mul_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_rescale_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_rescale_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_mod_up_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_int, C.c_int, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_mod_up_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64,
+     C.c_uint, VOIDP)
+_sig("ntt_rns_mod_down_batch", C.c_int, C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_mod_down_batch_strided", C.c_int, C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint,
+     VOIDP)
 _sig("ntt_transform_batch_strided", C.c_int, VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_transform_ptrs", C.c_int, VOIDP, C.POINTER(VOIDP), C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_transform_ptrs", C.c_int, C.c_int, C.POINTER(VOIDP), C.POINTER(VOIDP), C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
@@ -520,6 +529,24 @@ def rns_rescale(plans, dptr, batch, flags=0, stream=None, layout=None):
     RESCALE_TRANSFORMED; limbs laid out [limb][batch][N], layout = (limb_stride, poly_stride) in words for any other placement"""
     if layout: _check(_lib.ntt_rns_rescale_batch_strided(len(plans), _plan_array(plans), dptr, layout[0], layout[1], batch, flags, stream))
     else: _check(_lib.ntt_rns_rescale_batch(len(plans), _plan_array(plans), dptr, batch, flags, stream))
+
+
+def rns_mod_up(plans, dptr, first, count, batch, flags=0, stream=None, layout=None):
+    """ModUp in place: every limb outside the digit [first, first + count) of plans gets FastBConv of the digit (MODUP_TRANSFORMED:
+    the operand in the NTT domain); limbs laid out [limb][batch][N], layout = (limb_stride, poly_stride) in words otherwise"""
+    if layout:
+        _check(_lib.ntt_rns_mod_up_batch_strided(len(plans), _plan_array(plans), dptr, first, count, layout[0], layout[1], batch, flags,
+                                                 stream))
+    else: _check(_lib.ntt_rns_mod_up_batch(len(plans), _plan_array(plans), dptr, first, count, batch, flags, stream))
+
+
+def rns_mod_down(plans, np_, dptr, batch, flags=0, stream=None, layout=None):
+    """ModDown in place: the last np_ plans are P; the Q limbs become round(x / P) - v (MODDOWN_FLOOR: floor), in the NTT domain with
+    MODDOWN_TRANSFORMED; limbs laid out [limb][batch][N], layout = (limb_stride, poly_stride) in words otherwise"""
+    nq = len(plans) - np_
+    if layout:
+        _check(_lib.ntt_rns_mod_down_batch_strided(nq, np_, _plan_array(plans), dptr, layout[0], layout[1], batch, flags, stream))
+    else: _check(_lib.ntt_rns_mod_down_batch(nq, np_, _plan_array(plans), dptr, batch, flags, stream))
 
 
 def batch_multi(plans, dptrs, batches, inverse=False):

@@ -1,0 +1,200 @@
+/*
+ * ntt_kernels_keyswitch.h -- moddown_fwd_kernel: the NTT-domain RNS ModDown (divide by the product P of the special primes, drop
+ * the P limbs) for a run of Q limbs in ONE launch.  Included by the keyswitch_f64*.hip units only (the host layer sees the
+ * launchers of ntt_keyswitch.h).
+ *
+ * rescale_fwd_kernel's structure (ntt_kernels_rescale.h) with one change, the prologue.  Per block of Q limb l (FP64 policies,
+ * N = 2^6..2^14, one block = one polynomial):
+ *   prologue  the np P limbs' blocks (already inverse-transformed) as raw words -- up to 2^61, not exact in a double -- are reduced
+ *             in integer arithmetic to u_l = FastBConv_{P->q_l}([t + h]_P) - [h]_{q_l} (ntt_keyswitch.h), then converted;
+ *   stages    the forward block stages, unchanged;
+ *   epilogue  a quarter-tile at a time: c^ read in the last group's layout, (c^ - x) * P^-1 with the limb's FP64 constants.
+ * 8N np bytes of t and 16N of c^ per limb-polynomial.  [p^_j]_{q_l} = prod_{k != j} p_k mod q_l is formed once per workgroup
+ * (its limb is the grid's y index) into LDS: no table of np x nq words has room beside the run's limb records in the kernel
+ * arguments.  With np = 1 the prologue is the rescale's (moddown_digit1).
+ */
+#pragma once
+#include <hip/hip_runtime.h>
+
+/* the block kernels' pieces (Geom, KArgs, limb_params, the stage groups and exchanges) -- not all of ntt_kernels.h, whose launch
+ * section defines a kernel of its own (team_ctl_clear_kernel) in every unit that includes it */
+#include "ntt_core.h"
+#include "ntt_passplan.h"
+#include "ntt_kernels_block.h"
+#include "ntt_keyswitch.h"
+
+namespace ntt {
+
+template <class A> struct KModDown {
+  KArgs<A>        k;  /* k.a = the run's first Q limb (c^), limb_stride / poly_stride of the operand, the run's limb records */
+  const uint64_t *t;  /* the first P limb's coefficients; P limb j at t + j * k.limb_stride */
+  int             np;
+  BconvSrc        pl[kBconvLimbs];
+  BconvDst        ql[kBconvLimbs];
+};
+
+template <class A, int LOGN, int KSH>
+__global__ void __launch_bounds__((Geom<LOGN, false, flavor_of<A>()>::WG), (Geom<LOGN, false, flavor_of<A>()>::WPS))
+  moddown_fwd_kernel(const KModDown<A> kr)
+{
+  static_assert(A::kCompact, "built for the FP64 policies");
+  uint32_t        bid, gdim, limb;
+  const Params<A> p = limb_params<A, false, true>(kr.k, bid, gdim, limb);
+  using P = Plan<LOGN>;
+  using G = Geom<LOGN, false, flavor_of<A>()>;
+  constexpr uint32_t MASK   = fused_mask<A, LOGN, false, KSH>();
+  constexpr int      LDS_TW = G::LDS_TW;
+  __shared__ typename A::val lds_all[G::BPW * P::LDS_ELEMS + LDS_TW];
+  __shared__ uint64_t        ghat[kBconvLimbs]; /* [p^_j]_{q_l} */
+  const uint32_t       tid = threadIdx.x;
+  const uint32_t       sub = tid >> P::LT;
+  const uint32_t       t   = tid & (P::T - 1);
+  typename A::val *    lds = lds_all + sub * P::LDS_ELEMS;
+  const BconvDst       ql  = kr.ql[limb];
+  const int            np  = kr.np;
+  const lds_ctw_ptr<A> gtw = (lds_ctw_ptr<A>)reinterpret_cast<typename A::ctw *>(lds_all + G::BPW * P::LDS_ELEMS);
+  if constexpr(LDS_TW > 0) fill_lds_tables<A, LOGN, false>(reinterpret_cast<typename A::ctw *>(lds_all + G::BPW * P::LDS_ELEMS), p, 0u, tid);
+  if(np > 1) {
+    if(tid < (uint32_t)np) {
+      /* prod_{k != j} p_k mod q_l: g < q_l and p_k < 2^61, each product below 2^122 (bconv_reduce takes any 128-bit word) */
+      uint64_t g = 1;
+      for(int k = 0; k < np; k++) {
+        if(k == (int)tid) continue;
+        const uint64_t pk = kr.pl[k].p;
+        g                 = bconv_reduce(mulhi64(g, pk), g * pk, ql);
+        g                 = g >= ql.q ? g - ql.q : g;
+      }
+      ghat[tid] = g;
+    }
+  }
+  if constexpr(LDS_TW > 0) __syncthreads();
+  else if(np > 1) __syncthreads();
+  /* P^-1 mod q_l as a balanced double, |.| <= q/2 (the multiplier of every product of this workgroup) */
+  const double sb = A::reduce(A::u64_to_f64_lt52(ql.s), p.c);
+  for(uint64_t b0 = (uint64_t)bid * G::BPW; b0 < p.nblocks; b0 += (uint64_t)gdim * G::BPW) {
+    uint64_t   b    = b0 + sub;
+    const bool live = b < p.nblocks;
+    if(!live) b = p.nblocks - 1;
+    const uint64_t  off  = blk_off<LOGN>(p, b); /* (whole polynomials: s0 = 0) */
+    const uint64_t *tblk = kr.t + off;
+    uint64_t *      cblk = p.a + off;
+    uint32_t        tg   = t; /* (an opaque copy per block, as fwd_mul_kernel's plain loop) */
+    asm volatile("" : "+v"(tg));
+    typename A::val x[kE];
+    {
+      uint64_t raw[kE];
+      if(np == 1) {
+        const BconvSrc s0 = kr.pl[0];
+        static_for<0, kE>([&](auto ee) {
+          constexpr int   E   = decltype(ee)::value;
+          const uint64_t *row = tblk + ((uint32_t)E << P::LT);
+          raw[E]              = moddown_digit1(stream_load(coef_at(row, tg)), s0, ql);
+        });
+      } else {
+        /* half a tile at a time: the 128-bit sums of 8 words stay in registers beside nothing else (x is not live yet) */
+        static_for<0, 2>([&](auto hh) {
+          constexpr int H = decltype(hh)::value;
+          uint64_t      hi[kE / 2], lo[kE / 2];
+          static_for<0, kE / 2>([&](auto ee) {
+            hi[decltype(ee)::value] = 0;
+            lo[decltype(ee)::value] = 0;
+          });
+          const uint64_t *tj = tblk;
+          for(int j = 0; j < np; j++) {
+            const BconvSrc s = kr.pl[j];
+            const uint64_t g = ghat[j];
+            static_for<0, kE / 2>([&](auto ee) {
+              constexpr int   E   = decltype(ee)::value;
+              const uint64_t *row = tj + ((uint32_t)(H * kE / 2 + E) << P::LT);
+              bconv_mac(hi[E], lo[E], bconv_digit(stream_load(coef_at(row, tg)), s), g);
+            });
+            tj += kr.k.limb_stride;
+          }
+          static_for<0, kE / 2>([&](auto ee) {
+            constexpr int E     = decltype(ee)::value;
+            raw[H * kE / 2 + E] = moddown_digit(hi[E], lo[E], ql);
+          });
+        });
+      }
+      convert_inputs<A, false>(x, raw, false, p.c);
+    }
+    run_group<A, LOGN, 0, false, MASK, (G::TBL(0) > 0)>(x, tg, 0u, p, gtw);
+    static_for<0, P::NG - 1>([&](auto gg) {
+      constexpr int GI = decltype(gg)::value;
+      exchange<A, LOGN, GI, GI + 1>(x, tg, lds);
+      run_group<A, LOGN, GI + 1, false, MASK, (G::TBL(GI + 1) > 0)>(x, tg, 0u, p, gtw + G::TBL_OFF(GI + 1));
+    });
+    static_for<0, 4>([&](auto qq) {
+      constexpr int Q = decltype(qq)::value;
+      uint64_t      rc[kE], u[kE];
+      sched_fence();
+      load_last_raw<LOGN, 4 * Q, 4 * Q + 4>(rc, tg, cblk);
+      static_for<4 * Q, 4 * Q + 4>([&](auto ee) {
+        constexpr int E = decltype(ee)::value;
+        const double  d = A::reduce(A::u64_to_f64_lt52(rc[E]) - A::reduce(x[E], p.c), p.c); /* |c^ - x| < 1.5 q before */
+        u[E]            = A::mul_store(A::mulmod_c(sb, d, p.c), p.c);
+      });
+      if(live) store_last_raw<LOGN, 4 * Q, 4 * Q + 4>(u, tg, cblk);
+      sched_fence();
+    });
+  }
+}
+
+template <class A, int LOGN, int KSH> hipError_t launch_moddown_fwd_n(const ModDownFwdArgs &ma)
+{
+  using G = Geom<LOGN, false, flavor_of<A>()>;
+  if(ma.nlimbs < 1 || ma.nlimbs > kBconvLimbs || ma.nlimbs > kMaxLimbs || ma.np < 1 || ma.np > kBconvLimbs) return hipErrorInvalidValue;
+  KModDown<A>       kr{};
+  const LimbRec<A> *recs = static_cast<const LimbRec<A> *>(ma.limbs);
+  for(int l = 0; l < ma.nlimbs; l++) {
+    kr.k.limbs[l] = recs[l];
+    kr.ql[l]      = ma.ql[l];
+  }
+  for(int j = 0; j < ma.np; j++) kr.pl[j] = ma.pl[j];
+  kr.k.a           = ma.c;
+  kr.k.limb_stride = ma.limb_stride;
+  kr.k.poly_stride = ma.poly_stride ? ma.poly_stride : (1ull << ma.logn);
+  kr.k.logn        = ma.logn;
+  kr.k.s0          = 0;
+  kr.k.nblocks     = ma.batch;
+  kr.t             = ma.t;
+  kr.np            = ma.np;
+  /* the grid of launch_rescale_fwd_n: the forward block kernel's plain loop, the x extent a multiple of 8 */
+  const uint64_t nl  = (uint64_t)ma.nlimbs;
+  uint64_t       wgs = (ma.batch + G::BPW - 1) / G::BPW;
+  uint64_t       cap = 1ull << 20;
+  if(G::PERSISTENT) {
+    constexpr int by_lds   = G::WG_PER_CU0;
+    constexpr int by_waves = (G::WPS * 4 * 64) / G::WG;
+    constexpr int per_cu   = by_lds < by_waves ? by_lds : by_waves;
+    cap                    = (uint64_t)(ma.num_cus > 0 ? ma.num_cus : 256) * (per_cu > 0 ? per_cu : 1);
+  } else if(G::LDS_TW > 0) {
+    constexpr int per_cu = G::WG_PER_CU0 < 8 ? G::WG_PER_CU0 : 8;
+    cap                  = (uint64_t)(ma.num_cus > 0 ? ma.num_cus : 256) * (per_cu > 0 ? per_cu : 1) * 4;
+  }
+  if(ma.max_grid > 0) cap = (uint64_t)ma.max_grid;
+  cap = cap / nl > 8 ? (cap / nl) & ~7ull : 8;
+  if(wgs > cap) wgs = cap;
+  wgs = (wgs + 7) & ~7ull; /* (workgroups past the last block exit at once) */
+  if(ma.batch == 0) return hipSuccess;
+  kr.k.wgs_per_limb = (uint32_t)wgs;
+  hipLaunchKernelGGL((moddown_fwd_kernel<A, LOGN, KSH>), dim3((unsigned)wgs, (unsigned)nl), dim3(G::WG), 0, ma.stream, kr);
+  return hipGetLastError();
+}
+
+template <class A, int KSH> hipError_t launch_moddown_fwd_impl(const ModDownFwdArgs &ma)
+{
+  switch(ma.logn) {
+#define NTT_MODDOWN_CASE(LN) \
+  case LN: return launch_moddown_fwd_n<A, LN, KSH>(ma);
+    NTT_MODDOWN_CASE(6) NTT_MODDOWN_CASE(7) NTT_MODDOWN_CASE(8) NTT_MODDOWN_CASE(9) NTT_MODDOWN_CASE(10) NTT_MODDOWN_CASE(11)
+    NTT_MODDOWN_CASE(12) NTT_MODDOWN_CASE(13) NTT_MODDOWN_CASE(14)
+#undef NTT_MODDOWN_CASE
+    default: return hipErrorNotSupported;
+  }
+}
+
+#define NTT_DEFINE_LAUNCH_MODDOWN_FWD(A, KSH) \
+  template <> hipError_t launch_moddown_fwd<A, KSH>(const ModDownFwdArgs &ma) { return launch_moddown_fwd_impl<A, KSH>(ma); }
+
+} // namespace ntt
