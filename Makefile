@@ -83,3 +83,20 @@ build/skel5: tools/skel5.hip
 	mkdir -p build
 	$(HIPCC) -O3 --offload-arch=$(ARCH) -std=c++17 -ffp-contract=off -o $@ tools/skel5.hip
 .PHONY: skel5
+
+# what every launcher would launch, recorded instead of launched (host only, no device): for comparing two versions of the launch
+# layer -- $(PROBE_OUT)/launch_probe_<pair> > file for each, the same with PROBE_CSRC=<the other csrc> PROBE_OUT=<another directory>,
+# then cmp (tools/launch_probe.hip).  The probes are rebuilt on every call: which headers a program on disk was built against is not
+# something make can see.
+PROBE_CSRC ?= $(CSRC)
+PROBE_OUT  ?= build
+PROBE_PAIRS = f64k0:ArithF64:0:1 f64k1:ArithF64:1:1 f64k18:ArithF64:18:1 f64w:ArithF64W:0:1 u64:ArithU64:0:2 \
+              u64x_k0:ArithU64X<0>:0:2 u64x_k1:ArithU64X<1>:1:2 u64x_k3:ArithU64X<3>:3:2 u64r4:ArithU64R4:0:3
+launch-probe: $(foreach p,$(PROBE_PAIRS),$(PROBE_OUT)/launch_probe_$(firstword $(subst :, ,$(p))))
+$(PROBE_OUT)/launch_probe_%: tools/launch_probe.hip FORCE
+	mkdir -p $(PROBE_OUT)
+	$(HIPCC) --cuda-host-only -O0 -std=c++17 -ffp-contract=off -Iinclude -Iinclude/internal -I$(PROBE_CSRC) \
+	  $(foreach p,$(filter $*:%,$(PROBE_PAIRS)),'-DPROBE_POLICY=$(word 2,$(subst :, ,$(p)))' -DPROBE_KSH=$(word 3,$(subst :, ,$(p))) -DPROBE_KIND=$(word 4,$(subst :, ,$(p)))) \
+	  -o $@ tools/launch_probe.hip
+FORCE:
+.PHONY: launch-probe FORCE

@@ -128,6 +128,60 @@ template <class A> struct KArgs {
   LimbRec<A>        limbs[kMaxLimbs];
 };
 
+/* The fields every launcher fills alike: limb 0's pointer, the first nrecs (at most kMaxLimbs) of the caller's HOST array of
+ * LimbRec<A>, the strides (poly_stride 0 = dense: N), the sizes.  k is value-initialised by the caller; wgs_per_limb follows the grid. */
+template <class A>
+inline void fill_kargs(KArgs<A> &k, uint64_t *a, const void *limbs, uint64_t nrecs, uint64_t limb_stride, uint64_t poly_stride, uint32_t logn,
+                       uint32_t s0, uint64_t nblocks)
+{
+  const LimbRec<A> *recs = static_cast<const LimbRec<A> *>(limbs);
+  for(uint64_t l = 0; l < nrecs && l < (uint64_t)kMaxLimbs; l++) k.limbs[l] = recs[l];
+  k.a           = a;
+  k.limb_stride = limb_stride;
+  k.poly_stride = poly_stride ? poly_stride : (1ull << logn);
+  k.logn        = logn;
+  k.s0          = s0;
+  k.nblocks     = nblocks;
+}
+
+/* Workgroups per limb (the grid's x extent) of a launch of the block kernel with geometry G over nblocks blocks per limb, nl limbs
+ * as the grid's y extent.
+ *   cap      persistent kernels: the resident workgroups (LDS- and wave-limited) times per_slot, each striding over the blocks;
+ *            kernels that fill LDS tables once per workgroup: at most 8 per CU times per_slot, each looping; otherwise 2^20.
+ *            per_slot is the caller's policy (the measured facts stand at the call sites); min_cap raises the cap, max_grid > 0
+ *            (NTT_OPT_MAX_GRID) replaces it.
+ *   limbs    the limbs of one launch share the cap.  eights: the share and the result are multiples of 8 (at least 8; workgroups
+ *            past the last block exit at once), so the result is not 0 for nblocks = 0.
+ *   s0 > 0   one block per workgroup: a persistent workgroup must always see the same block position inside the polynomial (its
+ *            LDS twiddle table depends on it), so the grid, which is its stride, is a multiple of the 2^s0 blocks per polynomial
+ *            (nblocks always is). */
+template <class G>
+inline uint64_t block_grid(uint64_t nblocks, uint32_t s0, uint64_t nl, int num_cus, int max_grid, uint64_t per_slot, bool eights = false,
+                           uint64_t min_cap = 0)
+{
+  constexpr int by_lds   = G::WG_PER_CU0;
+  constexpr int by_waves = (G::WPS * 4 * 64) / G::WG;
+  constexpr int resident = by_lds < by_waves ? by_lds : by_waves;
+  constexpr int filling  = G::WG_PER_CU0 < 8 ? G::WG_PER_CU0 : 8;
+  const uint64_t cus = (uint64_t)(num_cus > 0 ? num_cus : 256);
+  uint64_t       wgs = (nblocks + G::BPW - 1) / G::BPW;
+  uint64_t       cap = 1ull << 20;
+  if(G::PERSISTENT) cap = cus * (resident > 0 ? resident : 1) * per_slot;
+  else if(G::LDS_TW > 0) cap = cus * (filling > 0 ? filling : 1) * per_slot;
+  if(cap < min_cap) cap = min_cap;
+  if(max_grid > 0) cap = (uint64_t)max_grid;
+  if(eights) {
+    cap = cap / nl > 8 ? (cap / nl) & ~7ull : 8;
+    return ((wgs < cap ? wgs : cap) + 7) & ~7ull;
+  }
+  cap = cap / nl > 0 ? cap / nl : 1;
+  if(G::BPW == 1 && s0 > 0) {
+    if(cap < (1ull << s0)) cap = 1ull << s0;
+    cap &= ~((1ull << s0) - 1);
+  }
+  return wgs < cap ? wgs : cap;
+}
+
 /* the launch's Params for this workgroup's limb; bid = its block id inside the limb's share of the grid */
 /* MULTI is a compile-time property of the kernel: with it off the limb is 0, every record field sits at a fixed offset of
  * the kernel-argument segment (the compiler re-loads such values at will instead of keeping them in registers) and the
@@ -365,7 +419,7 @@ __device__ __forceinline__ void pin_preloaded(const typename A::ctw (&pre)[4][kE
 /* Fills the LDS twiddle tables of a workgroup (Geom::TBL).  A table depends on the block's
  * position inside its polynomial; a persistent workgroup keeps it for the whole launch, which
  * is valid because its stride over the blocks is a multiple of the blocks per polynomial
- * (launch_fused enforces it).  Stage J of group g is stored TRANSPOSED: slot
+ * (block_grid enforces it).  Stage J of group g is stored TRANSPOSED: slot
  * l = prefix * 2^J + u goes to (2^J - 1) * 2^S + u * 2^S + prefix (see load_stage_tw). */
 template <class A, int LOGN, bool INV, class G = Geom<LOGN, INV, flavor_of<A>()>>
 __device__ __forceinline__ void fill_lds_tables(typename A::ctw *tabl, const Params<A> &p, uint32_t blk0, uint32_t tid)

@@ -144,38 +144,16 @@ template <class A, int LOGN, int KSH> hipError_t launch_moddown_fwd_n(const ModD
 {
   using G = Geom<LOGN, false, flavor_of<A>()>;
   if(ma.nlimbs < 1 || ma.nlimbs > kBconvLimbs || ma.nlimbs > kMaxLimbs || ma.np < 1 || ma.np > kBconvLimbs) return hipErrorInvalidValue;
-  KModDown<A>       kr{};
-  const LimbRec<A> *recs = static_cast<const LimbRec<A> *>(ma.limbs);
-  for(int l = 0; l < ma.nlimbs; l++) {
-    kr.k.limbs[l] = recs[l];
-    kr.ql[l]      = ma.ql[l];
-  }
+  KModDown<A>    kr{};
+  const uint64_t nl = (uint64_t)ma.nlimbs;
+  fill_kargs(kr.k, ma.c, ma.limbs, nl, ma.limb_stride, ma.poly_stride, ma.logn, 0, ma.batch);
+  for(int l = 0; l < ma.nlimbs; l++) kr.ql[l] = ma.ql[l];
   for(int j = 0; j < ma.np; j++) kr.pl[j] = ma.pl[j];
-  kr.k.a           = ma.c;
-  kr.k.limb_stride = ma.limb_stride;
-  kr.k.poly_stride = ma.poly_stride ? ma.poly_stride : (1ull << ma.logn);
-  kr.k.logn        = ma.logn;
-  kr.k.s0          = 0;
-  kr.k.nblocks     = ma.batch;
-  kr.t             = ma.t;
-  kr.np            = ma.np;
-  /* the grid of launch_rescale_fwd_n: the forward block kernel's plain loop, the x extent a multiple of 8 */
-  const uint64_t nl  = (uint64_t)ma.nlimbs;
-  uint64_t       wgs = (ma.batch + G::BPW - 1) / G::BPW;
-  uint64_t       cap = 1ull << 20;
-  if(G::PERSISTENT) {
-    constexpr int by_lds   = G::WG_PER_CU0;
-    constexpr int by_waves = (G::WPS * 4 * 64) / G::WG;
-    constexpr int per_cu   = by_lds < by_waves ? by_lds : by_waves;
-    cap                    = (uint64_t)(ma.num_cus > 0 ? ma.num_cus : 256) * (per_cu > 0 ? per_cu : 1);
-  } else if(G::LDS_TW > 0) {
-    constexpr int per_cu = G::WG_PER_CU0 < 8 ? G::WG_PER_CU0 : 8;
-    cap                  = (uint64_t)(ma.num_cus > 0 ? ma.num_cus : 256) * (per_cu > 0 ? per_cu : 1) * 4;
-  }
-  if(ma.max_grid > 0) cap = (uint64_t)ma.max_grid;
-  cap = cap / nl > 8 ? (cap / nl) & ~7ull : 8;
-  if(wgs > cap) wgs = cap;
-  wgs = (wgs + 7) & ~7ull; /* (workgroups past the last block exit at once) */
+  kr.t  = ma.t;
+  kr.np = ma.np;
+  /* the plain loop of the forward block kernel: no oversubscription of the persistent sizes, four table-filling workgroups per
+   * slot below them; the x extent a multiple of 8 (the header's note on the XCDs) */
+  const uint64_t wgs = block_grid<G>(ma.batch, 0, nl, ma.num_cus, ma.max_grid, G::PERSISTENT ? 1 : 4, true);
   if(ma.batch == 0) return hipSuccess;
   kr.k.wgs_per_limb = (uint32_t)wgs;
   hipLaunchKernelGGL((moddown_fwd_kernel<A, LOGN, KSH>), dim3((unsigned)wgs, (unsigned)nl), dim3(G::WG), 0, ma.stream, kr);

@@ -148,6 +148,33 @@ inline int pass_lazy(const PassArgs &pa) { return pa.ends ? pa.lazy : 1; }
  * 54..60-bit primes: a ciphertext is a few polynomials x tens of such limbs -- one launch instead of one chain per prime) */
 template <class A> constexpr bool multi_limb_built() { return A::kCompact || A::kIntWide; }
 
+inline uint64_t limb_count(int nlimbs) { return (uint64_t)(nlimbs > 0 ? nlimbs : 1); }
+
+/* Run-time flags as template arguments: with_bools(f, b0, b1, ..) calls f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ..).
+ * f is instantiated for EVERY combination: it guards the kernel variants that are not built with `if constexpr`. */
+template <class F> inline hipError_t with_bools(F &&f) { return f(); }
+template <class F, class... B> inline hipError_t with_bools(F &&f, bool b, B... rest)
+{
+  return b ? with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
+           : with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+/* a run-time value as a template argument: f(std::integral_constant<int, v>{}) for v in LO..HI, `otherwise` outside */
+template <int LO, int HI, class F> inline hipError_t with_int(int v, hipError_t otherwise, F &&f)
+{
+  if(v == LO) return f(std::integral_constant<int, LO>{});
+  if constexpr(LO < HI) return with_int<LO + 1, HI>(v, otherwise, f);
+  else return otherwise;
+}
+
+/* The pointer-table form of a launch (separately held polynomials): the kernel's PTRS variant reads every operand pointer as a
+ * DEVICE table of polynomial addresses; k.ptab is the table behind k.a's operand and k.a what is left of the address -- the words
+ * from every entry to the (first) limb of the launch, as a byte offset. */
+template <class A> inline void use_ptr_table(KArgs<A> &k, const uint64_t *table, uint64_t limb_off)
+{
+  k.ptab = table;
+  k.a    = reinterpret_cast<uint64_t *>((uintptr_t)limb_off * 8u);
+}
+
 /* Workgroups launched per resident slot of a persistent block kernel.  One workgroup per slot (the r01..r04 grids) lets the four
  * 256-thread workgroups that share a CU at 2^12 run IN PHASE for the whole launch: they start together, do identical work and
  * meet at the memory system, the LDS pipe and their barriers at the same time.  With several times as many workgroups as
@@ -164,127 +191,86 @@ template <int LOGN, int WG> inline uint64_t block_oversub(int requested, bool wh
 {
   return (uint64_t)(requested > 0 ? requested : block_oversub_default<LOGN, WG>(whole_polynomials));
 }
+/* block_grid's per_slot for the product launchers around a block kernel (dot, forward-multiply): the transforms' oversubscription
+ * of the persistent sizes, four looping workgroups per slot where the tables are filled once per workgroup */
+template <class G, int LOGN> inline uint64_t product_per_slot(int requested, bool whole_polynomials)
+{
+  return G::PERSISTENT ? block_oversub<LOGN, G::WG>(requested, whole_polynomials) : 4;
+}
+/* kernels that fill LDS tables once per workgroup and loop: whole polynomials only (the table depends on the block position) */
+template <class G> constexpr bool fills_tables() { return !G::PERSISTENT && G::LDS_TW > 0; }
 
 template <class A> KArgs<A> make_kargs(const PassArgs &pa)
 {
   KArgs<A> k{};
-  k.a            = pa.a;
-  const LimbRec<A> *recs = static_cast<const LimbRec<A> *>(pa.limbs);
-  for(int l = 0; l < (pa.nlimbs > 0 ? pa.nlimbs : 1) && l < kMaxLimbs; l++) k.limbs[l] = recs[l];
-  k.limb_stride  = pa.limb_stride;
-  k.poly_stride  = pa.poly_stride ? pa.poly_stride : (1ull << pa.logn);
-  k.wgs_per_limb = 1;
-  k.logn         = pa.logn;
-  k.s0           = 0;
-  k.wide         = (uint32_t)pa.wide;
-  k.lastinv      = (uint32_t)pa.lastinv;
-  k.lazy         = (uint32_t)pa.lazy;
-  k.nblocks      = pa.batch;
-  k.ptab         = pa.ptab;
+  fill_kargs(k, pa.a, pa.limbs, limb_count(pa.nlimbs), pa.limb_stride, pa.poly_stride, pa.logn, 0, pa.batch);
+  k.wide    = (uint32_t)pa.wide;
+  k.lastinv = (uint32_t)pa.lastinv;
+  k.lazy    = (uint32_t)pa.lazy;
+  k.ptab    = pa.ptab;
   return k;
 }
 
 template <class A, int LOGN, bool INV, int KSH> hipError_t launch_fused(const PassArgs &pa)
 {
   using G = Geom<LOGN, INV, flavor_of<A>()>;
+  if(fills_tables<G>() && pa.s != 0) return hipErrorInvalidValue;
   KArgs<A> p  = make_kargs<A>(pa);
   p.s0        = (uint32_t)pa.s;
   p.lazy      = (uint32_t)pass_lazy(pa);
   p.nblocks   = pa.batch << pa.s;
-  const uint64_t nl = (uint64_t)(pa.nlimbs > 0 ? pa.nlimbs : 1);
-  uint64_t wgs = (p.nblocks + G::BPW - 1) / G::BPW;
-  uint64_t cap = 1ull << 20;
-  if(G::PERSISTENT) {
-    /* persistent prefetching loop: exactly the resident workgroups (LDS- and
-     * wave-limited), each striding over the blocks */
-    constexpr int by_lds    = G::WG_PER_CU0;
-    constexpr int by_waves  = (G::WPS * 4 * 64) / G::WG;
-    constexpr int per_cu    = by_lds < by_waves ? by_lds : by_waves;
-    cap                     = (uint64_t)(pa.num_cus > 0 ? pa.num_cus : 256) * (per_cu > 0 ? per_cu : 1) * block_oversub<LOGN, G::WG>(pa.oversub, pa.s == 0);
-  }
-  if(!G::PERSISTENT && G::LDS_TW > 0) {
-    /* tables are filled once per workgroup: a few workgroups per resident slot, each looping */
-    if(pa.s != 0) return hipErrorInvalidValue;
-    constexpr int per_cu = G::WG_PER_CU0 < 8 ? G::WG_PER_CU0 : 8;
-    /* Workgroups that loop over the slab in step produce their loads and stores in bursts; how well the memory system takes
-     * them depends on the allocation (the "two modes" of 2^8..2^10: 0.63 or 0.72 of the roofline from one hipMalloc block to
-     * the next, profiles/r05/small_size_modes.txt).  At 2^8 and 2^9, where a table fill is cheap, sixteen times as many
-     * workgroups (one or two iterations each on a 6 GiB slab) lift the slow mode by 5-7 % (0.633 -> 0.678, 0.636 -> 0.667;
-     * inverse +4.5 %) and leave the fast one where it was; 2^10 and 2^11 lose what the larger tables cost, 2^6 and 2^7 are mixed:
-     * unchanged (profiles/r05/small_size_grid.txt). */
-    const int per_slot = pa.oversub > 0 ? pa.oversub : ((LOGN == 8 || LOGN == 9) ? 64 : 4); /* (NTT_OPT_BLOCK_OVERSUB: sweeps) */
-    cap                  = (uint64_t)(pa.num_cus > 0 ? pa.num_cus : 256) * (per_cu > 0 ? per_cu : 1) * (uint64_t)per_slot;
-    /* 2^10: about six iterations per workgroup on large batches (32768 workgroups on a 6 GiB slab: slow mode 0.633 -> 0.653; the
-     * 8192 of smaller batches stay, where more workgroups lost 2 %) */
-    if(LOGN == 10 && pa.oversub <= 0 && wgs / 6 > cap) cap = wgs / 6;
-  }
-  if(pa.max_grid > 0) cap = (uint64_t)pa.max_grid;
-  cap = cap / nl > 0 ? cap / nl : 1; /* the limbs of one launch share the resident workgroups */
-  /* a persistent workgroup must always see the same block position inside the
-   * polynomial (its LDS twiddle table depends on it): the grid, which is its
-   * stride, is a multiple of the 2^s blocks per polynomial (nblocks always is) */
-  if(G::BPW == 1 && pa.s > 0) {
-    if(cap < (1ull << pa.s)) cap = 1ull << pa.s;
-    cap &= ~((1ull << pa.s) - 1);
-  }
-  if(wgs > cap) wgs = cap;
+  const uint64_t nl = limb_count(pa.nlimbs);
+  /* Workgroups that loop over the slab in step produce their loads and stores in bursts; how well the memory system takes
+   * them depends on the allocation (the "two modes" of 2^8..2^10: 0.63 or 0.72 of the roofline from one hipMalloc block to
+   * the next, profiles/r05/small_size_modes.txt).  At 2^8 and 2^9, where a table fill is cheap, sixteen times as many
+   * workgroups (one or two iterations each on a 6 GiB slab) lift the slow mode by 5-7 % (0.633 -> 0.678, 0.636 -> 0.667;
+   * inverse +4.5 %) and leave the fast one where it was; 2^10 and 2^11 lose what the larger tables cost, 2^6 and 2^7 are mixed:
+   * unchanged (profiles/r05/small_size_grid.txt). */
+  const uint64_t per_slot = G::PERSISTENT ? block_oversub<LOGN, G::WG>(pa.oversub, pa.s == 0)
+                                          : (uint64_t)(pa.oversub > 0 ? pa.oversub : ((LOGN == 8 || LOGN == 9) ? 64 : 4)); /* (NTT_OPT_BLOCK_OVERSUB: sweeps) */
+  /* 2^10: about six iterations per workgroup on large batches (32768 workgroups on a 6 GiB slab: slow mode 0.633 -> 0.653; the
+   * 8192 of smaller batches stay, where more workgroups lost 2 %) */
+  const uint64_t min_cap = (fills_tables<G>() && LOGN == 10 && pa.oversub <= 0) ? ((p.nblocks + G::BPW - 1) / G::BPW) / 6 : 0;
+  const uint64_t wgs     = block_grid<G>(p.nblocks, p.s0, nl, pa.num_cus, pa.max_grid, per_slot, false, min_cap);
   if(wgs == 0) return hipSuccess;
   p.wgs_per_limb = (uint32_t)wgs;
   const dim3 grid((unsigned)wgs, (unsigned)nl), wg(G::WG); /* (MULTI variants: blockIdx.y is the limb) */
-  if(nl > 1) {
-    /* several limbs in one launch: the MULTI variants, built for the FP64 policies (the ones RNS bases use) */
-    if constexpr(multi_limb_built<A>()) {
-      if constexpr(INV) {
-        if(pa.lastinv) {
-          hipLaunchKernelGGL((fused_kernel<A, LOGN, true, KSH, true, false, true>), grid, wg, 0, pa.stream, p);
-        } else if constexpr(LOGN == kFusedLarge || LOGN == kFusedSmallBlock) {
-          hipLaunchKernelGGL((fused_kernel<A, LOGN, true, KSH, false, false, true>), grid, wg, 0, pa.stream, p);
-        } else {
-          return hipErrorInvalidValue;
-        }
-      } else {
-        if constexpr(A::kTracksBounds) { /* (lazy outputs: a kernel variant for the FP64 policies, a run-time flag for the integer ones) */
-          if(pa.ends && pa.lazy) {
-            hipLaunchKernelGGL((fused_kernel<A, LOGN, false, KSH, false, true, true>), grid, wg, 0, pa.stream, p);
-            return hipGetLastError();
-          }
-        }
-        hipLaunchKernelGGL((fused_kernel<A, LOGN, false, KSH, false, false, true>), grid, wg, 0, pa.stream, p);
-      }
-      return hipGetLastError();
-    } else {
+  /* several limbs in one launch: the MULTI variants, built for the policies RNS bases use */
+  return with_bools([&](auto multi) -> hipError_t {
+    constexpr bool MULTI = decltype(multi)::value;
+    if constexpr(MULTI && !multi_limb_built<A>()) {
       return hipErrorNotSupported;
-    }
-  }
-  if constexpr(INV) {
-    /* the inverse kernel exists in two variants: ending a whole transform (N^-1 folded into
-     * its last group) -- every block size -- and, for the block size used below column
-     * passes, not ending it */
-    if(pa.lastinv || A::kRadix4) {
-      /* (radix-4 formulation: N^-1 is a pass of its own, fused into the LAST pass's store -- the blocks of a larger
-       * transform run the same kernel with the multiplier record of 1: ntt_host.hip, limbrec_mid) */
-      hipLaunchKernelGGL((fused_kernel<A, LOGN, true, KSH, true>), grid, wg, 0, pa.stream, p);
-    } else if constexpr(LOGN == kFusedLarge || LOGN == kFusedSmallBlock) {
-      hipLaunchKernelGGL((fused_kernel<A, LOGN, true, KSH, false>), grid, wg, 0, pa.stream, p);
-    } else {
-      return hipErrorInvalidValue;
-    }
-  } else {
-    if constexpr(A::kTracksBounds) {
-      if(pa.ends && pa.lazy) {
-        hipLaunchKernelGGL((fused_kernel<A, LOGN, false, KSH, false, true>), grid, wg, 0, pa.stream, p);
-        return hipGetLastError();
+    } else if constexpr(INV) {
+      /* the inverse kernel exists in two variants: ending a whole transform (N^-1 folded into
+       * its last group) -- every block size -- and, for the block size used below column
+       * passes, not ending it */
+      static_assert(!(A::kRadix4 && multi_limb_built<A>()), "radix-4: single-limb launches only (its blocks always take the LASTINV kernel)");
+      if(pa.lastinv || A::kRadix4) {
+        /* (radix-4 formulation: N^-1 is a pass of its own, fused into the LAST pass's store -- the blocks of a larger
+         * transform run the same kernel with the multiplier record of 1: host/host_plan.inc, limbrec_mid) */
+        hipLaunchKernelGGL((fused_kernel<A, LOGN, true, KSH, true, false, MULTI>), grid, wg, 0, pa.stream, p);
+      } else if constexpr(LOGN == kFusedLarge || LOGN == kFusedSmallBlock) {
+        hipLaunchKernelGGL((fused_kernel<A, LOGN, true, KSH, false, false, MULTI>), grid, wg, 0, pa.stream, p);
+      } else {
+        return hipErrorInvalidValue;
       }
+    } else {
+      if constexpr(A::kTracksBounds) { /* (lazy outputs: a kernel variant for the FP64 policies, a run-time flag for the integer ones) */
+        if(pa.ends && pa.lazy) {
+          hipLaunchKernelGGL((fused_kernel<A, LOGN, false, KSH, false, true, MULTI>), grid, wg, 0, pa.stream, p);
+          return hipGetLastError();
+        }
+      }
+      hipLaunchKernelGGL((fused_kernel<A, LOGN, false, KSH, false, false, MULTI>), grid, wg, 0, pa.stream, p);
     }
-    hipLaunchKernelGGL((fused_kernel<A, LOGN, false, KSH, false, false>), grid, wg, 0, pa.stream, p);
-  }
-  return hipGetLastError();
+    return hipGetLastError();
+  }, nl > 1);
 }
 
 /* pa.r = LEAD (1..3): the whole transform of 2^(14+LEAD) points in one launch; pa.batch polynomials */
 /* Built for the FP64 policy at N = 2^16 and 2^17 (BASELINE configs 3 and 5).  The integer policy's larger
  * temporaries and the N = 2^15 inverse do not fit the 128-register budget of a 1024-thread workgroup without
- * scratch: those cases stay on the one-launch-per-pass path (ntt_host.hip: two_phase_applies). */
+ * scratch: those cases stay on the one-launch-per-pass path (host/host_transforms.inc: the two_phase condition). */
 template <class A, int LEAD> constexpr bool two_phase_built() { return A::kTracksBounds && LEAD >= 2; }
 
 template <class A, int LEAD, bool INV, int KSH> hipError_t launch_twophase(const PassArgs &pa)
@@ -296,7 +282,6 @@ template <class A, int LEAD, bool INV, int KSH> hipError_t launch_twophase(const
   KArgs<A> p = make_kargs<A>(pa);
   p.s0       = (uint32_t)LEAD;
   p.lastinv  = (uint32_t)pa.inverse;
-  p.nblocks  = pa.batch;
   uint64_t wgs = pa.batch;
   uint64_t cap = (uint64_t)(pa.num_cus > 0 ? pa.num_cus : 256);
   if(pa.max_grid > 0) cap = (uint64_t)pa.max_grid;
@@ -308,7 +293,16 @@ template <class A, int LEAD, bool INV, int KSH> hipError_t launch_twophase(const
   }
 }
 
-/* N = 2^15 in one pass (onepass_kernel): one persistent 1024-thread workgroup per CU, pa.batch polynomials per limb */
+/* grid of the one-pass 2^15 kernels: one persistent 1024-thread workgroup per CU, the limbs of a launch sharing them */
+inline uint64_t onepass_grid(uint64_t batch, uint64_t nl, int num_cus, int max_grid)
+{
+  uint64_t cap = (uint64_t)(num_cus > 0 ? num_cus : 256);
+  if(max_grid > 0) cap = (uint64_t)max_grid;
+  cap = cap / nl > 0 ? cap / nl : 1;
+  return batch < cap ? batch : cap;
+}
+
+/* N = 2^15 in one pass (onepass_kernel), pa.batch polynomials per limb */
 template <class A> constexpr bool onepass_built() { return A::kCompact && A::kTracksBounds; }
 template <class A, bool INV, int KSH> hipError_t launch_onepass(const PassArgs &pa)
 {
@@ -316,29 +310,23 @@ template <class A, bool INV, int KSH> hipError_t launch_onepass(const PassArgs &
     return hipErrorNotSupported;
   } else {
     if(pa.logn != (uint32_t)kFusedLarge + 1) return hipErrorNotSupported; /* (a lazy call gets canonical words: inside the lazy ranges) */
-    const uint64_t nl = (uint64_t)(pa.nlimbs > 0 ? pa.nlimbs : 1);
+    const uint64_t nl = limb_count(pa.nlimbs);
     if(nl > (uint64_t)kMaxLimbs) return hipErrorNotSupported;
     KArgs<A> p = make_kargs<A>(pa);
     p.s0       = 1;
     p.lastinv  = (uint32_t)pa.inverse;
     p.lazy     = 0;
-    p.nblocks  = pa.batch;
-    uint64_t wgs = pa.batch;
-    uint64_t cap = (uint64_t)(pa.num_cus > 0 ? pa.num_cus : 256);
-    if(pa.max_grid > 0) cap = (uint64_t)pa.max_grid;
-    cap = cap / nl > 0 ? cap / nl : 1;
-    if(wgs > cap) wgs = cap;
+    const uint64_t wgs = onepass_grid(pa.batch, nl, pa.num_cus, pa.max_grid);
     if(wgs == 0) return hipSuccess;
     p.wgs_per_limb = (uint32_t)wgs;
     const dim3 grid((unsigned)wgs, (unsigned)nl);
-    if(nl > 1) hipLaunchKernelGGL((onepass_kernel<A, INV, KSH, true>), grid, dim3(1024), 0, pa.stream, p);
-    else hipLaunchKernelGGL((onepass_kernel<A, INV, KSH, false>), grid, dim3(1024), 0, pa.stream, p);
-    return hipGetLastError();
+    return with_bools([&](auto multi) {
+      hipLaunchKernelGGL((onepass_kernel<A, INV, KSH, decltype(multi)::value>), grid, dim3(1024), 0, pa.stream, p);
+      return hipGetLastError();
+    }, nl > 1);
   }
 }
 
-/* pa.r = LEAD (3..5), pa.batch polynomials of 2^(12 + LEAD) points per limb; pa.team_ctl: TeamCtl with nlimbs * batch counters,
- * zeroed here.  Several limbs (an RNS set, [limb][batch][N]): the MULTI variant, the queues run over all limbs' polynomials. */
 /* Zeroes a control block (queue heads, owners, per-polynomial counters) in front of an XCD-local launch -- as a KERNEL, not as an
  * asynchronous memset: captured into a HIP graph, a memset node in front of the kernel node did not always take effect before the
  * kernel's first workgroups read the counters (stale counters of the previous replay: second-pass items that do not wait, or
@@ -358,33 +346,46 @@ static inline hipError_t team_ctl_clear(void *ctl, size_t bytes, hipStream_t str
   return hipGetLastError();
 }
 
+/* What the XCD-local ("team") launchers share, in front of their kernel arguments: refuses (before anything is enqueued) more limbs
+ * than records, a missing control block and 2^limit_log or more polynomials; fills kt's queue fields (ar.team_lag, else
+ * default_lag; the numbering of the queues' polynomials); zeroes the control block -- Ctl and `counters` counters per polynomial;
+ * and sets the grid: ar.team_wpc (default four: 40.6 KB of LDS each, at most 128 VGPRs) 256-thread workgroups per CU, or ar.max_grid. */
+template <class Ctl, class KT, class Args>
+inline hipError_t team_prologue(KT &kt, const Args &ar, int limit_log, int counters, int default_lag, dim3 &grid)
+{
+  const uint64_t nl = limb_count(ar.nlimbs);
+  if(nl > (uint64_t)kMaxLimbs || !ar.team_ctl || nl * ar.batch >= (1ull << limit_log)) return hipErrorNotSupported;
+  kt.ctl        = static_cast<Ctl *>(ar.team_ctl);
+  kt.lag        = (uint32_t)(ar.team_lag > 0 ? ar.team_lag : default_lag);
+  kt.nlimbs     = (uint32_t)nl;
+  kt.poly_major = nl > 1 && (ar.poly_stride ? ar.poly_stride : (1ull << ar.logn)) > ar.limb_stride;
+  kt.split_rcp  = team_split_rcp(kt.poly_major ? nl : ar.batch);
+  uint64_t wgs  = (uint64_t)(ar.num_cus > 0 ? ar.num_cus : 256) * (ar.team_wpc > 0 ? ar.team_wpc : 4);
+  if(ar.max_grid > 0) wgs = (uint64_t)ar.max_grid;
+  grid = dim3((unsigned)wgs);
+  return team_ctl_clear(ar.team_ctl, sizeof(Ctl) + (size_t)counters * (size_t)(nl * ar.batch) * sizeof(unsigned), ar.stream);
+}
+
+/* pa.r = LEAD (3..5), pa.batch polynomials of 2^(12 + LEAD) points per limb; pa.team_ctl: TeamCtl with nlimbs * batch counters,
+ * zeroed here.  Several limbs (an RNS set, [limb][batch][N]): the MULTI variant, the queues run over all limbs' polynomials. */
 template <class A, int LEAD, bool INV, int KSH> hipError_t launch_team(const PassArgs &pa)
 {
   if constexpr(!(A::kCompact || A::kIntWide)) {
     return hipErrorNotSupported;
   } else {
-    const uint64_t nl = (uint64_t)(pa.nlimbs > 0 ? pa.nlimbs : 1);
-    if(nl > (uint64_t)kMaxLimbs || !pa.team_ctl || pa.wide || pa.lazy || nl * pa.batch >= (1ull << 31)) return hipErrorNotSupported;
-    KTeam<A> kt{};
-    kt.k         = make_kargs<A>(pa);
-    kt.k.lazy    = 0; /* canonical out (the integer policies read this flag at run time) */
-    kt.k.lastinv = (uint32_t)pa.inverse;
-    kt.k.nblocks = pa.batch;
-    kt.ctl       = static_cast<TeamCtl *>(pa.team_ctl);
-    kt.lag       = (uint32_t)(pa.team_lag > 0 ? pa.team_lag : 6);
-    kt.nlimbs    = (uint32_t)nl;
-    kt.poly_major = nl > 1 && kt.k.poly_stride > kt.k.limb_stride;
-    kt.split_rcp  = team_split_rcp(kt.poly_major ? nl : pa.batch);
-    const size_t bytes = sizeof(TeamCtl) + (size_t)(nl * pa.batch) * sizeof(unsigned);
-    hipError_t   e     = team_ctl_clear(pa.team_ctl, bytes, pa.stream);
+    if(pa.wide || pa.lazy) return hipErrorNotSupported;
+    KTeam<A>         kt{};
+    dim3             grid;
+    const hipError_t e = team_prologue<TeamCtl>(kt, pa, 31, 1, 6, grid);
     if(e != hipSuccess) return e;
-    /* four workgroups per CU: 40,580 bytes of LDS each (32.9 KB exchange buffer + 7.5 KB table), at most 128 VGPRs */
-    uint64_t wgs = (uint64_t)(pa.num_cus > 0 ? pa.num_cus : 256) * (pa.team_wpc > 0 ? pa.team_wpc : 4);
-    if(pa.max_grid > 0) wgs = (uint64_t)pa.max_grid;
-    kt.k.wgs_per_limb = (uint32_t)wgs;
-    if(nl > 1) hipLaunchKernelGGL((team_kernel<A, LEAD, INV, KSH, true>), dim3((unsigned)wgs), dim3(256), 0, pa.stream, kt);
-    else hipLaunchKernelGGL((team_kernel<A, LEAD, INV, KSH, false>), dim3((unsigned)wgs), dim3(256), 0, pa.stream, kt);
-    return hipGetLastError();
+    kt.k              = make_kargs<A>(pa);
+    kt.k.lazy         = 0; /* canonical out (the integer policies read this flag at run time) */
+    kt.k.lastinv      = (uint32_t)pa.inverse;
+    kt.k.wgs_per_limb = grid.x;
+    return with_bools([&](auto multi) {
+      hipLaunchKernelGGL((team_kernel<A, LEAD, INV, KSH, decltype(multi)::value>), grid, dim3(256), 0, pa.stream, kt);
+      return hipGetLastError();
+    }, kt.nlimbs > 1);
   }
 }
 
@@ -393,8 +394,7 @@ template <class A, int R, bool INV, int KSH> hipError_t launch_column(const Pass
   KArgs<A> p = make_kargs<A>(pa);
   p.s0       = (uint32_t)pa.s;
   p.lazy     = (uint32_t)pass_lazy(pa);
-  p.nblocks  = pa.batch;
-  const uint64_t nl    = (uint64_t)(pa.nlimbs > 0 ? pa.nlimbs : 1);
+  const uint64_t nl    = limb_count(pa.nlimbs);
   const uint64_t total = pa.batch << (pa.logn - R);
   uint64_t       wgs   = (total + 255) / 256;
   uint64_t       cap   = pa.max_grid > 0 ? (uint64_t)pa.max_grid : (1ull << 22);
@@ -402,16 +402,49 @@ template <class A, int R, bool INV, int KSH> hipError_t launch_column(const Pass
   if(wgs > cap) wgs = cap;
   if(wgs == 0) return hipSuccess;
   p.wgs_per_limb = (uint32_t)wgs;
-  if(nl > 1) {
-    if constexpr(multi_limb_built<A>()) {
-      hipLaunchKernelGGL((column_kernel<A, R, INV, KSH, true>), dim3((unsigned)wgs, (unsigned)nl), dim3(256), 0, pa.stream, p);
+  return with_bools([&](auto multi) -> hipError_t {
+    constexpr bool MULTI = decltype(multi)::value;
+    if constexpr(MULTI && !multi_limb_built<A>()) {
+      return hipErrorNotSupported;
+    } else {
+      hipLaunchKernelGGL((column_kernel<A, R, INV, KSH, MULTI>), dim3((unsigned)wgs, (unsigned)nl), dim3(256), 0, pa.stream, p);
+      return hipGetLastError();
+    }
+  }, nl > 1);
+}
+
+/* fused product on blocks of 2^BL points: whole polynomials (BL = logn; 8..11: fused_product_small_kernel) or the blocks of a
+ * larger one between column passes (BL = 12 or 14); pp is filled but for the grid */
+template <class A, int KSH, int BL> hipError_t launch_product_blocks(const ProdArgs &pa, KProd<A> &pp)
+{
+  using G = Geom<BL, false, 3>;
+  const uint32_t s0 = pp.f.s0;
+  const uint64_t nl = limb_count(pa.nlimbs);
+  /* 2^8..2^11: tables filled once per workgroup, four looping workgroups per slot.  2^12: 256-thread workgroups, one wave per SIMD
+   * each; whole polynomials: several workgroups per resident slot, as for the transforms -- block_oversub; measured 0.369 -> 0.401
+   * of the 24N roofline at 8 per slot, profiles/r05/oversub_sweep.txt.  2^13: one 512-thread workgroup per CU by LDS (64 KB exchange
+   * buffer + 30 KB table; a second one does not fit); 2^14: one of 1024 threads.
+   * From 2^12 up a workgroup keeps the tables of ONE block position: its stride is a multiple of the blocks per polynomial. */
+  static_assert(BL < 12 ? fills_tables<G>() : (G::PERSISTENT && G::BPW == 1), "the grid rule block_grid applies to this geometry");
+  static_assert(BL != 12 || (G::WG == 256 && G::WG_PER_CU0 >= 1), "2^12: one wave per SIMD each, min(WG_PER_CU0, WPS) resident");
+  static_assert(BL < 13 || (G::WG_PER_CU0 == 1 && G::WPS * 256 >= G::WG), "2^13, 2^14: one workgroup per CU");
+  const uint64_t per_slot = BL < 12 ? 4 : (BL == 12 ? block_oversub<12, G::WG>(pa.oversub, s0 == 0) : 1);
+  pp.f.wgs_per_limb = (uint32_t)block_grid<G>(pp.f.nblocks, s0, nl, pa.num_cus, pa.max_grid, per_slot);
+  const dim3 grid(pp.f.wgs_per_limb, (unsigned)nl), wg(G::WG);
+  return with_bools([&](auto multi, auto both, auto whole, auto ptrs) -> hipError_t {
+    constexpr bool MULTI = decltype(multi)::value, BOTH = decltype(both)::value, WHOLE = decltype(whole)::value, PTRS = decltype(ptrs)::value;
+    /* (the PTRS kernels: both operands' coefficients, whole polynomials -- refused by the caller otherwise) */
+    /* (2^13-point blocks of a larger product: measured no faster than 2^14, not built) */
+    if constexpr((PTRS && !(BOTH && WHOLE)) || (BL == 13 && !WHOLE)) {
+      return hipErrorNotSupported;
+    } else if constexpr(BL < 12) {
+      hipLaunchKernelGGL((fused_product_small_kernel<A, BL, KSH, MULTI, BOTH, PTRS>), grid, wg, 0, pa.stream, pp);
       return hipGetLastError();
     } else {
-      return hipErrorNotSupported;
+      hipLaunchKernelGGL((fused_product_kernel<A, BL, KSH, true, WHOLE, MULTI, BOTH, PTRS>), grid, wg, 0, pa.stream, pp);
+      return hipGetLastError();
     }
-  }
-  hipLaunchKernelGGL((column_kernel<A, R, INV, KSH>), dim3((unsigned)wgs), dim3(256), 0, pa.stream, p);
-  return hipGetLastError();
+  }, nl > 1, pa.both, s0 == 0, pa.ptrs);
 }
 
 template <class A, int KSH> hipError_t launch_product_impl(const ProdArgs &pa)
@@ -424,153 +457,23 @@ template <class A, int KSH> hipError_t launch_product_impl(const ProdArgs &pa)
     if(blog < 12 && pa.logn > 14) return hipErrorInvalidValue;
     const uint32_t s0 = pa.logn - blog; /* leading stages done by column passes around this launch */
     KProd<A> pp{};
-    pp.f.a            = pa.b;
-    const LimbRec<A> *recs = static_cast<const LimbRec<A> *>(pa.limbs);
-    for(int l = 0; l < (pa.nlimbs > 0 ? pa.nlimbs : 1) && l < kMaxLimbs; l++) pp.f.limbs[l] = recs[l];
-    pp.f.limb_stride  = pa.limb_stride;
-    pp.f.poly_stride  = pa.poly_stride ? pa.poly_stride : (1ull << pa.logn);
-    pp.f.wgs_per_limb = 1;
-    pp.f.logn         = pa.logn;
-    pp.f.s0           = s0;
-    pp.f.nblocks      = pa.batch << s0;
-    pp.ahat           = pa.ahat;
-    pp.out            = pa.out;
-    pp.a_lazy         = (uint32_t)pa.a_lazy;
-    const uint64_t nl = (uint64_t)(pa.nlimbs > 0 ? pa.nlimbs : 1);
-    uint64_t wgs = pp.f.nblocks;
-    uint64_t cap = (uint64_t)(pa.num_cus > 0 ? pa.num_cus : 256);
-    if(pa.max_grid > 0) cap = (uint64_t)pa.max_grid;
-    cap = cap / nl > 0 ? cap / nl : 1;
-    /* a workgroup keeps the tables of ONE block position: its stride is a multiple of the blocks per polynomial */
-    if(cap < (1ull << s0)) cap = 1ull << s0;
-    cap &= ~((1ull << s0) - 1);
-    if(wgs > cap) wgs = cap;
-    if(wgs == 0) return hipSuccess;
+    fill_kargs(pp.f, pa.b, pa.limbs, limb_count(pa.nlimbs), pa.limb_stride, pa.poly_stride, pa.logn, s0, pa.batch << s0);
+    pp.ahat   = pa.ahat;
+    pp.out    = pa.out;
+    pp.a_lazy = (uint32_t)pa.a_lazy;
+    if(pp.f.nblocks == 0) return hipSuccess;
     /* a^ always arrives as the lazy words ntt_fwd_batch_lazy leaves (the canonical-operand variant is not built) -- or not
      * at all: pa.both, whole polynomials, a's coefficients in pa.ahat */
     if(!pa.a_lazy && !pa.both) return hipErrorNotSupported;
     if(pa.both && s0 != 0 && blog != 12 && blog != 14) return hipErrorInvalidValue;
     if(pa.ptrs) {
-      /* separately held polynomials: the three operand pointers are tables (fused_product_kernel's PTRS form) */
-      /* (several limbs: the limbs of every polynomial pa.limb_stride words apart behind its table entry -- the MULTI instances,
-       * whose limb_params add limb * limb_stride to the offset in pp.f.a) */
+      /* separately held polynomials: the three operand pointers are tables (several limbs: the limbs of every polynomial
+       * pa.limb_stride words apart behind its table entry -- the MULTI instances, whose limb_params add limb * limb_stride) */
       if(!pa.both || s0 != 0) return hipErrorNotSupported;
-      pp.f.ptab = reinterpret_cast<const uint64_t *>(pa.b);
-      pp.f.a    = reinterpret_cast<uint64_t *>((uintptr_t)pa.ptr_limb_off * 8u);
+      use_ptr_table(pp.f, pa.b, pa.ptr_limb_off);
     }
-    if(blog < 12) {
-      switch(pa.logn) {
-#define NTT_SMALL_PRODUCT(LN)                                                                                       \
-  case LN: {                                                                                                        \
-    using GS = Geom<LN, false, 3>;                                                                                  \
-    constexpr int per_cu = GS::WG_PER_CU0 < 8 ? GS::WG_PER_CU0 : 8;                                                 \
-    uint64_t      g      = (pp.f.nblocks + GS::BPW - 1) / GS::BPW;                                                  \
-    uint64_t      gcap   = (uint64_t)(pa.num_cus > 0 ? pa.num_cus : 256) * (per_cu > 0 ? per_cu : 1) * 4;           \
-    if(pa.max_grid > 0) gcap = (uint64_t)pa.max_grid;                                                               \
-    gcap = gcap / nl > 0 ? gcap / nl : 1;                                                                           \
-    if(g > gcap) g = gcap;                                                                                          \
-    pp.f.wgs_per_limb = (unsigned)g;                                                                                \
-    if(pa.ptrs) {                                                                                                   \
-      if(nl > 1) hipLaunchKernelGGL((fused_product_small_kernel<A, LN, KSH, true, true, true>), dim3((unsigned)g, (unsigned)nl), dim3(GS::WG), 0, pa.stream, pp); \
-      else hipLaunchKernelGGL((fused_product_small_kernel<A, LN, KSH, false, true, true>), dim3((unsigned)g), dim3(GS::WG), 0, pa.stream, pp); \
-      return hipGetLastError();                                                                                     \
-    }                                                                                                               \
-    if(pa.both) {                                                                                                   \
-      if(nl > 1) hipLaunchKernelGGL((fused_product_small_kernel<A, LN, KSH, true, true>), dim3((unsigned)g, (unsigned)nl), dim3(GS::WG), 0, pa.stream, pp); \
-      else hipLaunchKernelGGL((fused_product_small_kernel<A, LN, KSH, false, true>), dim3((unsigned)g), dim3(GS::WG), 0, pa.stream, pp); \
-      return hipGetLastError();                                                                                     \
-    }                                                                                                               \
-    if(nl > 1) hipLaunchKernelGGL((fused_product_small_kernel<A, LN, KSH, true>), dim3((unsigned)g, (unsigned)nl), dim3(GS::WG), 0, pa.stream, pp); \
-    else hipLaunchKernelGGL((fused_product_small_kernel<A, LN, KSH>), dim3((unsigned)g), dim3(GS::WG), 0, pa.stream, pp); \
-    return hipGetLastError();                                                                                       \
-  }
-        NTT_SMALL_PRODUCT(8)
-        NTT_SMALL_PRODUCT(9)
-        NTT_SMALL_PRODUCT(10)
-        NTT_SMALL_PRODUCT(11)
-#undef NTT_SMALL_PRODUCT
-        default: return hipErrorNotSupported;
-      }
-    }
-    if(blog == 12) {
-      using G12 = Geom<12, false, 3>;
-      constexpr int per_cu = G12::WG_PER_CU0 < G12::WPS ? G12::WG_PER_CU0 : G12::WPS; /* 256-thread workgroups: one wave per SIMD each */
-      /* (whole polynomials: several workgroups per resident slot, as for the transforms -- block_oversub; measured 0.369 -> 0.401 of
-       * the 24N roofline at 8 per slot, profiles/r05/oversub_sweep.txt) */
-      uint64_t      cap12  = (uint64_t)(pa.num_cus > 0 ? pa.num_cus : 256) * per_cu * block_oversub<12, G12::WG>(pa.oversub, s0 == 0);
-      if(pa.max_grid > 0) cap12 = (uint64_t)pa.max_grid;
-      cap12 = cap12 / nl > 0 ? cap12 / nl : 1;
-      if(cap12 < (1ull << s0)) cap12 = 1ull << s0;
-      cap12 &= ~((1ull << s0) - 1);
-      wgs = pp.f.nblocks < cap12 ? pp.f.nblocks : cap12;
-      pp.f.wgs_per_limb = (uint32_t)wgs;
-      if(pa.ptrs) {
-        if(nl > 1) hipLaunchKernelGGL((fused_product_kernel<A, 12, KSH, true, true, true, true, true>), dim3((unsigned)wgs, (unsigned)nl), dim3(G12::WG), 0, pa.stream, pp);
-        else hipLaunchKernelGGL((fused_product_kernel<A, 12, KSH, true, true, false, true, true>), dim3((unsigned)wgs), dim3(G12::WG), 0, pa.stream, pp);
-        return hipGetLastError();
-      }
-      if(pa.both) {
-        if(s0 == 0) {
-          if(nl > 1) hipLaunchKernelGGL((fused_product_kernel<A, 12, KSH, true, true, true, true>), dim3((unsigned)wgs, (unsigned)nl), dim3(G12::WG), 0, pa.stream, pp);
-          else hipLaunchKernelGGL((fused_product_kernel<A, 12, KSH, true, true, false, true>), dim3((unsigned)wgs), dim3(G12::WG), 0, pa.stream, pp);
-        } else {
-          if(nl > 1) hipLaunchKernelGGL((fused_product_kernel<A, 12, KSH, true, false, true, true>), dim3((unsigned)wgs, (unsigned)nl), dim3(G12::WG), 0, pa.stream, pp);
-          else hipLaunchKernelGGL((fused_product_kernel<A, 12, KSH, true, false, false, true>), dim3((unsigned)wgs), dim3(G12::WG), 0, pa.stream, pp);
-        }
-        return hipGetLastError();
-      }
-      if(nl > 1) {
-        if(s0 == 0) hipLaunchKernelGGL((fused_product_kernel<A, 12, KSH, true, true, true>), dim3((unsigned)wgs, (unsigned)nl), dim3(G12::WG), 0, pa.stream, pp);
-        else hipLaunchKernelGGL((fused_product_kernel<A, 12, KSH, true, false, true>), dim3((unsigned)wgs, (unsigned)nl), dim3(G12::WG), 0, pa.stream, pp);
-      } else {
-        if(s0 == 0) hipLaunchKernelGGL((fused_product_kernel<A, 12, KSH, true, true>), dim3((unsigned)wgs), dim3(G12::WG), 0, pa.stream, pp);
-        else hipLaunchKernelGGL((fused_product_kernel<A, 12, KSH, true, false>), dim3((unsigned)wgs), dim3(G12::WG), 0, pa.stream, pp);
-      }
-      return hipGetLastError();
-    }
-    if(blog == 13) {
-      using G13 = Geom<13, false, 3>;
-      /* one 512-thread workgroup per CU by LDS (64 KB exchange buffer + 30 KB table); a second one does not fit */
-      if(s0 != 0) return hipErrorNotSupported; /* (2^13-point blocks of a larger product: measured no faster than 2^14, not built) */
-      pp.f.wgs_per_limb = (uint32_t)wgs;
-      if(pa.ptrs) {
-        if(nl > 1) hipLaunchKernelGGL((fused_product_kernel<A, 13, KSH, true, true, true, true, true>), dim3((unsigned)wgs, (unsigned)nl), dim3(G13::WG), 0, pa.stream, pp);
-        else hipLaunchKernelGGL((fused_product_kernel<A, 13, KSH, true, true, false, true, true>), dim3((unsigned)wgs), dim3(G13::WG), 0, pa.stream, pp);
-        return hipGetLastError();
-      }
-      if(pa.both) {
-        if(nl > 1) hipLaunchKernelGGL((fused_product_kernel<A, 13, KSH, true, true, true, true>), dim3((unsigned)wgs, (unsigned)nl), dim3(G13::WG), 0, pa.stream, pp);
-        else hipLaunchKernelGGL((fused_product_kernel<A, 13, KSH, true, true, false, true>), dim3((unsigned)wgs), dim3(G13::WG), 0, pa.stream, pp);
-        return hipGetLastError();
-      }
-      if(nl > 1) hipLaunchKernelGGL((fused_product_kernel<A, 13, KSH, true, true, true>), dim3((unsigned)wgs, (unsigned)nl), dim3(G13::WG), 0, pa.stream, pp);
-      else hipLaunchKernelGGL((fused_product_kernel<A, 13, KSH, true, true>), dim3((unsigned)wgs), dim3(G13::WG), 0, pa.stream, pp);
-      return hipGetLastError();
-    }
-    pp.f.wgs_per_limb = (uint32_t)wgs;
-    if(pa.ptrs) {
-      if(nl > 1) hipLaunchKernelGGL((fused_product_kernel<A, 14, KSH, true, true, true, true, true>), dim3((unsigned)wgs, (unsigned)nl), dim3(1024), 0, pa.stream, pp);
-      else hipLaunchKernelGGL((fused_product_kernel<A, 14, KSH, true, true, false, true, true>), dim3((unsigned)wgs), dim3(1024), 0, pa.stream, pp);
-      return hipGetLastError();
-    }
-    if(pa.both) {
-      if(s0 == 0) {
-        if(nl > 1) hipLaunchKernelGGL((fused_product_kernel<A, 14, KSH, true, true, true, true>), dim3((unsigned)wgs, (unsigned)nl), dim3(1024), 0, pa.stream, pp);
-        else hipLaunchKernelGGL((fused_product_kernel<A, 14, KSH, true, true, false, true>), dim3((unsigned)wgs), dim3(1024), 0, pa.stream, pp);
-      } else {
-        if(nl > 1) hipLaunchKernelGGL((fused_product_kernel<A, 14, KSH, true, false, true, true>), dim3((unsigned)wgs, (unsigned)nl), dim3(1024), 0, pa.stream, pp);
-        else hipLaunchKernelGGL((fused_product_kernel<A, 14, KSH, true, false, false, true>), dim3((unsigned)wgs), dim3(1024), 0, pa.stream, pp);
-      }
-      return hipGetLastError();
-    }
-    if(nl > 1) {
-      if(s0 == 0) hipLaunchKernelGGL((fused_product_kernel<A, 14, KSH, true, true, true>), dim3((unsigned)wgs, (unsigned)nl), dim3(1024), 0, pa.stream, pp);
-      else hipLaunchKernelGGL((fused_product_kernel<A, 14, KSH, true, false, true>), dim3((unsigned)wgs, (unsigned)nl), dim3(1024), 0, pa.stream, pp);
-    } else {
-      if(s0 == 0) hipLaunchKernelGGL((fused_product_kernel<A, 14, KSH, true, true>), dim3((unsigned)wgs), dim3(1024), 0, pa.stream, pp);
-      else hipLaunchKernelGGL((fused_product_kernel<A, 14, KSH, true, false>), dim3((unsigned)wgs), dim3(1024), 0, pa.stream, pp);
-    }
-    return hipGetLastError();
+    /* (a block_log above 14 runs the 2^14 kernel) */
+    return with_int<8, 14>(blog < 14 ? (int)blog : 14, hipErrorNotSupported, [&](auto bl) { return launch_product_blocks<A, KSH, decltype(bl)::value>(pa, pp); });
   }
 }
 
@@ -581,154 +484,73 @@ template <class A, int KSH> hipError_t launch_team_product_impl(const ProdArgs &
   if constexpr(!A::kCompact) {
     return hipErrorNotSupported;
   } else {
-    const uint64_t nl = (uint64_t)(pa.nlimbs > 0 ? pa.nlimbs : 1);
-    if(nl > (uint64_t)kMaxLimbs || !pa.team_ctl || (!pa.a_lazy && !pa.four) || pa.logn < kTeamBlock + 3 || pa.logn > kTeamBlock + 5 ||
-       nl * pa.batch >= (1ull << 30)) {
-      return hipErrorNotSupported;
-    }
-    KTeamProd<A> kt{};
-    kt.k.f.a            = pa.b;
-    const LimbRec<A> *recs = static_cast<const LimbRec<A> *>(pa.limbs);
-    for(uint64_t l = 0; l < nl; l++) kt.k.f.limbs[l] = recs[l];
-    kt.k.f.limb_stride  = nl > 1 ? pa.limb_stride : 0;
-    kt.k.f.poly_stride  = pa.poly_stride ? pa.poly_stride : (1ull << pa.logn);
-    kt.k.f.logn         = pa.logn;
-    kt.k.f.s0           = pa.logn - kTeamBlock;
-    kt.k.f.nblocks      = pa.batch;
+    if((!pa.a_lazy && !pa.four) || pa.logn < kTeamBlock + 3 || pa.logn > kTeamBlock + 5) return hipErrorNotSupported;
+    KTeamProd<A>     kt{};
+    dim3             grid;
+    const hipError_t e = team_prologue<TeamProdCtl>(kt, pa, 30, 2, 8, grid);
+    if(e != hipSuccess) return e;
+    fill_kargs(kt.k.f, pa.b, pa.limbs, kt.nlimbs, kt.nlimbs > 1 ? pa.limb_stride : 0, pa.poly_stride, pa.logn, pa.logn - kTeamBlock, pa.batch);
+    kt.k.f.wgs_per_limb = grid.x;
     kt.k.ahat           = pa.ahat;
     kt.k.out            = pa.out;
     kt.k.a_lazy         = 1;
-    kt.ctl              = static_cast<TeamProdCtl *>(pa.team_ctl);
-    kt.lag              = (uint32_t)(pa.team_lag > 0 ? pa.team_lag : 8);
-    kt.nlimbs           = (uint32_t)nl;
-    kt.poly_major       = nl > 1 && kt.k.f.poly_stride > kt.k.f.limb_stride;
-    kt.split_rcp        = team_split_rcp(kt.poly_major ? nl : pa.batch);
-    const size_t bytes = sizeof(TeamProdCtl) + 2 * (size_t)(nl * pa.batch) * sizeof(unsigned);
-    hipError_t   e     = team_ctl_clear(pa.team_ctl, bytes, pa.stream);
-    if(e != hipSuccess) return e;
-    /* four workgroups per CU (121 VGPRs, 40.6 KB of LDS each) */
-    uint64_t wgs = (uint64_t)(pa.num_cus > 0 ? pa.num_cus : 256) * (pa.team_wpc > 0 ? pa.team_wpc : 4);
-    if(pa.max_grid > 0) wgs = (uint64_t)pa.max_grid;
-    kt.k.f.wgs_per_limb = (uint32_t)wgs;
-    const dim3 g((unsigned)wgs), t(256);
-#define NTT_TEAM_PROD(LEADV, FOURV)                                                                                \
-  do {                                                                                                             \
-    if(nl > 1) hipLaunchKernelGGL((team_product_kernel<A, LEADV, KSH, FOURV, true>), g, t, 0, pa.stream, kt);      \
-    else hipLaunchKernelGGL((team_product_kernel<A, LEADV, KSH, FOURV, false>), g, t, 0, pa.stream, kt);           \
-  } while(0)
-    if(pa.ptrs) {
-      /* separately held polynomials: b, ahat (a's coefficients) and out are device tables (team_product_kernel's PTRS form) */
-      /* (several limbs: every polynomial's limbs pa.limb_stride words apart behind its table entry -- the MULTI instances) */
-      if(!pa.four) return hipErrorNotSupported;
-      kt.k.f.ptab = reinterpret_cast<const uint64_t *>(pa.b);
-      kt.k.f.a    = reinterpret_cast<uint64_t *>((uintptr_t)pa.ptr_limb_off * 8u);
-#define NTT_TEAM_PROD_PTRS(LEADV)                                                                                  \
-  do {                                                                                                             \
-    if(nl > 1) hipLaunchKernelGGL((team_product_kernel<A, LEADV, KSH, true, true, true>), g, t, 0, pa.stream, kt); \
-    else hipLaunchKernelGGL((team_product_kernel<A, LEADV, KSH, true, false, true>), g, t, 0, pa.stream, kt);      \
-  } while(0)
-      switch(pa.logn - kTeamBlock) {
-        case 3: NTT_TEAM_PROD_PTRS(3); break;
-        case 4: NTT_TEAM_PROD_PTRS(4); break;
-        default: NTT_TEAM_PROD_PTRS(5); break;
-      }
-#undef NTT_TEAM_PROD_PTRS
-      return hipGetLastError();
-    }
-    if(pa.four) {
-      /* ahat = a itself (coefficients): both forward transforms happen inside the launch */
-      switch(pa.logn - kTeamBlock) {
-        case 3: NTT_TEAM_PROD(3, true); break;
-        case 4: NTT_TEAM_PROD(4, true); break;
-        default: NTT_TEAM_PROD(5, true); break;
-      }
-      return hipGetLastError();
-    }
-    switch(pa.logn - kTeamBlock) {
-      case 3: NTT_TEAM_PROD(3, false); break;
-      case 4: NTT_TEAM_PROD(4, false); break;
-      default: NTT_TEAM_PROD(5, false); break;
-    }
-#undef NTT_TEAM_PROD
-    return hipGetLastError();
+    /* pa.ptrs: b, ahat (a's coefficients) and out are device tables (several limbs: every polynomial's limbs pa.limb_stride words
+     * apart behind its table entry -- the MULTI instances) */
+    if(pa.ptrs) use_ptr_table(kt.k.f, pa.b, pa.ptr_limb_off);
+    return with_int<3, 5>((int)(pa.logn - kTeamBlock), hipErrorNotSupported, [&](auto lead) {
+      /* four: ahat = a itself (coefficients), both forward transforms happen inside the launch */
+      return with_bools([&](auto four, auto multi, auto ptrs) -> hipError_t {
+        constexpr bool FOUR = decltype(four)::value, MULTI = decltype(multi)::value, PTRS = decltype(ptrs)::value;
+        if constexpr(PTRS && !FOUR) {
+          return hipErrorNotSupported;
+        } else {
+          hipLaunchKernelGGL((team_product_kernel<A, decltype(lead)::value, KSH, FOUR, MULTI, PTRS>), grid, dim3(256), 0, pa.stream, kt);
+          return hipGetLastError();
+        }
+      }, pa.four, kt.nlimbs > 1, pa.ptrs);
+    });
   }
 }
 
-template <class A, int LOGN, int KSH, bool LASTINV> hipError_t launch_dot_blocks(const DotArgs &da)
+/* the operand fields of dot_inv_kernel and team_dot_kernel */
+template <class A> inline void fill_dot(KDot<A> &kd, const DotArgs &da, uint64_t b_limb_stride)
 {
-  using G = Geom<LOGN, true, flavor_of<A>()>;
-  KDot<A> kd{};
-  kd.k.a                 = da.out;
-  const LimbRec<A> *recs = static_cast<const LimbRec<A> *>(da.limbs);
-  const uint64_t    nl   = (uint64_t)(da.nlimbs > 0 ? da.nlimbs : 1);
-  for(uint64_t l = 0; l < nl && l < (uint64_t)kMaxLimbs; l++) kd.k.limbs[l] = recs[l];
-  kd.k.limb_stride = da.limb_stride;
-  kd.k.poly_stride = da.poly_stride ? da.poly_stride : (1ull << da.logn);
-  kd.k.logn        = da.logn;
-  kd.k.s0          = da.logn - (uint32_t)LOGN;
-  kd.k.lastinv     = LASTINV ? 1u : 0u;
-  kd.k.lazy        = LASTINV ? 0u : 1u;
-  kd.k.nblocks     = da.batch << kd.k.s0;
   kd.npairs        = (uint32_t)da.npairs;
   kd.lazy_in       = (uint32_t)da.lazy_in;
   kd.b_bcast       = (uint32_t)da.b_bcast;
-  kd.b_limb_stride = da.b_limb_stride;
+  kd.b_limb_stride = b_limb_stride;
   for(int i = 0; i < da.npairs && i < kMaxDot; i++) {
     kd.a[i] = da.a[i];
     kd.b[i] = da.b[i];
   }
-  /* the grid of the inverse block kernel (launch_fused): resident workgroups striding over the blocks */
-  uint64_t wgs = (kd.k.nblocks + G::BPW - 1) / G::BPW;
-  uint64_t cap = 1ull << 20;
-  if(G::PERSISTENT) {
-    constexpr int by_lds   = G::WG_PER_CU0;
-    constexpr int by_waves = (G::WPS * 4 * 64) / G::WG;
-    constexpr int per_cu   = by_lds < by_waves ? by_lds : by_waves;
-    cap                    = (uint64_t)(da.num_cus > 0 ? da.num_cus : 256) * (per_cu > 0 ? per_cu : 1) * block_oversub<LOGN, G::WG>(da.oversub, kd.k.s0 == 0);
-  }
-  if(!G::PERSISTENT && G::LDS_TW > 0) {
-    if(kd.k.s0 != 0) return hipErrorInvalidValue;
-    constexpr int per_cu = G::WG_PER_CU0 < 8 ? G::WG_PER_CU0 : 8;
-    cap                  = (uint64_t)(da.num_cus > 0 ? da.num_cus : 256) * (per_cu > 0 ? per_cu : 1) * 4;
-  }
-  if(da.max_grid > 0) cap = (uint64_t)da.max_grid;
-  cap = cap / nl > 0 ? cap / nl : 1;
-  if(G::BPW == 1 && kd.k.s0 > 0) { /* a workgroup keeps the tables of ONE block position */
-    if(cap < (1ull << kd.k.s0)) cap = 1ull << kd.k.s0;
-    cap &= ~((1ull << kd.k.s0) - 1);
-  }
-  if(wgs > cap) wgs = cap;
+}
+
+/* the inverse block kernel's grid: resident workgroups striding over the blocks */
+template <class A, int LOGN, int KSH, bool LASTINV> hipError_t launch_dot_blocks(const DotArgs &da)
+{
+  using G = Geom<LOGN, true, flavor_of<A>()>;
+  const uint32_t s0 = da.logn - (uint32_t)LOGN;
+  if(fills_tables<G>() && s0 != 0) return hipErrorInvalidValue;
+  KDot<A>        kd{};
+  const uint64_t nl = limb_count(da.nlimbs);
+  fill_kargs(kd.k, da.out, da.limbs, nl, da.limb_stride, da.poly_stride, da.logn, s0, da.batch << s0);
+  kd.k.lastinv = LASTINV ? 1u : 0u;
+  kd.k.lazy    = LASTINV ? 0u : 1u;
+  fill_dot(kd, da, da.b_limb_stride);
+  const uint64_t wgs = block_grid<G>(kd.k.nblocks, s0, nl, da.num_cus, da.max_grid, product_per_slot<G, LOGN>(da.oversub, s0 == 0));
   if(wgs == 0) return hipSuccess;
   kd.k.wgs_per_limb = (uint32_t)wgs;
-  if(da.ptrs) {
-    if constexpr(LASTINV) {
-      kd.k.ptab = reinterpret_cast<const uint64_t *>(da.out);
-      kd.k.a    = reinterpret_cast<uint64_t *>((uintptr_t)da.ptr_limb_off * 8u);
-      if(nl > 1) {
-        /* the limbs of an RNS set behind every table entry, da.limb_stride words apart: one launch over all of them */
-        if constexpr(multi_limb_built<A>()) {
-          hipLaunchKernelGGL((dot_inv_kernel<A, LOGN, KSH, true, true, true>), dim3((unsigned)wgs, (unsigned)nl), dim3(G::WG), 0, da.stream, kd);
-          return hipGetLastError();
-        } else {
-          return hipErrorNotSupported;
-        }
-      }
-      hipLaunchKernelGGL((dot_inv_kernel<A, LOGN, KSH, true, false, true>), dim3((unsigned)wgs), dim3(G::WG), 0, da.stream, kd);
-      return hipGetLastError();
-    } else {
+  if(da.ptrs) use_ptr_table(kd.k, da.out, da.ptr_limb_off);
+  /* (several limbs with tables: the limbs of an RNS set behind every table entry, da.limb_stride words apart) */
+  return with_bools([&](auto multi, auto ptrs) -> hipError_t {
+    constexpr bool MULTI = decltype(multi)::value, PTRS = decltype(ptrs)::value;
+    if constexpr((PTRS && !LASTINV) || (MULTI && !multi_limb_built<A>())) {
       return hipErrorNotSupported;
-    }
-  }
-  if(nl > 1) {
-    if constexpr(multi_limb_built<A>()) {
-      hipLaunchKernelGGL((dot_inv_kernel<A, LOGN, KSH, LASTINV, true>), dim3((unsigned)wgs, (unsigned)nl), dim3(G::WG), 0, da.stream, kd);
-      return hipGetLastError();
     } else {
-      return hipErrorNotSupported;
+      hipLaunchKernelGGL((dot_inv_kernel<A, LOGN, KSH, LASTINV, MULTI, PTRS>), dim3((unsigned)wgs, (unsigned)nl), dim3(G::WG), 0, da.stream, kd);
+      return hipGetLastError();
     }
-  }
-  hipLaunchKernelGGL((dot_inv_kernel<A, LOGN, KSH, LASTINV, false>), dim3((unsigned)wgs), dim3(G::WG), 0, da.stream, kd);
-  return hipGetLastError();
+  }, nl > 1, da.ptrs);
 }
 
 /* the NTT-domain product at N = 2^15..2^17 as ONE launch (team_dot_kernel); da.team_ctl: TeamCtl + nlimbs * batch counters, zeroed here */
@@ -737,70 +559,24 @@ template <class A, int KSH> hipError_t launch_team_dot(const DotArgs &da)
   if constexpr(!(A::kCompact || A::kIntWide)) {
     return hipErrorNotSupported;
   } else {
-    const uint64_t nl = (uint64_t)(da.nlimbs > 0 ? da.nlimbs : 1);
-    if(nl > (uint64_t)kMaxLimbs || !da.team_ctl || da.logn < (uint32_t)kTeamBlock + 3 || da.logn > (uint32_t)kTeamBlock + 5 ||
-       nl * da.batch >= (1ull << 31) || da.npairs < 1 || da.npairs > kMaxDot) {
-      return hipErrorNotSupported;
-    }
-    KTeamDot<A> kt{};
-    kt.d.k.a                = da.out;
-    const LimbRec<A> *recs = static_cast<const LimbRec<A> *>(da.limbs);
-    for(uint64_t l = 0; l < nl; l++) kt.d.k.limbs[l] = recs[l];
-    kt.d.k.limb_stride = nl > 1 ? da.limb_stride : 0;
-    kt.d.k.poly_stride = da.poly_stride ? da.poly_stride : (1ull << da.logn);
-    kt.d.k.logn        = da.logn;
-    kt.d.k.s0          = da.logn - (uint32_t)kTeamBlock;
-    kt.d.k.lastinv     = 1;
-    kt.d.k.lazy        = 0;
-    kt.d.k.nblocks     = da.batch;
-    kt.d.npairs        = (uint32_t)da.npairs;
-    kt.d.lazy_in       = (uint32_t)da.lazy_in;
-    kt.d.b_bcast       = (uint32_t)da.b_bcast;
-    kt.d.b_limb_stride = nl > 1 ? da.b_limb_stride : 0;
-    for(int i = 0; i < da.npairs; i++) {
-      kt.d.a[i] = da.a[i];
-      kt.d.b[i] = da.b[i];
-    }
-    kt.ctl        = static_cast<TeamCtl *>(da.team_ctl);
-    kt.lag        = (uint32_t)(da.team_lag > 0 ? da.team_lag : 8);
-    kt.nlimbs     = (uint32_t)nl;
-    kt.poly_major = nl > 1 && kt.d.k.poly_stride > kt.d.k.limb_stride;
-    kt.split_rcp  = team_split_rcp(kt.poly_major ? nl : da.batch);
-    const size_t bytes = sizeof(TeamCtl) + (size_t)(nl * da.batch) * sizeof(unsigned);
-    hipError_t   e     = team_ctl_clear(da.team_ctl, bytes, da.stream);
+    if(da.logn < (uint32_t)kTeamBlock + 3 || da.logn > (uint32_t)kTeamBlock + 5 || da.npairs < 1 || da.npairs > kMaxDot) return hipErrorNotSupported;
+    KTeamDot<A>      kt{};
+    dim3             grid;
+    const hipError_t e = team_prologue<TeamCtl>(kt, da, 31, 1, 8, grid);
     if(e != hipSuccess) return e;
-    uint64_t wgs = (uint64_t)(da.num_cus > 0 ? da.num_cus : 256) * (da.team_wpc > 0 ? da.team_wpc : 4);
-    if(da.max_grid > 0) wgs = (uint64_t)da.max_grid;
-    kt.d.k.wgs_per_limb = (uint32_t)wgs;
-    const dim3 g((unsigned)wgs), t(256);
-    if(da.ptrs) {
-      kt.d.k.ptab = reinterpret_cast<const uint64_t *>(da.out);
-      kt.d.k.a    = reinterpret_cast<uint64_t *>((uintptr_t)da.ptr_limb_off * 8u);
-#define NTT_TEAM_DOT_PTRS(LEADV)                                                                             \
-  do {                                                                                                       \
-    if(nl > 1) hipLaunchKernelGGL((team_dot_kernel<A, LEADV, KSH, true, true>), g, t, 0, da.stream, kt);     \
-    else hipLaunchKernelGGL((team_dot_kernel<A, LEADV, KSH, false, true>), g, t, 0, da.stream, kt);          \
-  } while(0)
-      switch(da.logn - kTeamBlock) {
-        case 3: NTT_TEAM_DOT_PTRS(3); break;
-        case 4: NTT_TEAM_DOT_PTRS(4); break;
-        default: NTT_TEAM_DOT_PTRS(5); break;
-      }
-#undef NTT_TEAM_DOT_PTRS
-      return hipGetLastError();
-    }
-#define NTT_TEAM_DOT(LEADV)                                                                                  \
-  do {                                                                                                       \
-    if(nl > 1) hipLaunchKernelGGL((team_dot_kernel<A, LEADV, KSH, true>), g, t, 0, da.stream, kt);           \
-    else hipLaunchKernelGGL((team_dot_kernel<A, LEADV, KSH, false>), g, t, 0, da.stream, kt);                \
-  } while(0)
-    switch(da.logn - kTeamBlock) {
-      case 3: NTT_TEAM_DOT(3); break;
-      case 4: NTT_TEAM_DOT(4); break;
-      default: NTT_TEAM_DOT(5); break;
-    }
-#undef NTT_TEAM_DOT
-    return hipGetLastError();
+    const bool multi = kt.nlimbs > 1;
+    fill_kargs(kt.d.k, da.out, da.limbs, kt.nlimbs, multi ? da.limb_stride : 0, da.poly_stride, da.logn, da.logn - (uint32_t)kTeamBlock, da.batch);
+    kt.d.k.wgs_per_limb = grid.x;
+    kt.d.k.lastinv      = 1;
+    kt.d.k.lazy         = 0;
+    fill_dot(kt.d, da, multi ? da.b_limb_stride : 0);
+    if(da.ptrs) use_ptr_table(kt.d.k, da.out, da.ptr_limb_off);
+    return with_int<3, 5>((int)(da.logn - kTeamBlock), hipErrorNotSupported, [&](auto lead) {
+      return with_bools([&](auto multi_c, auto ptrs) {
+        hipLaunchKernelGGL((team_dot_kernel<A, decltype(lead)::value, KSH, decltype(multi_c)::value, decltype(ptrs)::value>), grid, dim3(256), 0, da.stream, kt);
+        return hipGetLastError();
+      }, multi, da.ptrs);
+    });
   }
 }
 
@@ -814,85 +590,47 @@ template <class A, int KSH> hipError_t launch_dot_impl(const DotArgs &da)
     if(da.block_log == (uint32_t)kFusedLarge) return launch_dot_blocks<A, kFusedLarge, KSH, false>(da);
     return hipErrorInvalidValue;
   }
-  switch(da.logn) {
-#define NTT_DOT_CASE(LN) \
-  case LN: return launch_dot_blocks<A, LN, KSH, true>(da);
-    NTT_DOT_CASE(6) NTT_DOT_CASE(7) NTT_DOT_CASE(8) NTT_DOT_CASE(9) NTT_DOT_CASE(10) NTT_DOT_CASE(11) NTT_DOT_CASE(12) NTT_DOT_CASE(13)
-    NTT_DOT_CASE(14)
-#undef NTT_DOT_CASE
-    default: return hipErrorNotSupported;
-  }
+  return with_int<6, 14>((int)da.logn, hipErrorNotSupported, [&](auto ln) { return launch_dot_blocks<A, decltype(ln)::value, KSH, true>(da); });
 }
 
-template <class A, int LOGN, int KSH> hipError_t launch_fwd_mul_blocks(const MulArgs &ma)
+/* the operand fields of fwd_mul_kernel, team_mul_kernel and onepass_mul_kernel */
+template <class A> inline void fill_mul(KMul<A> &km, const MulArgs &ma, uint64_t b_limb_stride)
 {
-  using G = Geom<LOGN, false, flavor_of<A>()>;
-  KMul<A> km{};
-  km.k.a                 = ma.a;
-  const LimbRec<A> *recs = static_cast<const LimbRec<A> *>(ma.limbs);
-  const uint64_t    nl   = (uint64_t)(ma.nlimbs > 0 ? ma.nlimbs : 1);
-  for(uint64_t l = 0; l < nl && l < (uint64_t)kMaxLimbs; l++) km.k.limbs[l] = recs[l];
-  km.k.limb_stride = ma.limb_stride;
-  km.k.poly_stride = ma.poly_stride ? ma.poly_stride : (1ull << ma.logn);
-  km.k.logn        = ma.logn;
-  km.k.s0          = ma.logn - (uint32_t)LOGN;
-  km.k.nblocks     = ma.batch << km.k.s0;
   km.b             = ma.b;
   km.out           = ma.out;
-  km.b_limb_stride = ma.b_limb_stride;
+  km.b_limb_stride = b_limb_stride;
   km.lazy_in       = (uint32_t)ma.lazy_in;
   km.b_bcast       = (uint32_t)ma.b_bcast;
   km.accumulate    = (uint32_t)ma.accumulate;
-  /* the grid of the forward block kernel (launch_fused) */
-  uint64_t wgs = (km.k.nblocks + G::BPW - 1) / G::BPW;
-  uint64_t cap = 1ull << 20;
-  if(G::PERSISTENT) {
-    constexpr int by_lds   = G::WG_PER_CU0;
-    constexpr int by_waves = (G::WPS * 4 * 64) / G::WG;
-    constexpr int per_cu   = by_lds < by_waves ? by_lds : by_waves;
-    cap                    = (uint64_t)(ma.num_cus > 0 ? ma.num_cus : 256) * (per_cu > 0 ? per_cu : 1) * block_oversub<LOGN, G::WG>(ma.oversub, km.k.s0 == 0);
-  }
-  if(!G::PERSISTENT && G::LDS_TW > 0) {
-    if(km.k.s0 != 0) return hipErrorInvalidValue;
-    constexpr int per_cu = G::WG_PER_CU0 < 8 ? G::WG_PER_CU0 : 8;
-    cap                  = (uint64_t)(ma.num_cus > 0 ? ma.num_cus : 256) * (per_cu > 0 ? per_cu : 1) * 4;
-  }
-  if(ma.max_grid > 0) cap = (uint64_t)ma.max_grid;
-  cap = cap / nl > 0 ? cap / nl : 1;
-  if(G::BPW == 1 && km.k.s0 > 0) { /* a workgroup keeps the tables of ONE block position */
-    if(cap < (1ull << km.k.s0)) cap = 1ull << km.k.s0;
-    cap &= ~((1ull << km.k.s0) - 1);
-  }
-  if(G::BPW > 1 && km.k.s0 > 0) return hipErrorInvalidValue; /* (two blocks per workgroup: whole polynomials only) */
-  if(wgs > cap) wgs = cap;
+}
+
+/* the forward block kernel's grid */
+template <class A, int LOGN, int KSH> hipError_t launch_fwd_mul_blocks(const MulArgs &ma)
+{
+  using G = Geom<LOGN, false, flavor_of<A>()>;
+  const uint32_t s0 = ma.logn - (uint32_t)LOGN;
+  if((fills_tables<G>() || G::BPW > 1) && s0 != 0) return hipErrorInvalidValue; /* (two blocks per workgroup: whole polynomials only) */
+  KMul<A>        km{};
+  const uint64_t nl = limb_count(ma.nlimbs);
+  fill_kargs(km.k, ma.a, ma.limbs, nl, ma.limb_stride, ma.poly_stride, ma.logn, s0, ma.batch << s0);
+  fill_mul(km, ma, ma.b_limb_stride);
+  const uint64_t wgs = block_grid<G>(km.k.nblocks, s0, nl, ma.num_cus, ma.max_grid, product_per_slot<G, LOGN>(ma.oversub, s0 == 0));
   if(wgs == 0) return hipSuccess;
   km.k.wgs_per_limb = (uint32_t)wgs;
   if(ma.ptrs) {
-    if(km.k.s0 != 0) return hipErrorNotSupported;
-    km.k.ptab = reinterpret_cast<const uint64_t *>(ma.a);
-    km.k.a    = reinterpret_cast<uint64_t *>((uintptr_t)ma.ptr_limb_off * 8u);
-    if(nl > 1) {
-      /* the limbs of an RNS set behind every table entry, ma.limb_stride words apart: one launch over all of them */
-      if constexpr(multi_limb_built<A>()) {
-        hipLaunchKernelGGL((fwd_mul_kernel<A, LOGN, KSH, true, true>), dim3((unsigned)wgs, (unsigned)nl), dim3(G::WG), 0, ma.stream, km);
-        return hipGetLastError();
-      } else {
-        return hipErrorNotSupported;
-      }
-    }
-    hipLaunchKernelGGL((fwd_mul_kernel<A, LOGN, KSH, false, true>), dim3((unsigned)wgs), dim3(G::WG), 0, ma.stream, km);
-    return hipGetLastError();
+    if(s0 != 0) return hipErrorNotSupported;
+    use_ptr_table(km.k, ma.a, ma.ptr_limb_off);
   }
-  if(nl > 1) {
-    if constexpr(multi_limb_built<A>()) {
-      hipLaunchKernelGGL((fwd_mul_kernel<A, LOGN, KSH, true>), dim3((unsigned)wgs, (unsigned)nl), dim3(G::WG), 0, ma.stream, km);
-      return hipGetLastError();
-    } else {
+  /* (several limbs with tables: the limbs of an RNS set behind every table entry, ma.limb_stride words apart) */
+  return with_bools([&](auto multi, auto ptrs) -> hipError_t {
+    constexpr bool MULTI = decltype(multi)::value, PTRS = decltype(ptrs)::value;
+    if constexpr(MULTI && !multi_limb_built<A>()) {
       return hipErrorNotSupported;
+    } else {
+      hipLaunchKernelGGL((fwd_mul_kernel<A, LOGN, KSH, MULTI, PTRS>), dim3((unsigned)wgs, (unsigned)nl), dim3(G::WG), 0, ma.stream, km);
+      return hipGetLastError();
     }
-  }
-  hipLaunchKernelGGL((fwd_mul_kernel<A, LOGN, KSH, false>), dim3((unsigned)wgs), dim3(G::WG), 0, ma.stream, km);
-  return hipGetLastError();
+  }, nl > 1, ma.ptrs);
 }
 
 template <class A, int KSH> hipError_t launch_team_mul(const MulArgs &ma)
@@ -900,111 +638,50 @@ template <class A, int KSH> hipError_t launch_team_mul(const MulArgs &ma)
   if constexpr(!(A::kCompact || A::kIntWide)) {
     return hipErrorNotSupported;
   } else {
-    const uint64_t nl = (uint64_t)(ma.nlimbs > 0 ? ma.nlimbs : 1);
-    if(nl > (uint64_t)kMaxLimbs || !ma.team_ctl || ma.logn < (uint32_t)kTeamBlock + 3 || ma.logn > (uint32_t)kTeamBlock + 5 ||
-       nl * ma.batch >= (1ull << 31)) {
-      return hipErrorNotSupported;
-    }
-    KTeamMul<A> kt{};
-    kt.m.k.a               = ma.a;
-    const LimbRec<A> *recs = static_cast<const LimbRec<A> *>(ma.limbs);
-    for(uint64_t l = 0; l < nl; l++) kt.m.k.limbs[l] = recs[l];
-    kt.m.k.limb_stride = nl > 1 ? ma.limb_stride : 0;
-    kt.m.k.poly_stride = ma.poly_stride ? ma.poly_stride : (1ull << ma.logn);
-    kt.m.k.logn        = ma.logn;
-    kt.m.k.s0          = ma.logn - (uint32_t)kTeamBlock;
-    kt.m.k.lazy        = 0;
-    kt.m.k.nblocks     = ma.batch;
-    kt.m.b             = ma.b;
-    kt.m.out           = ma.out;
-    kt.m.b_limb_stride = nl > 1 ? ma.b_limb_stride : 0;
-    kt.m.lazy_in       = (uint32_t)ma.lazy_in;
-    kt.m.b_bcast       = (uint32_t)ma.b_bcast;
-    kt.m.accumulate    = (uint32_t)ma.accumulate;
-    kt.ctl             = static_cast<TeamCtl *>(ma.team_ctl);
-    kt.lag             = (uint32_t)(ma.team_lag > 0 ? ma.team_lag : 8);
-    kt.nlimbs          = (uint32_t)nl;
-    kt.poly_major      = nl > 1 && kt.m.k.poly_stride > kt.m.k.limb_stride;
-    kt.split_rcp       = team_split_rcp(kt.poly_major ? nl : ma.batch);
-    const size_t bytes = sizeof(TeamCtl) + (size_t)(nl * ma.batch) * sizeof(unsigned);
-    hipError_t   e     = team_ctl_clear(ma.team_ctl, bytes, ma.stream);
+    if(ma.logn < (uint32_t)kTeamBlock + 3 || ma.logn > (uint32_t)kTeamBlock + 5) return hipErrorNotSupported;
+    KTeamMul<A>      kt{};
+    dim3             grid;
+    const hipError_t e = team_prologue<TeamCtl>(kt, ma, 31, 1, 8, grid);
     if(e != hipSuccess) return e;
-    uint64_t wgs = (uint64_t)(ma.num_cus > 0 ? ma.num_cus : 256) * (ma.team_wpc > 0 ? ma.team_wpc : 4);
-    if(ma.max_grid > 0) wgs = (uint64_t)ma.max_grid;
-    kt.m.k.wgs_per_limb = (uint32_t)wgs;
-    const dim3 g((unsigned)wgs), t(256);
-    if(ma.ptrs) {
-      kt.m.k.ptab = reinterpret_cast<const uint64_t *>(ma.a);
-      kt.m.k.a    = reinterpret_cast<uint64_t *>((uintptr_t)ma.ptr_limb_off * 8u);
-#define NTT_TEAM_MUL_PTRS(LEADV)                                                                             \
-  do {                                                                                                       \
-    if(nl > 1) hipLaunchKernelGGL((team_mul_kernel<A, LEADV, KSH, true, true>), g, t, 0, ma.stream, kt);     \
-    else hipLaunchKernelGGL((team_mul_kernel<A, LEADV, KSH, false, true>), g, t, 0, ma.stream, kt);          \
-  } while(0)
-      switch(ma.logn - kTeamBlock) {
-        case 3: NTT_TEAM_MUL_PTRS(3); break;
-        case 4: NTT_TEAM_MUL_PTRS(4); break;
-        default: NTT_TEAM_MUL_PTRS(5); break;
-      }
-#undef NTT_TEAM_MUL_PTRS
-      return hipGetLastError();
-    }
-#define NTT_TEAM_MUL(LEADV)                                                                                  \
-  do {                                                                                                       \
-    if(nl > 1) hipLaunchKernelGGL((team_mul_kernel<A, LEADV, KSH, true>), g, t, 0, ma.stream, kt);           \
-    else hipLaunchKernelGGL((team_mul_kernel<A, LEADV, KSH, false>), g, t, 0, ma.stream, kt);                \
-  } while(0)
-    switch(ma.logn - kTeamBlock) {
-      case 3: NTT_TEAM_MUL(3); break;
-      case 4: NTT_TEAM_MUL(4); break;
-      default: NTT_TEAM_MUL(5); break;
-    }
-#undef NTT_TEAM_MUL
-    return hipGetLastError();
+    const bool multi = kt.nlimbs > 1;
+    fill_kargs(kt.m.k, ma.a, ma.limbs, kt.nlimbs, multi ? ma.limb_stride : 0, ma.poly_stride, ma.logn, ma.logn - (uint32_t)kTeamBlock, ma.batch);
+    kt.m.k.wgs_per_limb = grid.x;
+    kt.m.k.lazy         = 0;
+    fill_mul(kt.m, ma, multi ? ma.b_limb_stride : 0);
+    if(ma.ptrs) use_ptr_table(kt.m.k, ma.a, ma.ptr_limb_off);
+    return with_int<3, 5>((int)(ma.logn - kTeamBlock), hipErrorNotSupported, [&](auto lead) {
+      return with_bools([&](auto multi_c, auto ptrs) {
+        hipLaunchKernelGGL((team_mul_kernel<A, decltype(lead)::value, KSH, decltype(multi_c)::value, decltype(ptrs)::value>), grid, dim3(256), 0, ma.stream, kt);
+        return hipGetLastError();
+      }, multi, ma.ptrs);
+    });
   }
 }
 
-/* N = 2^15 in one pass with the product at the output (onepass_mul_kernel): one persistent 1024-thread workgroup per CU */
+/* N = 2^15 in one pass with the product at the output (onepass_mul_kernel) */
 template <class A, int KSH> hipError_t launch_onepass_mul(const MulArgs &ma)
 {
   if constexpr(!onepass_built<A>()) {
     return hipErrorNotSupported;
   } else {
     if(ma.logn != (uint32_t)kFusedLarge + 1) return hipErrorNotSupported;
-    const uint64_t nl = (uint64_t)(ma.nlimbs > 0 ? ma.nlimbs : 1);
-    KMul<A> km{};
-    km.k.a = ma.a;
-    const LimbRec<A> *recs = static_cast<const LimbRec<A> *>(ma.limbs);
-    for(uint64_t i = 0; i < nl; i++) km.k.limbs[i] = recs[i];
-    km.k.limb_stride = ma.limb_stride;
-    km.k.poly_stride = ma.poly_stride ? ma.poly_stride : (1ull << ma.logn);
-    km.k.logn        = ma.logn;
-    km.k.s0          = 1;
-    km.k.nblocks     = ma.batch;
-    km.b             = ma.b;
-    km.out           = ma.out;
-    km.b_limb_stride = ma.b_limb_stride;
-    km.lazy_in       = (uint32_t)ma.lazy_in;
-    km.b_bcast       = (uint32_t)ma.b_bcast;
-    km.accumulate    = (uint32_t)ma.accumulate;
-    uint64_t wgs = ma.batch;
-    uint64_t cap = (uint64_t)(ma.num_cus > 0 ? ma.num_cus : 256);
-    if(ma.max_grid > 0) cap = (uint64_t)ma.max_grid;
-    cap = cap / nl > 0 ? cap / nl : 1;
-    if(wgs > cap) wgs = cap;
+    const uint64_t nl = limb_count(ma.nlimbs);
+    KMul<A>        km{};
+    fill_kargs(km.k, ma.a, ma.limbs, nl, ma.limb_stride, ma.poly_stride, ma.logn, 1, ma.batch);
+    fill_mul(km, ma, ma.b_limb_stride);
+    const uint64_t wgs = onepass_grid(ma.batch, nl, ma.num_cus, ma.max_grid);
     if(wgs == 0) return hipSuccess;
     km.k.wgs_per_limb = (uint32_t)wgs;
-    const dim3 grid((unsigned)wgs, (unsigned)nl);
-    if(ma.ptrs) {
-      if(nl > 1) return hipErrorNotSupported;
-      km.k.ptab = reinterpret_cast<const uint64_t *>(ma.a);
-      km.k.a    = reinterpret_cast<uint64_t *>((uintptr_t)ma.ptr_limb_off * 8u);
-      hipLaunchKernelGGL((onepass_mul_kernel<A, KSH, false, true>), grid, dim3(1024), 0, ma.stream, km);
-      return hipGetLastError();
-    }
-    if(nl > 1) hipLaunchKernelGGL((onepass_mul_kernel<A, KSH, true>), grid, dim3(1024), 0, ma.stream, km);
-    else hipLaunchKernelGGL((onepass_mul_kernel<A, KSH, false>), grid, dim3(1024), 0, ma.stream, km);
-    return hipGetLastError();
+    if(ma.ptrs) use_ptr_table(km.k, ma.a, ma.ptr_limb_off);
+    return with_bools([&](auto multi, auto ptrs) -> hipError_t {
+      constexpr bool MULTI = decltype(multi)::value, PTRS = decltype(ptrs)::value;
+      if constexpr(MULTI && PTRS) { /* (tables: one limb per launch) */
+        return hipErrorNotSupported;
+      } else {
+        hipLaunchKernelGGL((onepass_mul_kernel<A, KSH, MULTI, PTRS>), dim3((unsigned)wgs, (unsigned)nl), dim3(1024), 0, ma.stream, km);
+        return hipGetLastError();
+      }
+    }, nl > 1, ma.ptrs);
   }
 }
 
@@ -1019,15 +696,41 @@ template <class A, int KSH> hipError_t launch_fwd_mul_impl(const MulArgs &ma)
     if(ma.block_log == (uint32_t)kFusedLarge) return launch_fwd_mul_blocks<A, kFusedLarge, KSH>(ma);
     return hipErrorInvalidValue;
   }
-  switch(ma.logn) {
-#define NTT_MUL_CASE(LN) \
-  case LN: return launch_fwd_mul_blocks<A, LN, KSH>(ma);
-    NTT_MUL_CASE(6) NTT_MUL_CASE(7) NTT_MUL_CASE(8) NTT_MUL_CASE(9) NTT_MUL_CASE(10) NTT_MUL_CASE(11) NTT_MUL_CASE(12) NTT_MUL_CASE(13)
-    NTT_MUL_CASE(14)
-#undef NTT_MUL_CASE
-    default: return hipErrorNotSupported;
-  }
+  return with_int<6, 14>((int)ma.logn, hipErrorNotSupported, [&](auto ln) { return launch_fwd_mul_blocks<A, decltype(ln)::value, KSH>(ma); });
 }
+
+/* launch_pass<A, KSH>: pa.fused and pa.r pick the launcher */
+template <class A, int KSH> hipError_t launch_pass_impl(const PassArgs &pa)
+{
+  return with_bools([&](auto inverse) -> hipError_t {
+    constexpr bool INV = decltype(inverse)::value;
+    if(pa.fused == 4) return launch_onepass<A, INV, KSH>(pa);
+    if(pa.fused == 3) return with_int<3, 5>(pa.r, hipErrorInvalidValue, [&](auto lead) { return launch_team<A, decltype(lead)::value, INV, KSH>(pa); });
+    if(pa.fused == 2) return with_int<1, 3>(pa.r, hipErrorInvalidValue, [&](auto lead) { return launch_twophase<A, decltype(lead)::value, INV, KSH>(pa); });
+    if(pa.fused) return with_int<6, 14>(pa.r, hipErrorInvalidValue, [&](auto ln) { return launch_fused<A, decltype(ln)::value, INV, KSH>(pa); });
+    return with_int<1, 4>(pa.r, hipErrorInvalidValue, [&](auto r) { return launch_column<A, decltype(r)::value, INV, KSH>(pa); });
+  }, pa.inverse);
+}
+
+/* the radix-4 formulation (ArithU64R4): block passes, and column passes of one or two radix-4 levels before (forward) or
+ * after (inverse) them (ntt_passplan.h: make_passes_r4) */
+template <class A, int KSH> hipError_t launch_pass_radix4_impl(const PassArgs &pa)
+{
+  return with_bools([&](auto inverse) -> hipError_t {
+    constexpr bool INV = decltype(inverse)::value;
+    if(pa.fused == 1) return with_int<6, 14>(pa.r, hipErrorInvalidValue, [&](auto ln) { return launch_fused<A, decltype(ln)::value, INV, KSH>(pa); });
+    if(pa.fused || pa.s != 0) return hipErrorInvalidValue;
+    if(pa.r == 2) return launch_column<A, 2, INV, KSH>(pa);
+    if(pa.r == 4) return launch_column<A, 4, INV, KSH>(pa);
+    return hipErrorInvalidValue;
+  }, pa.inverse);
+}
+
+/* each instantiating .hip file expands the macros of its policy and class once */
+#define NTT_DEFINE_LAUNCH_PASS(A, KSH) \
+  template <> hipError_t launch_pass<A, KSH>(const PassArgs &pa) { return launch_pass_impl<A, KSH>(pa); }
+#define NTT_DEFINE_LAUNCH_PASS_RADIX4(A, KSH) \
+  template <> hipError_t launch_pass<A, KSH>(const PassArgs &pa) { return launch_pass_radix4_impl<A, KSH>(pa); }
 
 #define NTT_DEFINE_LAUNCH_FWD_MUL(A, KSH) \
   template <> hipError_t launch_fwd_mul<A, KSH>(const MulArgs &ma) { return launch_fwd_mul_impl<A, KSH>(ma); }
@@ -1040,68 +743,5 @@ template <class A, int KSH> hipError_t launch_fwd_mul_impl(const MulArgs &ma)
 /* (a translation unit of its own per policy: inst_team_*.hip) */
 #define NTT_DEFINE_LAUNCH_TEAM_PRODUCT(A, KSH) \
   template <> hipError_t launch_team_product<A, KSH>(const ProdArgs &pa) { return launch_team_product_impl<A, KSH>(pa); }
-
-/* body of launch_pass<A,KSH>; each instantiating .hip file expands this once */
-#define NTT_DEFINE_LAUNCH_PASS(A, KSH)                                                   \
-  template <> hipError_t launch_pass<A, KSH>(const PassArgs &pa)                         \
-  {                                                                                      \
-    if(pa.fused == 4) return pa.inverse ? launch_onepass<A, true, KSH>(pa) : launch_onepass<A, false, KSH>(pa); \
-    if(pa.fused == 3) {                                                                  \
-      switch(pa.r) {                                                                     \
-        case 3: return pa.inverse ? launch_team<A, 3, true, KSH>(pa) : launch_team<A, 3, false, KSH>(pa); \
-        case 4: return pa.inverse ? launch_team<A, 4, true, KSH>(pa) : launch_team<A, 4, false, KSH>(pa); \
-        case 5: return pa.inverse ? launch_team<A, 5, true, KSH>(pa) : launch_team<A, 5, false, KSH>(pa); \
-        default: return hipErrorInvalidValue;                                            \
-      }                                                                                  \
-    }                                                                                    \
-    if(pa.fused == 2) {                                                                  \
-      switch(pa.r) {                                                                     \
-        case 1: return pa.inverse ? launch_twophase<A, 1, true, KSH>(pa) : launch_twophase<A, 1, false, KSH>(pa); \
-        case 2: return pa.inverse ? launch_twophase<A, 2, true, KSH>(pa) : launch_twophase<A, 2, false, KSH>(pa); \
-        case 3: return pa.inverse ? launch_twophase<A, 3, true, KSH>(pa) : launch_twophase<A, 3, false, KSH>(pa); \
-        default: return hipErrorInvalidValue;                                            \
-      }                                                                                  \
-    }                                                                                    \
-    if(pa.fused) {                                                                       \
-      switch(pa.r) {                                                                     \
-        NTT_FUSED_CASES(A, KSH)                                                          \
-        default: return hipErrorInvalidValue;                                            \
-      }                                                                                  \
-    }                                                                                    \
-    switch(pa.r) {                                                                       \
-      case 1: return pa.inverse ? launch_column<A, 1, true, KSH>(pa) : launch_column<A, 1, false, KSH>(pa); \
-      case 2: return pa.inverse ? launch_column<A, 2, true, KSH>(pa) : launch_column<A, 2, false, KSH>(pa); \
-      case 3: return pa.inverse ? launch_column<A, 3, true, KSH>(pa) : launch_column<A, 3, false, KSH>(pa); \
-      case 4: return pa.inverse ? launch_column<A, 4, true, KSH>(pa) : launch_column<A, 4, false, KSH>(pa); \
-      default: return hipErrorInvalidValue;                                              \
-    }                                                                                    \
-  }
-
-/* the radix-4 formulation (ArithU64R4): block passes, and column passes of one or two radix-4 levels before (forward) or
- * after (inverse) them (ntt_passplan.h: make_passes_r4) */
-#define NTT_DEFINE_LAUNCH_PASS_RADIX4(A, KSH)                                            \
-  template <> hipError_t launch_pass<A, KSH>(const PassArgs &pa)                         \
-  {                                                                                      \
-    if(pa.fused == 1) {                                                                  \
-      switch(pa.r) {                                                                     \
-        NTT_FUSED_CASES(A, KSH)                                                          \
-        default: return hipErrorInvalidValue;                                            \
-      }                                                                                  \
-    }                                                                                    \
-    if(pa.fused || pa.s != 0) return hipErrorInvalidValue;                               \
-    switch(pa.r) {                                                                       \
-      case 2: return pa.inverse ? launch_column<A, 2, true, KSH>(pa) : launch_column<A, 2, false, KSH>(pa); \
-      case 4: return pa.inverse ? launch_column<A, 4, true, KSH>(pa) : launch_column<A, 4, false, KSH>(pa); \
-      default: return hipErrorInvalidValue;                                              \
-    }                                                                                    \
-  }
-
-#define NTT_FUSED_CASE(A, KSH, LN) \
-  case LN: return pa.inverse ? launch_fused<A, LN, true, KSH>(pa) : launch_fused<A, LN, false, KSH>(pa);
-
-#define NTT_FUSED_CASES(A, KSH)                                                        \
-  NTT_FUSED_CASE(A, KSH, 6) NTT_FUSED_CASE(A, KSH, 7) NTT_FUSED_CASE(A, KSH, 8)        \
-  NTT_FUSED_CASE(A, KSH, 9) NTT_FUSED_CASE(A, KSH, 10) NTT_FUSED_CASE(A, KSH, 11)      \
-  NTT_FUSED_CASE(A, KSH, 12) NTT_FUSED_CASE(A, KSH, 13) NTT_FUSED_CASE(A, KSH, 14)
 
 } /* namespace ntt */

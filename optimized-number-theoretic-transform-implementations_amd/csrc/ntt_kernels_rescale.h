@@ -100,38 +100,16 @@ template <class A, int LOGN, int KSH> hipError_t launch_rescale_fwd_n(const Resc
 {
   using G = Geom<LOGN, false, flavor_of<A>()>;
   if(ra.nlimbs < 1 || ra.nlimbs > kRescaleLimbs || ra.nlimbs > kMaxLimbs) return hipErrorInvalidValue;
-  KRescale<A>       kr{};
-  const LimbRec<A> *recs = static_cast<const LimbRec<A> *>(ra.limbs);
-  for(int l = 0; l < ra.nlimbs; l++) {
-    kr.k.limbs[l] = recs[l];
-    kr.rl[l]      = ra.rl[l];
-  }
-  kr.k.a           = ra.c;
-  kr.k.limb_stride = ra.limb_stride;
-  kr.k.poly_stride = ra.poly_stride ? ra.poly_stride : (1ull << ra.logn);
-  kr.k.logn        = ra.logn;
-  kr.k.s0          = 0;
-  kr.k.nblocks     = ra.batch;
-  kr.t             = ra.t;
-  kr.qL            = ra.qL;
-  kr.hL            = ra.hL;
-  /* the grid of the forward block kernel's plain loop (launch_fwd_mul_blocks), the x extent a multiple of 8 */
-  const uint64_t nl  = (uint64_t)ra.nlimbs;
-  uint64_t       wgs = (ra.batch + G::BPW - 1) / G::BPW;
-  uint64_t       cap = 1ull << 20;
-  if(G::PERSISTENT) {
-    constexpr int by_lds   = G::WG_PER_CU0;
-    constexpr int by_waves = (G::WPS * 4 * 64) / G::WG;
-    constexpr int per_cu   = by_lds < by_waves ? by_lds : by_waves;
-    cap                    = (uint64_t)(ra.num_cus > 0 ? ra.num_cus : 256) * (per_cu > 0 ? per_cu : 1);
-  } else if(G::LDS_TW > 0) {
-    constexpr int per_cu = G::WG_PER_CU0 < 8 ? G::WG_PER_CU0 : 8;
-    cap                  = (uint64_t)(ra.num_cus > 0 ? ra.num_cus : 256) * (per_cu > 0 ? per_cu : 1) * 4;
-  }
-  if(ra.max_grid > 0) cap = (uint64_t)ra.max_grid;
-  cap = cap / nl > 8 ? (cap / nl) & ~7ull : 8;
-  if(wgs > cap) wgs = cap;
-  wgs = (wgs + 7) & ~7ull; /* (workgroups past the last block exit at once) */
+  KRescale<A>    kr{};
+  const uint64_t nl = (uint64_t)ra.nlimbs;
+  fill_kargs(kr.k, ra.c, ra.limbs, nl, ra.limb_stride, ra.poly_stride, ra.logn, 0, ra.batch);
+  for(int l = 0; l < ra.nlimbs; l++) kr.rl[l] = ra.rl[l];
+  kr.t  = ra.t;
+  kr.qL = ra.qL;
+  kr.hL = ra.hL;
+  /* the plain loop of the forward block kernel: no oversubscription of the persistent sizes, four table-filling workgroups per
+   * slot below them; the x extent a multiple of 8 (the header's note on the XCDs) */
+  const uint64_t wgs = block_grid<G>(ra.batch, 0, nl, ra.num_cus, ra.max_grid, G::PERSISTENT ? 1 : 4, true);
   if(ra.batch == 0) return hipSuccess;
   kr.k.wgs_per_limb = (uint32_t)wgs;
   hipLaunchKernelGGL((rescale_fwd_kernel<A, LOGN, KSH>), dim3((unsigned)wgs, (unsigned)nl), dim3(G::WG), 0, ra.stream, kr);
