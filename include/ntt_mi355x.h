@@ -345,6 +345,48 @@ NTT_API int ntt_rns_mod_down_batch(int nq, int np, ntt_plan *const *plans, uint6
 NTT_API int ntt_rns_mod_down_batch_strided(int nq, int np, ntt_plan *const *plans, uint64_t *d_a, uint64_t limb_stride,
                                            uint64_t poly_stride, uint64_t batch, unsigned flags, void *stream);
 
+/* ---- Galois automorphisms (rotation, conjugation) and the rotation key product.  For odd g, 0 < g < 2N,
+ *     sigma_g(a)(X) = a(X^g)  in Z_q[X] / (X^N + 1).
+ * g = 5^steps mod 2N rotates the CKKS / BGV slots by `steps` (ntt_galois_rotation; negative steps: the inverse power),
+ * g = 2N - 1 is the conjugation, g = 1 is a copy.
+ * Coefficients (without NTT_GALOIS_TRANSFORMED; natural order, canonical words in and out): with u = g^-1 t mod 2N for t in [0, N),
+ *     out[t] = a[u] if u < N, else (q - a[u - N]) mod q  (a zero stays zero);
+ * equivalently a[i] goes to position g i mod N, negated when (g i mod 2N) >= N.
+ * NTT domain (NTT_GALOIS_TRANSFORMED; bit-reversed storage, as ntt_fwd_batch leaves it): storage slot s holds the evaluation at
+ * psi^(2i+1), i = bitrev_m(s), m = log2 N, and sigma_g is a permutation of words without arithmetic:
+ *     out[s] = in[bitrev_m(j)],  j = (g i + (g - 1) / 2) mod N,  i = bitrev_m(s).
+ * Words are copied bit for bit, so lazy words (ntt_fwd_batch_lazy) pass through.  ntt_galois_batch is the one-limb case
+ * ([batch][N]); the RNS forms take the layouts of the other RNS forms ([limb][batch][N]; _strided: any strides those accept, both
+ * operands in the same layout).  One launch per 16 limbs.
+ * ntt_rns_galois_dot_batch is the inner loop of hoisted rotations: the ModUp'd digits a_i^ (NTT domain, over Q u P) are formed once
+ * per ciphertext, and each rotation needs c^ = sum_{i<k} sigma_g(a_i^) (.) key_i^ per limb (NTT_GALOIS_ACCUMULATE: c^ += ..., c^
+ * canonical on entry), then ModDown.  One element-wise kernel, the permutation applied while the digits are read:
+ *     c[s] (+)= sum_i a_i[bitrev_m(j(s))] * key_i[s] mod q,
+ * canonical words in and out, the sum exact in 128 bits and reduced once.  d_ahat and d_keyhat are HOST arrays of k device pointers,
+ * 1 <= k <= 32, as for ntt_rns_inv_dot_batch; every operand is in the call's layout, except that with NTT_GALOIS_KEY_BROADCAST
+ * every key_i^ is ONE polynomial per limb ([limb][N]) shared by the batch, as for NTT_MUL_B_BROADCAST.  The dot is always in the NTT
+ * domain: NTT_GALOIS_TRANSFORMED is accepted there and changes nothing.
+ * All calls are OUT OF PLACE.  NTT_ERR_ARG, nothing written: g even, 0 or >= 2N; nlimbs < 1, k out of range, a null pointer; plans
+ * that differ in N or device; an unknown flag (NTT_GALOIS_ACCUMULATE or NTT_GALOIS_KEY_BROADCAST passed to galois included);
+ * strides under which two (limb, polynomial) ranges overlap; an output whose span of words under the layout (first word to last)
+ * overlaps that of an input (d_out with d_in; d_c with any a_i^ or key_i^; inputs may overlap each other).  Allocate nothing, do
+ * not synchronise the host, issue no memset: capturable. ---- */
+enum { NTT_GALOIS_TRANSFORMED = 1,   /* operands in the NTT domain (bit-reversed, as ntt_fwd_batch leaves them) */
+       NTT_GALOIS_ACCUMULATE = 2,    /* galois_dot: c^ += ... (c^ canonical on entry) */
+       NTT_GALOIS_KEY_BROADCAST = 4  /* galois_dot: every key_i^ is ONE polynomial per limb ([limb][N]) shared by the batch */ };
+NTT_API uint64_t ntt_galois_rotation(uint64_t N, int64_t steps); /* 5^steps mod 2N (negative steps: the inverse power); 0 on a bad N */
+NTT_API int ntt_galois_batch(const ntt_plan *p, uint64_t *d_out, const uint64_t *d_in, uint64_t g, uint64_t batch, unsigned flags,
+                             void *stream);
+NTT_API int ntt_rns_galois_batch(int nlimbs, ntt_plan *const *plans, uint64_t *d_out, const uint64_t *d_in, uint64_t g, uint64_t batch,
+                                 unsigned flags, void *stream);
+NTT_API int ntt_rns_galois_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_out, const uint64_t *d_in, uint64_t g,
+                                         uint64_t limb_stride, uint64_t poly_stride, uint64_t batch, unsigned flags, void *stream);
+NTT_API int ntt_rns_galois_dot_batch(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, int k, const uint64_t *const *d_ahat,
+                                     const uint64_t *const *d_keyhat, uint64_t g, uint64_t batch, unsigned flags, void *stream);
+NTT_API int ntt_rns_galois_dot_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, int k, const uint64_t *const *d_ahat,
+                                             const uint64_t *const *d_keyhat, uint64_t g, uint64_t limb_stride, uint64_t poly_stride,
+                                             uint64_t batch, unsigned flags, void *stream);
+
 /* ---- caller-native layouts (round 5).  The entry points above take RNS operands as [limb][batch][N].  SURVEY 8(d) config 5
  * -- and every FHE library -- keeps a polynomial's limbs side by side: [batch][prime][N].  The *_strided forms take the two
  * distances in WORDS instead of assuming either:

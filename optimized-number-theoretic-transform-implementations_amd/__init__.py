@@ -47,6 +47,7 @@ OPT_RESCALE_FUSED = 17
 RESCALE_TRANSFORMED, RESCALE_FLOOR = 1, 2
 MODUP_TRANSFORMED = 1
 MODDOWN_TRANSFORMED, MODDOWN_FLOOR = 1, 2
+GALOIS_TRANSFORMED, GALOIS_ACCUMULATE, GALOIS_KEY_BROADCAST = 1, 2, 4
 
 #: every symbol include/ntt_mi355x.h and the reference-named headers declare
 EXPORTED_SYMBOLS = [
@@ -60,6 +61,8 @@ EXPORTED_SYMBOLS = [
     "ntt_rns_fwd_batch_strided", "ntt_rns_inv_batch_strided", "ntt_rns_negacyclic_mul_batch_strided", "ntt_rns_inv_dot_batch_strided",
     "ntt_rns_mul_transformed_batch_strided", "ntt_rns_fwd_mul_batch_strided", "ntt_rns_rescale_batch", "ntt_rns_rescale_batch_strided",
     "ntt_rns_mod_up_batch", "ntt_rns_mod_up_batch_strided", "ntt_rns_mod_down_batch", "ntt_rns_mod_down_batch_strided",
+    "ntt_galois_rotation", "ntt_galois_batch", "ntt_rns_galois_batch", "ntt_rns_galois_batch_strided", "ntt_rns_galois_dot_batch",
+    "ntt_rns_galois_dot_batch_strided",
     "ntt_transform_batch_strided", "ntt_transform_ptrs", "ntt_rns_transform_ptrs", "ntt_transform_dev_ptrs", "ntt_rns_transform_dev_ptrs", "ntt_inv_dot_dev_ptrs", "ntt_fwd_mul_dev_ptrs", "ntt_negacyclic_mul_dev_ptrs",
     "ntt_rns_inv_dot_dev_ptrs", "ntt_rns_fwd_mul_dev_ptrs", "ntt_rns_negacyclic_mul_dev_ptrs", "ntt_dev_malloc", "ntt_dev_free", "ntt_dev_mem_info",
     "ntt_h2d", "ntt_d2h", "ntt_stream_create", "ntt_stream_destroy", "ntt_stream_sync",
@@ -142,6 +145,15 @@ _sig("ntt_rns_mod_up_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, 
 _sig("ntt_rns_mod_down_batch", C.c_int, C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_mod_down_batch_strided", C.c_int, C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint,
      VOIDP)
+_sig("ntt_galois_rotation", C.c_uint64, C.c_uint64, C.c_int64)
+_sig("ntt_galois_batch", C.c_int, VOIDP, VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_galois_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_galois_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+     C.c_uint, VOIDP)
+_sig("ntt_rns_galois_dot_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_int, C.POINTER(VOIDP), C.POINTER(VOIDP), C.c_uint64,
+     C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_galois_dot_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_int, C.POINTER(VOIDP), C.POINTER(VOIDP), C.c_uint64,
+     C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_transform_batch_strided", C.c_int, VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_transform_ptrs", C.c_int, VOIDP, C.POINTER(VOIDP), C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_transform_ptrs", C.c_int, C.c_int, C.POINTER(VOIDP), C.POINTER(VOIDP), C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
@@ -413,6 +425,10 @@ class Plan:
         """c^ = fwd(a) (.) b^ (MUL_ACCUMULATE: c^ += ...): the result stays in the NTT domain"""
         _check(_lib.ntt_fwd_mul_batch(self.h, dc, da, dbhat, batch, flags, stream))
 
+    def galois(self, dout, din, g, batch, flags=0, stream=None):
+        """out = sigma_g(in): a(X) -> a(X^g), out of place (GALOIS_TRANSFORMED: both in the NTT domain, a permutation of words)"""
+        _check(_lib.ntt_galois_batch(self.h, dout, din, g, batch, flags, stream))
+
     # host-array conveniences used by the parity tests
     def fwd_host(self, a, wide=False, lazy=False):
         a = np.ascontiguousarray(a, dtype=np.uint64)
@@ -547,6 +563,32 @@ def rns_mod_down(plans, np_, dptr, batch, flags=0, stream=None, layout=None):
     if layout:
         _check(_lib.ntt_rns_mod_down_batch_strided(nq, np_, _plan_array(plans), dptr, layout[0], layout[1], batch, flags, stream))
     else: _check(_lib.ntt_rns_mod_down_batch(nq, np_, _plan_array(plans), dptr, batch, flags, stream))
+
+
+def galois_rotation(n, steps):
+    """the Galois element 5^steps mod 2n of a rotation by `steps` slots (negative steps: the inverse power); 0 on a bad n"""
+    return int(_lib.ntt_galois_rotation(n, steps))
+
+
+def rns_galois(plans, dout, din, g, batch, flags=0, stream=None, layout=None):
+    """out = sigma_g(in): a(X) -> a(X^g) on every limb, out of place (GALOIS_TRANSFORMED: both in the NTT domain); limbs laid out
+    [limb][batch][N], layout = (limb_stride, poly_stride) in words otherwise"""
+    if layout:
+        _check(_lib.ntt_rns_galois_batch_strided(len(plans), _plan_array(plans), dout, din, g, layout[0], layout[1], batch, flags, stream))
+    else: _check(_lib.ntt_rns_galois_batch(len(plans), _plan_array(plans), dout, din, g, batch, flags, stream))
+
+
+def rns_galois_dot(plans, dc, dahats, dkeyhats, g, batch, flags=0, stream=None, layout=None):
+    """c^ = sum_i sigma_g(a_i^) (.) key_i^ in the NTT domain (GALOIS_ACCUMULATE: c^ += ...; GALOIS_KEY_BROADCAST: every key is
+    [limb][N], shared by the batch)"""
+    k = len(dahats)
+    assert k == len(dkeyhats)
+    if layout:
+        _check(_lib.ntt_rns_galois_dot_batch_strided(len(plans), _plan_array(plans), dc, k, (VOIDP * k)(*dahats), (VOIDP * k)(*dkeyhats), g,
+                                                     layout[0], layout[1], batch, flags, stream))
+    else:
+        _check(_lib.ntt_rns_galois_dot_batch(len(plans), _plan_array(plans), dc, k, (VOIDP * k)(*dahats), (VOIDP * k)(*dkeyhats), g, batch,
+                                             flags, stream))
 
 
 def batch_multi(plans, dptrs, batches, inverse=False):

@@ -31,17 +31,6 @@ struct KModDownCoef {
   uint64_t        g[kBconvLimbs][kBconvLimbs];
 };
 
-/* the grid of rescale_coef_kernel (host_products.inc grid_pw): about four iterations per workgroup */
-static unsigned coef_grid(uint64_t n, int max_grid)
-{
-  const uint64_t total = (n + 255) / 256;
-  uint64_t       g     = (total + 3) / 4;
-  if(g < 2048) g = total < 2048 ? total : 2048;
-  if(g > (1u << 22)) g = 1u << 22;
-  if(max_grid > 0) g = total < (uint64_t)max_grid ? total : (uint64_t)max_grid;
-  return (unsigned)(g ? g : 1);
-}
-
 /* One coefficient position per thread and iteration: the source words requested together, the digits z_i, then per destination
  * limb the 128-bit sum over the sources, its reduction and the store. */
 __global__ void __launch_bounds__(256) bconv_kernel(const KBconv k)

@@ -21,6 +21,7 @@
 
 #include "ntt_kernels.h"
 #include "ntt_passplan.h"
+#include "ntt_galois.h"
 #include "ntt_keyswitch.h"
 #include "ntt_rescale.h"
 #include "ntt_tables.h"
@@ -135,5 +136,6 @@ static int check_device(int device)
 #include "host/host_ntt_domain.inc"
 #include "host/host_rescale.inc"
 #include "host/host_keyswitch.inc"
+#include "host/host_galois.inc"
 #include "host/host_runtime.inc"
 #include "host/host_compat.inc"

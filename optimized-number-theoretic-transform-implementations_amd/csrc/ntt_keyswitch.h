@@ -103,6 +103,18 @@ NTT_HD uint64_t moddown_digit1(uint64_t t, const BconvSrc &s, const BconvDst &d)
   return v >= d.h ? v - d.h : v + (d.q - d.h);
 }
 
+/* the grid of the element-wise kernels over n coefficient positions (bconv_kernel, moddown_coef_kernel, the galois kernels): that of
+ * rescale_coef_kernel (host_products.inc grid_pw), about four iterations per workgroup */
+inline unsigned coef_grid(uint64_t n, int max_grid)
+{
+  const uint64_t total = (n + 255) / 256;
+  uint64_t       g     = (total + 3) / 4;
+  if(g < 2048) g = total < 2048 ? total : 2048;
+  if(g > (1u << 22)) g = 1u << 22;
+  if(max_grid > 0) g = total < (uint64_t)max_grid ? total : (uint64_t)max_grid;
+  return (unsigned)(g ? g : 1);
+}
+
 /* ModUp, coefficients: destination limb k of the launch (k0 + k of the operand's other limbs: slot k0 + k, or k0 + k + count
  * from the digit on) <- FastBConv of the count source limbs (bconv_kernel; keyswitch_coef.hip).  g[i][k] = [b^_i]_{q_k}. */
 struct BconvArgs {
