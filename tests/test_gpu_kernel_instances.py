@@ -1,6 +1,7 @@
-"""GPU: every kernel instance the recipe table covers (tests/kernel_recipes.py) launched and checked word for word against
-the oracle; a kernel trace proves that the recipes launch every instance they claim; route precedence of explicit plan
-options over the automatic one-pass choice."""
+"""GPU: every kernel instance the recipe table covers (tests/kernel_recipes.py) -- the transform families (onepass, twophase, team,
+column), the coefficient-domain product families (fused_product, fused_product_small, team_product) and the pointwise kernels --
+launched and checked word for word against the oracle; a kernel trace, one traced child per family, proves that the recipes
+launch every instance they claim; route precedence of explicit plan options over the automatic one-pass choice."""
 import csv
 import glob
 import os
@@ -57,12 +58,32 @@ def _traced(args, seconds):
     return keys
 
 
+# Limit of each family's traced child, seconds: 3 x the untraced wall time of `python3 tests/kernel_recipes.py --family NAME` on an
+# MI355X (in the comments), rounded up to a minute, at least 120 s.  A guard against a hang, not a performance claim.
+FAMILY_LIMITS = {
+    "onepass_kernel": 120,               # 1.7 s
+    "twophase_kernel": 120,              # 1.9 s
+    "team_kernel": 120,                  # 14.9 s
+    "column_kernel": 120,                # 6.0 s
+    "fused_product_kernel": 120,         # 4.3 s
+    "fused_product_small_kernel": 120,   # 3.1 s
+    "team_product_kernel": 120,          # 24.8 s
+    "pointwise_kernel": 120,             # 1.0 s
+    "pointwise_acc_kernel": 120,         # 0.8 s
+    "pointwise_ptrs_kernel": 120,        # 0.8 s
+}
+
+
 @pytest.mark.gpu
 def test_every_covered_instance_is_launched():
     """the instances the recipes claim (every shipped instance outside tests/golden/uncovered_kernel_instances.txt) - launched -
-    allowlist = {}, and no allowlisted instance is launched"""
+    allowlist = {}, and no allowlisted instance is launched.  One traced child per family, one after the other (a failing child
+    fails the test before the next one starts); the union of their traces is what is asserted."""
     inv = kernel_inventory.instances()
-    launched = _traced([], 900)
+    assert set(FAMILY_LIMITS) == set(kernel_recipes.RECIPES)
+    launched = set()
+    for family in kernel_recipes.RECIPES:
+        launched |= _traced(["--family", family], FAMILY_LIMITS[family])
     # the trace's names normalise to the inventory's: the headline kernel (the block pass behind the recipes' 1-stage column
     # passes) by name
     assert "fused_kernel<ArithF64,14,false,0,false,false,false>" in inv
