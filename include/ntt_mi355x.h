@@ -122,6 +122,12 @@ typedef enum ntt_option {
                           * kept limbs with the rescale in its prologue and epilogue where it is built (FP64 policies, N = 2^6..2^14);
                           * 0 = inverse, element-wise kernel and forward transform around every run.  Read from plans[0]; results
                           * are identical.  The same switch selects the route of ntt_rns_mod_down_batch in the NTT domain */
+  NTT_OPT_MODUP_FUSED = 18, /* ntt_rns_mod_up_mul_batch: 1 = every run of limbs the fused kernel is built for (FP64 policies,
+                          * N = 2^6..2^14) takes it: one forward-transform launch with ModUp in its prologue and the key product in
+                          * its epilogue; 0 = every run takes the composition (the base-conversion launches into the operand's other
+                          * slots, then the ntt_rns_fwd_mul_batch route); -1 (default) = the fused kernel where the recorded
+                          * measurement says it is not slower (the rule is quoted at ntt_rns_mod_up_mul_batch).  Read from plans[0];
+                          * results are identical */
   NTT_OPT_FUSED_PRODUCT = 5 /* N = 2^8..2^17, FP64: 1 (default) = ntt_negacyclic_mul_batch as ONE launch that takes both
                           * operands through the forward stages, multiplies in registers and runs the inverse: 24N bytes up to
                           * 2^14; from 2^23 coefficients per operand of N >= 2^15 on likewise one launch (all limbs of an RNS set
@@ -344,6 +350,37 @@ NTT_API int ntt_rns_mod_down_batch(int nq, int np, ntt_plan *const *plans, uint6
                                    void *stream);
 NTT_API int ntt_rns_mod_down_batch_strided(int nq, int np, ntt_plan *const *plans, uint64_t *d_a, uint64_t limb_stride,
                                            uint64_t poly_stride, uint64_t batch, unsigned flags, void *stream);
+
+/* ---- ModUp fused into the key product: one digit's term of the key-switching inner product in ONE call,
+ *     c^ (+)= fwd( ModUp(digit) ) (.) key^   for every limb of Q u P.
+ * d_ext is an operand over the extended basis as for ntt_rns_mod_up_batch: limbs [first, first + count), 1 <= count <= 16, hold the
+ * digit's COEFFICIENTS, canonical.  Its other limb slots are scratch: the caller must treat them as undefined after the call.  Where
+ * every run of limbs of the call is served by the fused kernel those slots are NOT WRITTEN AT ALL (nor read).  The digit's own limbs
+ * follow ntt_rns_fwd_mul_batch's rule for d_a: left as they were up to N = 2^14, scratch above.  d_c and d_keyhat are NTT-domain
+ * operands in the call's layout; flags are NTT_MUL_B_BROADCAST (the key is [limb][N]), NTT_MUL_ACCUMULATE and NTT_MUL_LAZY_IN (key
+ * words), with ntt_rns_fwd_mul_batch's meaning.  The result is, bit for bit, ntt_rns_mod_up_batch(..., flags = 0) on d_ext followed
+ * by ntt_rns_fwd_mul_batch(nlimbs, plans, d_c, d_ext, d_keyhat, batch, flags); outputs are canonical.
+ * Per run of compatible limbs: FP64 policies at N = 2^6..2^14 -- one launch of the forward block kernel with the integer base
+ * conversion in its prologue and the product in its epilogue (the extended digit never exists in memory: 8N count bytes of the
+ * digit, 8N of the key, 8N or 16N of c^ per limb-polynomial); anything else (integer policies, N < 2^6, N >= 2^15) -- the
+ * composition: the base-conversion launches into d_ext's slots of the run, then the ntt_rns_fwd_mul_batch route.  NTT_OPT_MODUP_FUSED
+ * on plans[0]: 1 / 0 force the fused kernel (where built) / the composition for every run; the default, -1, takes the fused kernel
+ * where the measurement recorded in profiles/r10/modup_mul_bench.txt says it is not slower than the two calls:
+ *     fused for count == 1, the composition for count >= 2.
+ * (Call rate of the fused route over ntt_rns_mod_up_batch + ntt_rns_fwd_mul_batch of the parent commit, 24 50-bit limbs, broadcast
+ * key, accumulating, 2^14 x 2 / 64 / 1024 polynomials: count 1: 1.22-1.33 / 1.86-1.96 / 1.47-1.49; count 2: 0.70-0.74 / 1.10-1.13 /
+ * 0.85-0.86; count 3: 0.59-0.64 / 0.96-0.99 / 0.73-0.74; count 8: 0.35-0.54 throughout.  The largest count not slower at both 64 and
+ * 1024 polynomials is 1, and the 2-polynomial rows show no gain beyond it, so small calls get no rule of their own.)
+ * NTT_ERR_ARG, nothing written: everything ntt_rns_mod_up_batch and ntt_rns_fwd_mul_batch refuse (the digit out of range, plans that
+ * differ in N or device, a prime that appears twice, an unknown flag, a null pointer, overlapping strides, a plan without its
+ * forward table), and d_c's span of words under the layout (first word to last) overlapping d_ext's: every limb's workgroups read
+ * the digit while others write c^.  d_c against d_keyhat follows ntt_rns_fwd_mul_batch (c^ may alias key^).  Allocates nothing,
+ * does not synchronise the host, issues no memset: capturable. ---- */
+NTT_API int ntt_rns_mod_up_mul_batch(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, uint64_t *d_ext, int first, int count,
+                                     const uint64_t *d_keyhat, uint64_t batch, unsigned flags, void *stream);
+NTT_API int ntt_rns_mod_up_mul_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, uint64_t *d_ext, int first, int count,
+                                             const uint64_t *d_keyhat, uint64_t limb_stride, uint64_t poly_stride, uint64_t batch,
+                                             unsigned flags, void *stream);
 
 /* ---- Galois automorphisms (rotation, conjugation) and the rotation key product.  For odd g, 0 < g < 2N,
  *     sigma_g(a)(X) = a(X^g)  in Z_q[X] / (X^N + 1).

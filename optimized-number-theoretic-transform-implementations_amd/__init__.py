@@ -44,6 +44,7 @@ OPT_MAX_GRID, OPT_CHUNK_MIB, OPT_F64_CLASS, OPT_TWO_PHASE, OPT_FUSED_PRODUCT, OP
 OPT_XCD_LOCAL, OPT_XCD_LOCAL_LAG, OPT_XCD_LOCAL_WGS_PER_CU, OPT_INT_WIDE, OPT_BLOCK_OVERSUB = 7, 8, 9, 10, 11
 OPT_RNS_LAUNCH, OPT_DOT_FUSED, OPT_MAX_BATCH_HINT, OPT_CTL_ALLOCATIONS, OPT_ONE_PASS = 12, 13, 14, 15, 16
 OPT_RESCALE_FUSED = 17
+OPT_MODUP_FUSED = 18
 RESCALE_TRANSFORMED, RESCALE_FLOOR = 1, 2
 MODUP_TRANSFORMED = 1
 MODDOWN_TRANSFORMED, MODDOWN_FLOOR = 1, 2
@@ -61,6 +62,7 @@ EXPORTED_SYMBOLS = [
     "ntt_rns_fwd_batch_strided", "ntt_rns_inv_batch_strided", "ntt_rns_negacyclic_mul_batch_strided", "ntt_rns_inv_dot_batch_strided",
     "ntt_rns_mul_transformed_batch_strided", "ntt_rns_fwd_mul_batch_strided", "ntt_rns_rescale_batch", "ntt_rns_rescale_batch_strided",
     "ntt_rns_mod_up_batch", "ntt_rns_mod_up_batch_strided", "ntt_rns_mod_down_batch", "ntt_rns_mod_down_batch_strided",
+    "ntt_rns_mod_up_mul_batch", "ntt_rns_mod_up_mul_batch_strided",
     "ntt_galois_rotation", "ntt_galois_batch", "ntt_rns_galois_batch", "ntt_rns_galois_batch_strided", "ntt_rns_galois_dot_batch",
     "ntt_rns_galois_dot_batch_strided",
     "ntt_transform_batch_strided", "ntt_transform_ptrs", "ntt_rns_transform_ptrs", "ntt_transform_dev_ptrs", "ntt_rns_transform_dev_ptrs", "ntt_inv_dot_dev_ptrs", "ntt_fwd_mul_dev_ptrs", "ntt_negacyclic_mul_dev_ptrs",
@@ -145,6 +147,9 @@ _sig("ntt_rns_mod_up_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, 
 _sig("ntt_rns_mod_down_batch", C.c_int, C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_mod_down_batch_strided", C.c_int, C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint,
      VOIDP)
+_sig("ntt_rns_mod_up_mul_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_int, C.c_int, VOIDP, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_mod_up_mul_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_int, C.c_int, VOIDP, C.c_uint64, C.c_uint64,
+     C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_galois_rotation", C.c_uint64, C.c_uint64, C.c_int64)
 _sig("ntt_galois_batch", C.c_int, VOIDP, VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_galois_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
@@ -554,6 +559,17 @@ def rns_mod_up(plans, dptr, first, count, batch, flags=0, stream=None, layout=No
         _check(_lib.ntt_rns_mod_up_batch_strided(len(plans), _plan_array(plans), dptr, first, count, layout[0], layout[1], batch, flags,
                                                  stream))
     else: _check(_lib.ntt_rns_mod_up_batch(len(plans), _plan_array(plans), dptr, first, count, batch, flags, stream))
+
+
+def rns_mod_up_mul(plans, dc, dext, first, count, dkeyhat, batch, flags=0, stream=None, layout=None):
+    """c^ (+)= fwd(ModUp(digit)) (.) key^ on every limb: one digit's term of the key-switching inner product.  dext holds the digit's
+    coefficients in limbs [first, first + count), its other slots are scratch (untouched where the fused kernel serves every run:
+    OPT_MODUP_FUSED on plans[0]); flags: MUL_B_BROADCAST (the key is [limb][N]), MUL_ACCUMULATE, MUL_LAZY_IN (key words); limbs laid
+    out [limb][batch][N], layout = (limb_stride, poly_stride) in words otherwise"""
+    if layout:
+        _check(_lib.ntt_rns_mod_up_mul_batch_strided(len(plans), _plan_array(plans), dc, dext, first, count, dkeyhat, layout[0], layout[1],
+                                                     batch, flags, stream))
+    else: _check(_lib.ntt_rns_mod_up_mul_batch(len(plans), _plan_array(plans), dc, dext, first, count, dkeyhat, batch, flags, stream))
 
 
 def rns_mod_down(plans, np_, dptr, batch, flags=0, stream=None, layout=None):

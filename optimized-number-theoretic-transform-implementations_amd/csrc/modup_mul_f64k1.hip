@@ -1,0 +1,6 @@
+/* modup_mul_f64k1.hip -- instantiates the ModUp-times-key kernels (modup_mul_kernel, N = 2^6..2^14) for (ArithF64, headroom class 1). */
+#include "ntt_kernels_modup_mul.h"
+
+namespace ntt {
+NTT_DEFINE_LAUNCH_MODUP_MUL(ArithF64, 1)
+} /* namespace ntt */

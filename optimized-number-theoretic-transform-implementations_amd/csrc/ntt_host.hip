@@ -137,5 +137,6 @@ static int check_device(int device)
 #include "host/host_rescale.inc"
 #include "host/host_keyswitch.inc"
 #include "host/host_galois.inc"
+#include "host/host_modup_mul.inc"
 #include "host/host_runtime.inc"
 #include "host/host_compat.inc"

@@ -169,4 +169,30 @@ template <> hipError_t launch_moddown_fwd<ArithF64, 1>(const ModDownFwdArgs &);
 template <> hipError_t launch_moddown_fwd<ArithF64, 18>(const ModDownFwdArgs &);
 template <> hipError_t launch_moddown_fwd<ArithF64W, 0>(const ModDownFwdArgs &);
 
+/* ModUp fused into the key product, FP64 policies, N = 2^6..2^14: c_l^ (+)= fwd(FastBConv_{digit->q_l}) (.) key_l^ in ONE launch over a
+ * run of limbs of the extended basis (modup_mul_kernel; modup_mul_f64*.hip); a digit limb inside the run is transformed as it stands.
+ * The extended digit is never written.  [b^_i]_{q_l} is formed by each workgroup, as in moddown_fwd_kernel. */
+struct ModUpMulArgs {
+  uint64_t *      a;      /* the run's first limb of the extended operand (read only: the digit's own limbs)  */
+  const uint64_t *dig;    /* the digit's first limb, coefficients                                             */
+  const uint64_t *b;      /* key^, the run's first limb                                                       */
+  uint64_t *      out;    /* c^, the run's first limb                                                         */
+  const void *    limbs;  /* HOST array of the run's LimbRec<A>                                               */
+  int             nlimbs; /* 1 .. kBconvLimbs                                                                 */
+  int             count;  /* 1 .. kBconvLimbs                                                                 */
+  uint32_t        own;    /* bit l: limb l of the run belongs to the digit                                    */
+  uint64_t        limb_stride, poly_stride, b_limb_stride, batch;
+  uint32_t        logn;
+  bool            lazy_in, b_bcast, accumulate;
+  BconvSrc        sl[kBconvLimbs];
+  BconvDst        dl[kBconvLimbs];
+  int             max_grid, num_cus;
+  hipStream_t     stream;
+};
+template <class A, int KSH> hipError_t launch_modup_mul(const ModUpMulArgs &ma);
+template <> hipError_t launch_modup_mul<ArithF64, 0>(const ModUpMulArgs &);
+template <> hipError_t launch_modup_mul<ArithF64, 1>(const ModUpMulArgs &);
+template <> hipError_t launch_modup_mul<ArithF64, 18>(const ModUpMulArgs &);
+template <> hipError_t launch_modup_mul<ArithF64W, 0>(const ModUpMulArgs &);
+
 } // namespace ntt

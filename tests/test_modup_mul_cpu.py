@@ -1,0 +1,109 @@
+"""CPU: ntt_rns_mod_up_mul_batch without a GPU -- the model of tests/modup_mul_model.py against the definition over the CRT (lift the
+digit to x in [0, B), extend as x + u B with 0 <= u < count, reduce mod every prime, forward transform, times the key, plus the
+accumulator) on the chains of test_keyswitch_cpu.UP_CHAINS; the exported symbols; the plain-C example against the public header
+alone; and the kernels of the new translation units (modup_mul_*.o): exactly the 36 expected instances, none spilling vector
+registers or using scratch."""
+import glob
+import os
+import random
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import keyswitch_model as km
+import modup_mul_model as mm
+import test_keyswitch_cpu as tkc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_amd", "csrc")
+LIB = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_amd", "libntt_mi355x.so")
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+N = 64
+
+
+@pytest.mark.parametrize("bits,first,count", tkc.UP_CHAINS, ids=["start", "middle", "end", "one-limb", "count16"])
+@pytest.mark.parametrize("flags", [0, mm.ACCUMULATE, mm.BROADCAST, mm.BROADCAST | mm.ACCUMULATE | mm.LAZY_IN])
+def test_model_equals_the_definition(oracle, bits, first, count, flags):
+    batch = 2
+    primes, roots = tkc._chain(oracle, N, bits)
+    basis = primes[first:first + count]
+    B = km.prod(basis)
+    rng = random.Random(len(bits) * 37 + first + flags)
+    xs = [0, B - 1, 1, B // 2] + [rng.randrange(B) for _ in range(batch * N - 4)]
+    digit = [np.array([x % b for x in xs], dtype=np.uint64) for b in basis]
+    _, key, acc = mm.operands(oracle, primes, N, batch, first, count, flags, seed=5)
+    got, ext = mm.model(oracle, primes, roots, digit, key, acc, N, batch, first, count, flags)
+    sums = km.fastbconv_int(basis, digit)
+    us = []
+    for s, x in zip(sums, xs):
+        assert (s - x) % B == 0
+        us.append((s - x) // B)
+        assert 0 <= us[-1] < count, "u = %d outside [0, %d)" % (us[-1], count)
+    for l, (q, w) in enumerate(zip(primes, roots)):
+        lifted = np.array([(x + u * B) % q for x, u in zip(xs, us)], dtype=np.uint64)
+        if first <= l < first + count:
+            assert np.array_equal(lifted, digit[l - first]), "x + u B reduces to the digit's own limb"
+        assert np.array_equal(ext[l], lifted), "ModUp limb %d" % l
+        kq = [int(v) % q for v in key[l]]
+        f = oracle.ctx(N, q, w).fwd(lifted)
+        want = [(int(f[i]) * kq[i % N if flags & mm.BROADCAST else i] + (int(acc[l][i]) if flags & mm.ACCUMULATE else 0)) % q
+                for i in range(batch * N)]
+        assert got[l].tolist() == want, "limb %d" % l
+
+
+def test_digit_of_largest_words_is_the_largest_sum(oracle):
+    """every digit word b_i - 1: z_i = [(b_i - 1) b^_i^-1]_{b_i}; the model still agrees with the integers"""
+    bits, first, count = [50] * 18, 1, 16
+    primes, roots = tkc._chain(oracle, N, bits)
+    digit, key, acc = mm.operands(oracle, primes, N, 1, first, count, 0, seed=3, digit_max=True)
+    basis = primes[first:first + count]
+    assert all(int(d[0]) == b - 1 and int(d[-1]) == b - 1 for d, b in zip(digit, basis))
+    got, ext = mm.model(oracle, primes, roots, digit, key, acc, N, 1, first, count, 0)
+    s = km.fastbconv_int(basis, digit)[0]
+    for l in (0, 17):
+        assert set(ext[l].tolist()) == {s % primes[l]}
+
+
+def test_exports_the_two_symbols(lib):
+    out = subprocess.check_output(["nm", "-D", "--defined-only", lib.LIB_PATH], text=True)
+    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert {"ntt_rns_mod_up_mul_batch", "ntt_rns_mod_up_mul_batch_strided"} <= names
+    assert lib.OPT_MODUP_FUSED == 18
+
+
+def test_fused_example_builds_against_the_public_header(lib):
+    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
+    exe = os.path.join(ROOT, "build", "rns_key_switch_fused")
+    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "examples", "rns_key_switch_fused.c"), "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x",
+                           "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
+    assert os.path.exists(exe)
+
+
+def expected_instances():
+    return {"modup_mul_kernel<%s,%d,%d>" % (pol, logn, k) for pol, k, logn in mm.launch_cases()}
+
+
+def modup_mul_kernels():
+    """{normalised name: metadata} of every kernel in the new translation units (or, where the objects are not at hand, the
+    modup_mul kernels of the linked library)"""
+    import check_spills
+    import kernel_inventory
+    objs = sorted(glob.glob(os.path.join(CSRC, "modup_mul_*.o")))
+    ks = [k for o in objs for k in check_spills.kernels_of(o)] if objs else \
+        [k for k in check_spills.kernels_of(LIB) if "modup_mul" in k["name"]]
+    names = [k["name"] for k in ks]
+    return {kernel_inventory.normalise(d): k for d, k in zip(kernel_inventory.demangle(names), ks)}
+
+
+def test_modup_mul_objects_hold_exactly_the_expected_instances_without_spills():
+    ks = modup_mul_kernels()
+    want = expected_instances()
+    assert len(want) == 36
+    assert set(ks) == want, ("missing %s, unexpected %s" % (sorted(want - set(ks))[:8], sorted(set(ks) - want)[:8]))
+    bad = {n: (k.get("vgpr_spill_count"), k.get("private_segment_fixed_size"), k.get("group_segment_fixed_size"))
+           for n, k in ks.items()
+           if k.get("vgpr_spill_count", 0) or k.get("private_segment_fixed_size", 0) or k.get("group_segment_fixed_size", 0) > 160 * 1024}
+    assert not bad, "spills / scratch / LDS: %s" % bad
