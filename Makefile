@@ -20,7 +20,8 @@ OBJS     = $(CSRC)/inst_f64k0.o $(CSRC)/inst_f64k1.o $(CSRC)/inst_f64k18.o $(CSR
            $(CSRC)/rescale_f64k0.o $(CSRC)/rescale_f64k1.o $(CSRC)/rescale_f64k18.o $(CSRC)/rescale_f64w.o $(CSRC)/rescale_coef.o \
            $(CSRC)/keyswitch_f64k0.o $(CSRC)/keyswitch_f64k1.o $(CSRC)/keyswitch_f64k18.o $(CSRC)/keyswitch_f64w.o $(CSRC)/keyswitch_coef.o \
            $(CSRC)/modup_mul_f64k0.o $(CSRC)/modup_mul_f64k1.o $(CSRC)/modup_mul_f64k18.o $(CSRC)/modup_mul_f64w.o \
-           $(CSRC)/galois_coef.o \
+           $(CSRC)/modup_mul2_f64k0.o $(CSRC)/modup_mul2_f64k1.o $(CSRC)/modup_mul2_f64k18.o $(CSRC)/modup_mul2_f64w.o \
+           $(CSRC)/galois_coef.o $(CSRC)/keypair_dot2.o \
            $(CSRC)/ntt_host.o
 # the kernel translation units see the kernel headers only; the host layer also the public headers
 KHDRS    = $(wildcard $(CSRC)/*.h)

@@ -128,6 +128,12 @@ typedef enum ntt_option {
                           * slots, then the ntt_rns_fwd_mul_batch route); -1 (default) = the fused kernel where the recorded
                           * measurement says it is not slower (the rule is quoted at ntt_rns_mod_up_mul_batch).  Read from plans[0];
                           * results are identical */
+  NTT_OPT_PAIR_FUSED = 19, /* ntt_rns_fwd_mul_pair_batch, ntt_rns_mod_up_mul_pair_batch: 1 = every run of limbs the fused pair kernel is built
+                          * for (FP64 policies, N = 2^6..2^14) takes it: one forward-transform launch whose epilogue multiplies by both
+                          * key components; 0 = every run takes the composition (base-conversion launches, ONE forward transform in
+                          * place, one two-output element-wise product); -1 (default) = the fused kernel where the recorded
+                          * measurement says it is not slower (the rule is quoted at ntt_rns_mod_up_mul_pair_batch).  Read from
+                          * plans[0]; results are identical */
   NTT_OPT_FUSED_PRODUCT = 5 /* N = 2^8..2^17, FP64: 1 (default) = ntt_negacyclic_mul_batch as ONE launch that takes both
                           * operands through the forward stages, multiplies in registers and runs the inverse: 24N bytes up to
                           * 2^14; from 2^23 coefficients per operand of N >= 2^15 on likewise one launch (all limbs of an RNS set
@@ -382,6 +388,45 @@ NTT_API int ntt_rns_mod_up_mul_batch_strided(int nlimbs, ntt_plan *const *plans,
                                              const uint64_t *d_keyhat, uint64_t limb_stride, uint64_t poly_stride, uint64_t batch,
                                              unsigned flags, void *stream);
 
+/* ---- The key products for BOTH components of a key-switching key.  A key-switching key is a pair (key0_j, key1_j) per digit and the
+ * result of a key switch a pair (c0, c1); the expensive operand -- the extended, forward-transformed digit -- is the same for both:
+ *     c0^ (+)= fwd(x) (.) key0^,   c1^ (+)= fwd(x) (.) key1^,
+ * x = d_a as it stands (ntt_rns_fwd_mul_pair_batch) or ModUp of the digit in d_ext (ntt_rns_mod_up_mul_pair_batch); x is read,
+ * converted and transformed ONCE.  c0^ and c1^ are, bit for bit, what ntt_rns_fwd_mul_batch / ntt_rns_mod_up_mul_batch give with
+ * (d_c0, key0) and with (d_c1, key1) on copies of the operand; flags (NTT_MUL_B_BROADCAST, NTT_MUL_ACCUMULATE, NTT_MUL_LAZY_IN: one
+ * word for both components), layouts, limits (count <= 16) and canonical outputs are those of the single calls.
+ * d_a, and the slots of d_ext outside the digit, are scratch after the call.  Where the fused pair kernel serves every run of the call
+ * they are neither read nor written, and d_a / the digit's limbs are left as they were.
+ * Per run of compatible limbs: FP64 policies at N = 2^6..2^14 -- one launch of the forward block kernel (the base conversion in its
+ * prologue) whose epilogue runs once per component: 8N count + 16N (keys) + 16N or 32N (c0^, c1^) bytes per limb-polynomial, one set
+ * of forward stages; anything else (integer policies, N < 2^6, N >= 2^15) -- the composition: the base-conversion launches into
+ * d_ext's slots of the run, ONE forward transform of the run in place, one element-wise launch per 16 limbs that forms both
+ * products.  NTT_OPT_PAIR_FUSED on plans[0]: 1 / 0 force the fused kernel (where built) / the composition for every run; the
+ * default, -1, applies the rule recorded in profiles/r11/key_pair_bench.txt:
+ *     fused for ntt_rns_fwd_mul_pair_batch and for count <= 2, the composition for count >= 3.
+ * (Call rate over the better of the parent commit's two compositions -- the single call twice; ModUp + forward transform + two
+ * element-wise accumulates --, 24 50-bit limbs, broadcast keys, accumulating, 2^14 x 64 / 1024 polynomials, ranges over eight rounds,
+ * the parent's own spread 1.01-1.03.  Fused: no conversion 1.26-1.38 / 1.29-1.38; count 1: 1.21-1.31 / 1.21-1.32; count 2: 1.15-1.23 /
+ * 1.11-1.16; count 3: 1.04-1.11 / 0.99-1.03; count 4: 0.95-1.00 / 0.90-0.92; count 8: 0.66-0.68 / 0.62-0.63.  Composition: 1.01-1.14 /
+ * 1.05-1.09 for count 2..8, 0.82-0.87 / 0.80-0.83 for count 1.  The largest count at which the fused kernel is not slower at both is
+ * 2; at count 3 it is inside the spread at 1024 polynomials and the composition is ahead.  At 2 polynomials, launch-bound, the fused
+ * kernel reads 1.27-1.31 for count 1 and 0.78-0.83 for count 2, where the composition reads 1.06-1.13: the default loses there.)
+ * NTT_ERR_ARG, nothing written: everything the single call refuses; a null pointer; c0^'s span of words under the layout (first word
+ * to last) overlapping c1^'s; either output's span overlapping d_a / d_ext; either output's span overlapping the OTHER component's
+ * key.  c_j^ against its own key_j^ follows ntt_rns_fwd_mul_batch.  Allocate nothing, do not synchronise the host, issue no memset:
+ * capturable.  The pair form of the rotation key product is ntt_rns_galois_dot_pair_batch below. ---- */
+NTT_API int ntt_rns_fwd_mul_pair_batch(int nlimbs, ntt_plan *const *plans, uint64_t *d_c0, uint64_t *d_c1, uint64_t *d_a,
+                                       const uint64_t *d_b0hat, const uint64_t *d_b1hat, uint64_t batch, unsigned flags, void *stream);
+NTT_API int ntt_rns_fwd_mul_pair_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_c0, uint64_t *d_c1, uint64_t *d_a,
+                                               const uint64_t *d_b0hat, const uint64_t *d_b1hat, uint64_t limb_stride,
+                                               uint64_t poly_stride, uint64_t batch, unsigned flags, void *stream);
+NTT_API int ntt_rns_mod_up_mul_pair_batch(int nlimbs, ntt_plan *const *plans, uint64_t *d_c0, uint64_t *d_c1, uint64_t *d_ext, int first,
+                                          int count, const uint64_t *d_key0hat, const uint64_t *d_key1hat, uint64_t batch, unsigned flags,
+                                          void *stream);
+NTT_API int ntt_rns_mod_up_mul_pair_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_c0, uint64_t *d_c1, uint64_t *d_ext,
+                                                  int first, int count, const uint64_t *d_key0hat, const uint64_t *d_key1hat,
+                                                  uint64_t limb_stride, uint64_t poly_stride, uint64_t batch, unsigned flags, void *stream);
+
 /* ---- Galois automorphisms (rotation, conjugation) and the rotation key product.  For odd g, 0 < g < 2N,
  *     sigma_g(a)(X) = a(X^g)  in Z_q[X] / (X^N + 1).
  * g = 5^steps mod 2N rotates the CKKS / BGV slots by `steps` (ntt_galois_rotation; negative steps: the inverse power),
@@ -423,6 +468,22 @@ NTT_API int ntt_rns_galois_dot_batch(int nlimbs, ntt_plan *const *plans, uint64_
 NTT_API int ntt_rns_galois_dot_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, int k, const uint64_t *const *d_ahat,
                                              const uint64_t *const *d_keyhat, uint64_t g, uint64_t limb_stride, uint64_t poly_stride,
                                              uint64_t batch, unsigned flags, void *stream);
+
+/* the rotation key product for both components of the rotation key: c_j^ (+)= sum_{i<k} sigma_g(a_i^) (.) key_j,i^, j = 0, 1, bit for bit
+ * two ntt_rns_galois_dot_batch calls; every permuted digit word is loaded once and enters two 128-bit sums (8N(k + 4) bytes per
+ * limb-polynomial accumulating with broadcast keys, against 2 * 8N(k + 2)).  One launch per 16 limbs, every policy.  Refused as
+ * ntt_rns_galois_dot_batch refuses, and: a null pointer among the new arguments, d_c0's span overlapping d_c1's, either output
+ * overlapping any a_i^ or any key of either component.
+ * Measured (profiles/r11/key_pair_bench.txt, 24 50-bit limbs, broadcast keys, accumulating, 2^14 x 64 / 1024 polynomials): k = 3:
+ * 1.23-1.31 / 1.28-1.37 x the call rate of two ntt_rns_galois_dot_batch calls of the parent commit, k = 8: 1.43-1.54 / 1.44-1.55 x;
+ * the call takes 4.4-4.5 (k = 3) and 8.2-8.5 (k = 8) times ntt_copy_probe of one operand. */
+NTT_API int ntt_rns_galois_dot_pair_batch(int nlimbs, ntt_plan *const *plans, uint64_t *d_c0, uint64_t *d_c1, int k,
+                                          const uint64_t *const *d_ahat, const uint64_t *const *d_key0hat, const uint64_t *const *d_key1hat,
+                                          uint64_t g, uint64_t batch, unsigned flags, void *stream);
+NTT_API int ntt_rns_galois_dot_pair_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_c0, uint64_t *d_c1, int k,
+                                                  const uint64_t *const *d_ahat, const uint64_t *const *d_key0hat,
+                                                  const uint64_t *const *d_key1hat, uint64_t g, uint64_t limb_stride, uint64_t poly_stride,
+                                                  uint64_t batch, unsigned flags, void *stream);
 
 /* ---- caller-native layouts (round 5).  The entry points above take RNS operands as [limb][batch][N].  SURVEY 8(d) config 5
  * -- and every FHE library -- keeps a polynomial's limbs side by side: [batch][prime][N].  The *_strided forms take the two

@@ -45,6 +45,7 @@ OPT_XCD_LOCAL, OPT_XCD_LOCAL_LAG, OPT_XCD_LOCAL_WGS_PER_CU, OPT_INT_WIDE, OPT_BL
 OPT_RNS_LAUNCH, OPT_DOT_FUSED, OPT_MAX_BATCH_HINT, OPT_CTL_ALLOCATIONS, OPT_ONE_PASS = 12, 13, 14, 15, 16
 OPT_RESCALE_FUSED = 17
 OPT_MODUP_FUSED = 18
+OPT_PAIR_FUSED = 19
 RESCALE_TRANSFORMED, RESCALE_FLOOR = 1, 2
 MODUP_TRANSFORMED = 1
 MODDOWN_TRANSFORMED, MODDOWN_FLOOR = 1, 2
@@ -63,6 +64,8 @@ EXPORTED_SYMBOLS = [
     "ntt_rns_mul_transformed_batch_strided", "ntt_rns_fwd_mul_batch_strided", "ntt_rns_rescale_batch", "ntt_rns_rescale_batch_strided",
     "ntt_rns_mod_up_batch", "ntt_rns_mod_up_batch_strided", "ntt_rns_mod_down_batch", "ntt_rns_mod_down_batch_strided",
     "ntt_rns_mod_up_mul_batch", "ntt_rns_mod_up_mul_batch_strided",
+    "ntt_rns_fwd_mul_pair_batch", "ntt_rns_fwd_mul_pair_batch_strided", "ntt_rns_mod_up_mul_pair_batch", "ntt_rns_mod_up_mul_pair_batch_strided",
+    "ntt_rns_galois_dot_pair_batch", "ntt_rns_galois_dot_pair_batch_strided",
     "ntt_galois_rotation", "ntt_galois_batch", "ntt_rns_galois_batch", "ntt_rns_galois_batch_strided", "ntt_rns_galois_dot_batch",
     "ntt_rns_galois_dot_batch_strided",
     "ntt_transform_batch_strided", "ntt_transform_ptrs", "ntt_rns_transform_ptrs", "ntt_transform_dev_ptrs", "ntt_rns_transform_dev_ptrs", "ntt_inv_dot_dev_ptrs", "ntt_fwd_mul_dev_ptrs", "ntt_negacyclic_mul_dev_ptrs",
@@ -150,6 +153,17 @@ _sig("ntt_rns_mod_down_batch_strided", C.c_int, C.c_int, C.c_int, C.POINTER(VOID
 _sig("ntt_rns_mod_up_mul_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_int, C.c_int, VOIDP, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_mod_up_mul_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_int, C.c_int, VOIDP, C.c_uint64, C.c_uint64,
      C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_fwd_mul_pair_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, VOIDP, VOIDP, VOIDP, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_fwd_mul_pair_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, VOIDP, VOIDP, VOIDP, C.c_uint64, C.c_uint64,
+     C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_mod_up_mul_pair_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, VOIDP, C.c_int, C.c_int, VOIDP, VOIDP, C.c_uint64,
+     C.c_uint, VOIDP)
+_sig("ntt_rns_mod_up_mul_pair_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, VOIDP, C.c_int, C.c_int, VOIDP, VOIDP,
+     C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_galois_dot_pair_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_int, C.POINTER(VOIDP), C.POINTER(VOIDP),
+     C.POINTER(VOIDP), C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_galois_dot_pair_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_int, C.POINTER(VOIDP), C.POINTER(VOIDP),
+     C.POINTER(VOIDP), C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_galois_rotation", C.c_uint64, C.c_uint64, C.c_int64)
 _sig("ntt_galois_batch", C.c_int, VOIDP, VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_galois_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
@@ -572,6 +586,29 @@ def rns_mod_up_mul(plans, dc, dext, first, count, dkeyhat, batch, flags=0, strea
     else: _check(_lib.ntt_rns_mod_up_mul_batch(len(plans), _plan_array(plans), dc, dext, first, count, dkeyhat, batch, flags, stream))
 
 
+def rns_fwd_mul_pair(plans, dc0, dc1, da, db0hat, db1hat, batch, flags=0, stream=None, layout=None):
+    """c0^ (+)= fwd(a) (.) b0^ and c1^ (+)= fwd(a) (.) b1^ on every limb from ONE forward transform of a (a is scratch; untouched where
+    the fused pair kernel serves every run: OPT_PAIR_FUSED on plans[0]); flags as rns_fwd_mul, one word for both components; limbs laid
+    out [limb][batch][N], layout = (limb_stride, poly_stride) in words otherwise"""
+    if layout:
+        _check(_lib.ntt_rns_fwd_mul_pair_batch_strided(len(plans), _plan_array(plans), dc0, dc1, da, db0hat, db1hat, layout[0], layout[1],
+                                                       batch, flags, stream))
+    else: _check(_lib.ntt_rns_fwd_mul_pair_batch(len(plans), _plan_array(plans), dc0, dc1, da, db0hat, db1hat, batch, flags, stream))
+
+
+def rns_mod_up_mul_pair(plans, dc0, dc1, dext, first, count, dkey0hat, dkey1hat, batch, flags=0, stream=None, layout=None):
+    """c0^ (+)= fwd(ModUp(digit)) (.) key0^ and c1^ (+)= fwd(ModUp(digit)) (.) key1^ on every limb: one digit's term of both components
+    of a key switch, the digit converted and transformed once.  dext as for rns_mod_up_mul (its other slots are scratch; untouched
+    where the fused pair kernel serves every run: OPT_PAIR_FUSED on plans[0]); flags: MUL_B_BROADCAST, MUL_ACCUMULATE, MUL_LAZY_IN,
+    one word for both components; limbs laid out [limb][batch][N], layout = (limb_stride, poly_stride) in words otherwise"""
+    if layout:
+        _check(_lib.ntt_rns_mod_up_mul_pair_batch_strided(len(plans), _plan_array(plans), dc0, dc1, dext, first, count, dkey0hat, dkey1hat,
+                                                          layout[0], layout[1], batch, flags, stream))
+    else:
+        _check(_lib.ntt_rns_mod_up_mul_pair_batch(len(plans), _plan_array(plans), dc0, dc1, dext, first, count, dkey0hat, dkey1hat, batch,
+                                                  flags, stream))
+
+
 def rns_mod_down(plans, np_, dptr, batch, flags=0, stream=None, layout=None):
     """ModDown in place: the last np_ plans are P; the Q limbs become round(x / P) - v (MODDOWN_FLOOR: floor), in the NTT domain with
     MODDOWN_TRANSFORMED; limbs laid out [limb][batch][N], layout = (limb_stride, poly_stride) in words otherwise"""
@@ -605,6 +642,20 @@ def rns_galois_dot(plans, dc, dahats, dkeyhats, g, batch, flags=0, stream=None, 
     else:
         _check(_lib.ntt_rns_galois_dot_batch(len(plans), _plan_array(plans), dc, k, (VOIDP * k)(*dahats), (VOIDP * k)(*dkeyhats), g, batch,
                                              flags, stream))
+
+
+def rns_galois_dot_pair(plans, dc0, dc1, dahats, dkey0hats, dkey1hats, g, batch, flags=0, stream=None, layout=None):
+    """c_j^ = sum_i sigma_g(a_i^) (.) key_j,i^ for both components j of the rotation key in one launch per 16 limbs, every permuted
+    digit read once (flags as rns_galois_dot, one word for both components)"""
+    k = len(dahats)
+    assert k == len(dkey0hats) == len(dkey1hats)
+    arrs = ((VOIDP * k)(*dahats), (VOIDP * k)(*dkey0hats), (VOIDP * k)(*dkey1hats))
+    if layout:
+        _check(_lib.ntt_rns_galois_dot_pair_batch_strided(len(plans), _plan_array(plans), dc0, dc1, k, arrs[0], arrs[1], arrs[2], g,
+                                                          layout[0], layout[1], batch, flags, stream))
+    else:
+        _check(_lib.ntt_rns_galois_dot_pair_batch(len(plans), _plan_array(plans), dc0, dc1, k, arrs[0], arrs[1], arrs[2], g, batch, flags,
+                                                  stream))
 
 
 def batch_multi(plans, dptrs, batches, inverse=False):

@@ -1,12 +1,13 @@
 /* host/host_galois.inc -- the Galois automorphisms sigma_g: a(X) -> a(X^g) and the rotation key product: ntt_galois_rotation,
- * ntt_galois_batch, ntt_rns_galois_batch, ntt_rns_galois_dot_batch and the strided forms.  A section of ntt_host.hip (one translation
- * unit, included from there in order); not compiled by itself.  The kernels are in galois_coef.hip; this section sees their launchers
+ * ntt_galois_batch, ntt_rns_galois_batch, ntt_rns_galois_dot_batch, ntt_rns_galois_dot_pair_batch and the strided forms.  A section of ntt_host.hip (one translation
+ * unit, included from there in order); not compiled by itself.  The kernels are in galois_coef.hip and keypair_dot2.hip; this section sees their launchers
  * and the index functions only (ntt_galois.h).
  *
  *   galois       out of place; NTT domain -- galois_ntt_kernel, a permutation of words (lazy words pass through); coefficients --
  *                galois_coef_kernel (canonical words).  One launch per 16 limbs.
  *   galois_dot   c^ (+)= sum_i sigma_g(a_i^) (.) key_i^ in the NTT domain -- galois_dot_kernel, one launch per 16 limbs: the hoisted
- *                digits are permuted on their way into the product, never materialised.
+ *                digits are permuted on their way into the product, never materialised.  The pair form (both components of the
+ *                rotation key) -- keypair_dot2_kernel, likewise: each permuted digit word read once for the two sums.
  * Nothing is allocated, the host is not synchronised and no memset is issued: the calls can be captured into a graph. */
 
 /* the words [p, p + extent) an operand spans: limbs x polynomials of N words under the layout (a broadcast key: [limb][N]) */
@@ -98,49 +99,63 @@ extern "C" int ntt_rns_galois_batch_strided(int nlimbs, ntt_plan *const *plans, 
   return rns_galois(nlimbs, plans, d_out, d_in, g, batch, flags, stream, Layout{limb_stride, poly_stride});
 }
 
-static int rns_galois_dot(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, int k, const uint64_t *const *d_ahat, const uint64_t *const *d_keyhat,
-                          uint64_t g, uint64_t batch, unsigned flags, void *stream, const Layout &lay)
+/* nc = 1: c^ = d_c[0] with the keys d_keyhat[0]; nc = 2: the pair form, both components of the key in one launch per 16 limbs */
+static int rns_galois_dot(int nlimbs, ntt_plan *const *plans, int nc, uint64_t *const *d_c, int k, const uint64_t *const *d_ahat,
+                          const uint64_t *const *const *d_keyhat, uint64_t g, uint64_t batch, unsigned flags, void *stream, const Layout &lay)
 {
   if(flags & ~(unsigned)(NTT_GALOIS_TRANSFORMED | NTT_GALOIS_ACCUMULATE | NTT_GALOIS_KEY_BROADCAST)) return fail(NTT_ERR_ARG, "unknown flag");
-  if(k < 1 || k > kGaloisDot || !d_ahat || !d_keyhat) return fail(NTT_ERR_ARG, "number of operand pairs must be 1 .. 32");
-  if(!d_c) return fail(NTT_ERR_ARG, "null argument");
+  if(k < 1 || k > kGaloisDot || !d_ahat) return fail(NTT_ERR_ARG, "number of operand pairs must be 1 .. 32");
+  for(int j = 0; j < nc; j++) {
+    if(!d_keyhat[j]) return fail(NTT_ERR_ARG, "number of operand pairs must be 1 .. 32");
+    if(!d_c[j]) return fail(NTT_ERR_ARG, "null argument");
+  }
   for(int i = 0; i < k; i++) {
-    if(!d_ahat[i] || !d_keyhat[i]) return fail(NTT_ERR_ARG, "null operand"); /* (before any limb offset is added) */
+    if(!d_ahat[i]) return fail(NTT_ERR_ARG, "null operand"); /* (before any limb offset is added) */
+    for(int j = 0; j < nc; j++) {
+      if(!d_keyhat[j][i]) return fail(NTT_ERR_ARG, "null operand");
+    }
   }
   int rc = galois_check(nlimbs, plans, g, batch, lay);
   if(rc || batch == 0) return rc;
   const uint64_t   N      = plans[0]->N;
   const bool       bcast  = (flags & NTT_GALOIS_KEY_BROADCAST) != 0;
   const uint64_t   kls    = bcast ? N : lay.limb, kps = bcast ? 0 : lay.poly; /* a broadcast key is [limb][N] */
-  const GaloisSpan out    = galois_span(d_c, N, nlimbs, batch, lay.limb, lay.poly);
-  for(int i = 0; i < k; i++) {
-    if(galois_overlap(out, galois_span(d_ahat[i], N, nlimbs, batch, lay.limb, lay.poly)) ||
-       galois_overlap(out, galois_span(d_keyhat[i], N, nlimbs, bcast ? 1 : batch, kls, kps)))
-      return fail(NTT_ERR_ARG, "galois_dot: the output overlaps an operand (the call is out of place)");
+  for(int j = 0; j < nc; j++) {
+    const GaloisSpan out = galois_span(d_c[j], N, nlimbs, batch, lay.limb, lay.poly);
+    if(j == 1 && galois_overlap(out, galois_span(d_c[0], N, nlimbs, batch, lay.limb, lay.poly)))
+      return fail(NTT_ERR_ARG, "galois_dot: the two outputs overlap");
+    for(int i = 0; i < k; i++) {
+      bool hit = galois_overlap(out, galois_span(d_ahat[i], N, nlimbs, batch, lay.limb, lay.poly));
+      for(int jj = 0; jj < nc; jj++) hit = hit || galois_overlap(out, galois_span(d_keyhat[jj][i], N, nlimbs, bcast ? 1 : batch, kls, kps));
+      if(hit) return fail(NTT_ERR_ARG, "galois_dot: the output overlaps an operand (the call is out of place)");
+    }
   }
   USE_DEVICE(plans[0]->device);
-  GaloisDotArgs da{};
-  da.k               = k;
-  da.limb_stride     = lay.limb;
-  da.poly_stride     = lay.poly;
-  da.key_limb_stride = kls;
-  da.key_poly_stride = kps;
-  da.batch           = batch;
-  da.logn            = (uint32_t)plans[0]->m;
-  da.g               = (uint32_t)g;
-  da.accumulate      = (flags & NTT_GALOIS_ACCUMULATE) != 0;
-  da.max_grid        = plans[0]->max_grid;
-  da.stream          = (hipStream_t)stream;
+  GaloisDotArgs  da{};
+  GaloisDot2Args da2{};
+  da.k = da2.k                             = k;
+  da.limb_stride = da2.limb_stride         = lay.limb;
+  da.poly_stride = da2.poly_stride         = lay.poly;
+  da.key_limb_stride = da2.key_limb_stride = kls;
+  da.key_poly_stride = da2.key_poly_stride = kps;
+  da.batch = da2.batch                     = batch;
+  da.logn = da2.logn                       = (uint32_t)plans[0]->m;
+  da.g = da2.g                             = (uint32_t)g;
+  da.accumulate = da2.accumulate           = (flags & NTT_GALOIS_ACCUMULATE) != 0;
+  da.max_grid = da2.max_grid               = plans[0]->max_grid;
+  da.stream = da2.stream                   = (hipStream_t)stream;
   for(int first = 0; first < nlimbs; first += kGaloisLimbs) {
-    da.nlimbs = nlimbs - first < kGaloisLimbs ? nlimbs - first : kGaloisLimbs;
-    da.c      = d_c + (uint64_t)first * lay.limb;
+    da.nlimbs = da2.nlimbs = nlimbs - first < kGaloisLimbs ? nlimbs - first : kGaloisLimbs;
+    da.c                   = d_c[0] + (uint64_t)first * lay.limb;
+    for(int j = 0; j < nc; j++) da2.c[j] = d_c[j] + (uint64_t)first * lay.limb;
     for(int i = 0; i < k; i++) {
-      da.a[i]   = d_ahat[i] + (uint64_t)first * lay.limb;
-      da.key[i] = d_keyhat[i] + (uint64_t)first * kls;
+      da.a[i] = da2.a[i] = d_ahat[i] + (uint64_t)first * lay.limb;
+      da.key[i]          = d_keyhat[0][i] + (uint64_t)first * kls;
+      for(int j = 0; j < nc; j++) da2.key[j][i] = d_keyhat[j][i] + (uint64_t)first * kls;
     }
-    for(int l = 0; l < da.nlimbs; l++) da.ql[l] = bconv_dst(plans[first + l]->q);
-    const hipError_t e = launch_galois_dot(da);
-    if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("galois_dot_kernel: ") + hipGetErrorString(e));
+    for(int l = 0; l < da.nlimbs; l++) da.ql[l] = da2.ql[l] = bconv_dst(plans[first + l]->q);
+    const hipError_t e = nc == 2 ? launch_galois_dot2(da2) : launch_galois_dot(da);
+    if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string(nc == 2 ? "keypair_dot2_kernel: " : "galois_dot_kernel: ") + hipGetErrorString(e));
   }
   return NTT_OK;
 }
@@ -148,12 +163,32 @@ static int rns_galois_dot(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, int
 extern "C" int ntt_rns_galois_dot_batch(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, int k, const uint64_t *const *d_ahat,
                                         const uint64_t *const *d_keyhat, uint64_t g, uint64_t batch, unsigned flags, void *stream)
 {
-  return rns_galois_dot(nlimbs, plans, d_c, k, d_ahat, d_keyhat, g, batch, flags, stream, limb_major(plans, nlimbs, batch));
+  return rns_galois_dot(nlimbs, plans, 1, &d_c, k, d_ahat, &d_keyhat, g, batch, flags, stream, limb_major(plans, nlimbs, batch));
 }
 
 extern "C" int ntt_rns_galois_dot_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, int k, const uint64_t *const *d_ahat,
                                                 const uint64_t *const *d_keyhat, uint64_t g, uint64_t limb_stride, uint64_t poly_stride,
                                                 uint64_t batch, unsigned flags, void *stream)
 {
-  return rns_galois_dot(nlimbs, plans, d_c, k, d_ahat, d_keyhat, g, batch, flags, stream, Layout{limb_stride, poly_stride});
+  return rns_galois_dot(nlimbs, plans, 1, &d_c, k, d_ahat, &d_keyhat, g, batch, flags, stream, Layout{limb_stride, poly_stride});
+}
+
+/* the pair form: c0^ (+)= sum_i sigma_g(a_i^) (.) key0_i^ and c1^ (+)= sum_i sigma_g(a_i^) (.) key1_i^, every permuted digit read once */
+extern "C" int ntt_rns_galois_dot_pair_batch(int nlimbs, ntt_plan *const *plans, uint64_t *d_c0, uint64_t *d_c1, int k, const uint64_t *const *d_ahat,
+                                             const uint64_t *const *d_key0hat, const uint64_t *const *d_key1hat, uint64_t g, uint64_t batch,
+                                             unsigned flags, void *stream)
+{
+  uint64_t *const              c[2]   = {d_c0, d_c1};
+  const uint64_t *const *const key[2] = {d_key0hat, d_key1hat};
+  return rns_galois_dot(nlimbs, plans, 2, c, k, d_ahat, key, g, batch, flags, stream, limb_major(plans, nlimbs, batch));
+}
+
+extern "C" int ntt_rns_galois_dot_pair_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_c0, uint64_t *d_c1, int k,
+                                                     const uint64_t *const *d_ahat, const uint64_t *const *d_key0hat,
+                                                     const uint64_t *const *d_key1hat, uint64_t g, uint64_t limb_stride, uint64_t poly_stride,
+                                                     uint64_t batch, unsigned flags, void *stream)
+{
+  uint64_t *const              c[2]   = {d_c0, d_c1};
+  const uint64_t *const *const key[2] = {d_key0hat, d_key1hat};
+  return rns_galois_dot(nlimbs, plans, 2, c, k, d_ahat, key, g, batch, flags, stream, Layout{limb_stride, poly_stride});
 }

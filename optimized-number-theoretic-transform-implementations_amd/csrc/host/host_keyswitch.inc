@@ -65,6 +65,68 @@ static int distinct_primes(int nlimbs, ntt_plan *const *plans)
   return NTT_OK;
 }
 
+/* ModUp's constants and launch loop, shared by ntt_rns_mod_up_batch and the key products that convert on their composition route
+ * (host_modup_mul.inc, host_key_pair.inc).  modup_args: the digit's primes into b[] and everything of the launch record that does not
+ * depend on the destination limbs. */
+static void modup_args(ntt_plan *const *plans, uint64_t *d_a, int first, int count, uint64_t batch, void *stream, const Layout &lay, uint64_t *b,
+                       BconvArgs &ba)
+{
+  for(int i = 0; i < count; i++) b[i] = plans[first + i]->q;
+  bconv_sources(b, count, false, ba.sl);
+  ba.a           = d_a;
+  ba.limb_stride = lay.limb;
+  ba.poly_stride = lay.poly;
+  ba.batch       = batch;
+  ba.logn        = (uint32_t)plans[0]->m;
+  ba.first       = first;
+  ba.count       = count;
+  ba.max_grid    = plans[0]->max_grid;
+  ba.stream      = (hipStream_t)stream;
+}
+
+/* bconv_kernel over ranges (k0, ndst) of ModUp's destination index -- the operand's limbs without the digit: destination k is slot k
+ * in front of the digit, slot k + count behind it --, one launch per 16 destination limbs of a range */
+static int modup_launches(ntt_plan *const *plans, const uint64_t *b, BconvArgs &ba, const std::pair<int, int> *ranges, size_t nranges)
+{
+  const int first = ba.first, count = ba.count;
+  for(size_t r = 0; r < nranges; r++) {
+    const int end = ranges[r].first + ranges[r].second;
+    for(int k0 = ranges[r].first; k0 < end; k0 += kBconvLimbs) {
+      ba.k0   = k0;
+      ba.ndst = end - k0 < kBconvLimbs ? end - k0 : kBconvLimbs;
+      for(int d = 0; d < ba.ndst; d++) {
+        const int      k = k0 + d;
+        const uint64_t q = plans[k < first ? k : k + count]->q;
+        uint64_t       g[kBconvLimbs];
+        ba.dl[d] = bconv_dst(q);
+        bconv_hats(b, count, q, g);
+        for(int i = 0; i < count; i++) ba.g[i][d] = g[i];
+      }
+      const hipError_t e = launch_bconv(ba);
+      if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("bconv_kernel: ") + hipGetErrorString(e));
+    }
+  }
+  return NTT_OK;
+}
+
+/* the destination ranges of the runs that convert through memory (fused[r] == 0), adjacent ranges joined: every run gives
+ * [0, nlimbs - count), ntt_rns_mod_up_batch's launches */
+static std::vector<std::pair<int, int>> modup_dst_ranges(const std::vector<std::pair<int, int>> &runs, const std::vector<char> &fused, int first,
+                                                         int count)
+{
+  std::vector<std::pair<int, int>> dst;
+  for(size_t r = 0; r < runs.size(); r++) {
+    if(fused[r]) continue;
+    for(int l = runs[r].first; l < runs[r].first + runs[r].second; l++) {
+      if(l >= first && l < first + count) continue;
+      const int k = l < first ? l : l - count;
+      if(!dst.empty() && dst.back().first + dst.back().second == k) dst.back().second++;
+      else dst.emplace_back(k, 1);
+    }
+  }
+  return dst;
+}
+
 /* ------------------------------------------------------------------ */
 /* ModUp                                                               */
 /* ------------------------------------------------------------------ */
@@ -90,34 +152,11 @@ static int rns_mod_up(int nlimbs, ntt_plan *const *plans, uint64_t *d_a, int fir
   USE_DEVICE(plans[0]->device);
   const Layout one{lay.limb, lay.poly};
   uint64_t     b[kBconvLimbs];
-  for(int i = 0; i < count; i++) b[i] = plans[first + i]->q;
-  BconvArgs ba{};
-  bconv_sources(b, count, false, ba.sl);
-  ba.a           = d_a;
-  ba.limb_stride = lay.limb;
-  ba.poly_stride = lay.poly;
-  ba.batch       = batch;
-  ba.logn        = (uint32_t)plans[0]->m;
-  ba.first       = first;
-  ba.count       = count;
-  ba.max_grid    = plans[0]->max_grid;
-  ba.stream      = (hipStream_t)stream;
+  BconvArgs    ba{};
+  modup_args(plans, d_a, first, count, batch, stream, lay, b, ba);
   if(ntt_dom) rc = rns_transform(count, plans + first, d_a + (uint64_t)first * lay.limb, batch, true, stream, one);
-  const int ndst = nlimbs - count;
-  for(int k0 = 0; !rc && k0 < ndst; k0 += kBconvLimbs) {
-    ba.k0   = k0;
-    ba.ndst = ndst - k0 < kBconvLimbs ? ndst - k0 : kBconvLimbs;
-    for(int d = 0; d < ba.ndst; d++) {
-      const int      k = k0 + d;
-      const uint64_t q = plans[k < first ? k : k + count]->q;
-      uint64_t       g[kBconvLimbs];
-      ba.dl[d] = bconv_dst(q);
-      bconv_hats(b, count, q, g);
-      for(int i = 0; i < count; i++) ba.g[i][d] = g[i];
-    }
-    const hipError_t e = launch_bconv(ba);
-    if(e != hipSuccess) rc = fail(NTT_ERR_HIP, std::string("bconv_kernel: ") + hipGetErrorString(e));
-  }
+  const std::pair<int, int> all(0, nlimbs - count);
+  if(!rc) rc = modup_launches(plans, b, ba, &all, 1);
   if(!rc && ntt_dom) rc = rns_transform(nlimbs, plans, d_a, batch, false, stream, one);
   return rc;
 }

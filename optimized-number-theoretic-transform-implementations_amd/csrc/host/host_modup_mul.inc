@@ -103,51 +103,14 @@ static int rns_mod_up_mul(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, uin
   USE_DEVICE(plans[0]->device);
   const uint64_t bslab = (flags & NTT_MUL_B_BROADCAST) ? N : lay.limb; /* a broadcast key is [limb][N] */
   uint64_t       b[kBconvLimbs];
-  for(int i = 0; i < count; i++) b[i] = plans[first + i]->q;
-  BconvArgs ba{};
-  bconv_sources(b, count, false, ba.sl);
+  BconvArgs      ba{};
+  modup_args(plans, d_ext, first, count, batch, stream, lay, b, ba);
   const std::vector<std::pair<int, int>> runs = rns_runs(nlimbs, plans);
   std::vector<char>                      fused(runs.size(), 0);
-  /* the composition runs' destination limbs as ranges of ModUp's destination index (the operand's limbs without the digit), adjacent
-   * ranges joined: all runs on the composition give [0, nlimbs - count), ntt_rns_mod_up_batch's launches */
-  std::vector<std::pair<int, int>> dst;
-  for(size_t r = 0; r < runs.size(); r++) {
-    const int rf = runs[r].first, rn = runs[r].second;
-    fused[r]     = modup_fused_applies(plans[0], plans[rf], count) ? 1 : 0;
-    if(fused[r]) continue;
-    for(int l = rf; l < rf + rn; l++) {
-      if(l >= first && l < first + count) continue;
-      const int k = l < first ? l : l - count;
-      if(!dst.empty() && dst.back().first + dst.back().second == k) dst.back().second++;
-      else dst.emplace_back(k, 1);
-    }
-  }
-  ba.a           = d_ext;
-  ba.limb_stride = lay.limb;
-  ba.poly_stride = lay.poly;
-  ba.batch       = batch;
-  ba.logn        = (uint32_t)plans[0]->m;
-  ba.first       = first;
-  ba.count       = count;
-  ba.max_grid    = plans[0]->max_grid;
-  ba.stream      = (hipStream_t)stream;
-  for(const std::pair<int, int> &rg : dst) {
-    for(int k0 = rg.first; !rc && k0 < rg.first + rg.second; k0 += kBconvLimbs) {
-      const int left = rg.first + rg.second - k0;
-      ba.k0          = k0;
-      ba.ndst        = left < kBconvLimbs ? left : kBconvLimbs;
-      for(int d = 0; d < ba.ndst; d++) {
-        const int      k = k0 + d;
-        const uint64_t q = plans[k < first ? k : k + count]->q;
-        uint64_t       g[kBconvLimbs];
-        ba.dl[d] = bconv_dst(q);
-        bconv_hats(b, count, q, g);
-        for(int i = 0; i < count; i++) ba.g[i][d] = g[i];
-      }
-      const hipError_t e = launch_bconv(ba);
-      if(e != hipSuccess) rc = fail(NTT_ERR_HIP, std::string("bconv_kernel: ") + hipGetErrorString(e));
-    }
-  }
+  for(size_t r = 0; r < runs.size(); r++) fused[r] = modup_fused_applies(plans[0], plans[runs[r].first], count) ? 1 : 0;
+  /* the composition runs' destination limbs as ranges of ModUp's destination index */
+  const std::vector<std::pair<int, int>> dst = modup_dst_ranges(runs, fused, first, count);
+  rc = modup_launches(plans, b, ba, dst.data(), dst.size());
   for(size_t r = 0; !rc && r < runs.size(); r++) {
     if(fused[r]) rc = modup_mul_launch(plans, runs[r].first, runs[r].second, first, count, d_c, d_ext, d_keyhat, bslab, batch, flags, stream, lay, ba.sl);
   }

@@ -1,0 +1,6 @@
+/* modup_mul2_f64k1.hip -- instantiates the pair form of the ModUp-times-key kernels (modup_mul2_kernel, N = 2^6..2^14) for (ArithF64, headroom class 1). */
+#include "ntt_kernels_modup_mul2.h"
+
+namespace ntt {
+NTT_DEFINE_LAUNCH_MODUP_MUL2(ArithF64, 1)
+} /* namespace ntt */

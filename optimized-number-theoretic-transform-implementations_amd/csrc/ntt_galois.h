@@ -2,7 +2,7 @@
  * ntt_galois.h -- launchers of the Galois automorphism kernels (ntt_galois_batch, ntt_rns_galois_batch, ntt_rns_galois_dot_batch):
  * the host layer's view of them, and the index functions the kernels, the host checks and the CPU tests share.
  *
- * The kernels live in galois_coef.hip (galois_ntt_kernel, galois_dot_kernel, galois_coef_kernel); this header declares the argument
+ * The kernels live in galois_coef.hip (galois_ntt_kernel, galois_dot_kernel, galois_coef_kernel) and in keypair_dot2.hip (keypair_dot2_kernel); this header declares the argument
  * records and the launchers, nothing that the host translation unit would instantiate.
  *
  * sigma_g(a)(X) = a(X^g) in Z_q[X] / (X^N + 1), g odd, 0 < g < 2N, N = 2^m.
@@ -98,5 +98,23 @@ struct GaloisDotArgs {
   hipStream_t     stream;
 };
 hipError_t launch_galois_dot(const GaloisDotArgs &da);
+
+/* the rotation key product for both components of the key (keypair_dot2_kernel):
+ *   c_j[s] (+)= sum_{i<k} a_i[galois_ntt_src(s)] * key_j,i[s] mod q_l,  j = 0, 1,
+ * every permuted digit word loaded once */
+struct GaloisDot2Args {
+  uint64_t *      c[2]; /* the run's first limb, as every a[i] and key[j][i] */
+  const uint64_t *a[kGaloisDot];
+  const uint64_t *key[2][kGaloisDot];
+  int             k;
+  uint64_t        limb_stride, poly_stride, key_limb_stride, key_poly_stride, batch;
+  uint32_t        logn, g;
+  int             nlimbs;
+  bool            accumulate;
+  BconvDst        ql[kGaloisLimbs];
+  int             max_grid;
+  hipStream_t     stream;
+};
+hipError_t launch_galois_dot2(const GaloisDot2Args &da);
 
 } // namespace ntt

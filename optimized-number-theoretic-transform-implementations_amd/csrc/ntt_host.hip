@@ -138,5 +138,6 @@ static int check_device(int device)
 #include "host/host_keyswitch.inc"
 #include "host/host_galois.inc"
 #include "host/host_modup_mul.inc"
+#include "host/host_key_pair.inc"
 #include "host/host_runtime.inc"
 #include "host/host_compat.inc"

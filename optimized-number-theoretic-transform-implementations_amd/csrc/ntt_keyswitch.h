@@ -195,4 +195,30 @@ template <> hipError_t launch_modup_mul<ArithF64, 1>(const ModUpMulArgs &);
 template <> hipError_t launch_modup_mul<ArithF64, 18>(const ModUpMulArgs &);
 template <> hipError_t launch_modup_mul<ArithF64W, 0>(const ModUpMulArgs &);
 
+/* The pair form of the above: c0_l^ (+)= fwd(.) (.) key0_l^ and c1_l^ (+)= fwd(.) (.) key1_l^ from ONE conversion and ONE set of forward
+ * stages (modup_mul2_kernel; modup_mul2_f64*.hip).  own = all ones (count = 1, dig = a): every limb is transformed as it stands, the
+ * pair form of the forward-multiply. */
+struct ModUpMul2Args {
+  uint64_t *      a;      /* the run's first limb of the extended operand (read only: the digit's own limbs)  */
+  const uint64_t *dig;    /* the digit's first limb, coefficients                                             */
+  const uint64_t *b[2];   /* key0^, key1^, the run's first limb                                               */
+  uint64_t *      out[2]; /* c0^, c1^, the run's first limb                                                   */
+  const void *    limbs;  /* HOST array of the run's LimbRec<A>                                               */
+  int             nlimbs; /* 1 .. kBconvLimbs                                                                 */
+  int             count;  /* 1 .. kBconvLimbs                                                                 */
+  uint32_t        own;    /* bit l: limb l of the run belongs to the digit                                    */
+  uint64_t        limb_stride, poly_stride, b_limb_stride, batch;
+  uint32_t        logn;
+  bool            lazy_in, b_bcast, accumulate;
+  BconvSrc        sl[kBconvLimbs];
+  BconvDst        dl[kBconvLimbs];
+  int             max_grid, num_cus;
+  hipStream_t     stream;
+};
+template <class A, int KSH> hipError_t launch_modup_mul2(const ModUpMul2Args &ma);
+template <> hipError_t launch_modup_mul2<ArithF64, 0>(const ModUpMul2Args &);
+template <> hipError_t launch_modup_mul2<ArithF64, 1>(const ModUpMul2Args &);
+template <> hipError_t launch_modup_mul2<ArithF64, 18>(const ModUpMul2Args &);
+template <> hipError_t launch_modup_mul2<ArithF64W, 0>(const ModUpMul2Args &);
+
 } // namespace ntt

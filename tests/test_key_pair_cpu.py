@@ -1,0 +1,144 @@
+"""CPU: the pair key products without a GPU -- the model of tests/key_pair_model.py against big-integer arithmetic over the CRT at
+N = 2^4 (mod_up_mul_pair: lift the digit to x in [0, B), extend as x + u B with 0 <= u < count, reduce mod every prime, forward
+transform, times each component's key, plus that component's accumulator; fwd_mul_pair: the same without the extension; the Galois
+pair: the permuted sum of products per component); the six exported symbols and their declarations in the public header; the Python
+wrappers; the plain-C example against the public header alone; and the kernels of the new translation units (modup_mul2_*.o):
+exactly the 36 expected instances, none spilling vector registers or using scratch, keypair_dot2_kernel likewise."""
+import glob
+import os
+import random
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import galois_model as gm
+import key_pair_model as kp
+import keyswitch_model as km
+import test_keyswitch_cpu as tkc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_amd", "csrc")
+LIB = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_amd", "libntt_mi355x.so")
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+N = 16
+SYMBOLS = ["ntt_rns_fwd_mul_pair_batch", "ntt_rns_mod_up_mul_pair_batch", "ntt_rns_galois_dot_pair_batch"]
+SYMBOLS += [s + "_strided" for s in SYMBOLS]
+A, B, L = kp.ACCUMULATE, kp.BROADCAST, kp.LAZY_IN
+
+
+def _want(f, key, acc, q, batch, flags):
+    kq = [int(v) % q for v in key]
+    return [(int(f[i]) * kq[i % N if flags & B else i] + (int(acc[i]) if flags & A else 0)) % q for i in range(batch * N)]
+
+
+@pytest.mark.parametrize("bits,first,count", tkc.UP_CHAINS, ids=["start", "middle", "end", "one-limb", "count16"])
+@pytest.mark.parametrize("flags", [0, A, B, B | A | L])
+def test_mod_up_mul_pair_model_equals_the_definition(oracle, bits, first, count, flags):
+    batch = 2
+    primes, roots = tkc._chain(oracle, N, bits)
+    basis = primes[first:first + count]
+    Bp = km.prod(basis)
+    rng = random.Random(len(bits) * 41 + first + flags)
+    xs = [0, Bp - 1, 1, Bp // 2] + [rng.randrange(Bp) for _ in range(batch * N - 4)]
+    digit = [np.array([x % b for x in xs], dtype=np.uint64) for b in basis]
+    _, keys, accs = kp.operands(oracle, primes, N, batch, first, count, flags, seed=5)
+    got, ext = kp.model(oracle, primes, roots, digit, keys, accs, N, batch, first, count, flags)
+    us = [(s - x) // Bp for s, x in zip(km.fastbconv_int(basis, digit), xs)]
+    assert all(0 <= u < count for u in us)
+    differ = 0
+    for l, (q, w) in enumerate(zip(primes, roots)):
+        lifted = np.array([(x + u * Bp) % q for x, u in zip(xs, us)], dtype=np.uint64)
+        assert np.array_equal(ext[l], lifted), "ModUp limb %d" % l
+        f = oracle.ctx(N, q, w).fwd(lifted)
+        for j in range(2):
+            assert got[j][l].tolist() == _want(f, keys[j][l], accs[j][l], q, batch, flags), "component %d limb %d" % (j, l)
+        differ += not np.array_equal(got[0][l], got[1][l])
+    assert differ, "the two components' expected values coincide: a swapped component would pass"
+
+
+@pytest.mark.parametrize("flags", [0, A, B, B | A | L])
+def test_fwd_mul_pair_model_equals_the_definition(oracle, flags):
+    batch = 3
+    primes, roots = tkc._chain(oracle, N, [50, 52, 60, 30])
+    a, keys, accs = kp.operands(oracle, primes, N, batch, 0, len(primes), flags, seed=9)
+    got, fa = kp.fwd_model(oracle, primes, roots, a, keys, accs, N, batch, flags)
+    for l, (q, w) in enumerate(zip(primes, roots)):
+        f = oracle.ctx(N, q, w).fwd(a[l])
+        assert np.array_equal(fa[l], f)
+        for j in range(2):
+            assert got[j][l].tolist() == _want(f, keys[j][l], accs[j][l], q, batch, flags), "component %d limb %d" % (j, l)
+        assert not np.array_equal(got[0][l], got[1][l])
+
+
+@pytest.mark.parametrize("k", [1, 3, 5])
+@pytest.mark.parametrize("flags", [gm.TRANSFORMED, gm.TRANSFORMED | gm.ACCUMULATE | gm.KEY_BROADCAST])
+def test_galois_pair_model_equals_the_definition(oracle, k, flags):
+    """galois_model.dot_model per component against the permuted sum of products in Python integers"""
+    batch, q = 2, oracle.find_prime(60, N, 0)
+    g = gm.rotation(N, -3)
+    src = gm.ntt_source(N, g)
+    bc = bool(flags & gm.KEY_BROADCAST)
+    a = [oracle.fill_uniform(batch * N, q, 10 + i) for i in range(k)]
+    for j in range(2):
+        key = [oracle.fill_uniform(N if bc else batch * N, q, 100 + i + 50 * j) for i in range(k)]
+        c = oracle.fill_uniform(batch * N, q, 7 + j)
+        got = gm.dot_model(oracle, c, a, key, N, g, q, flags)
+        want = []
+        for p in range(batch):
+            for s in range(N):
+                t = sum(int(a[i][p * N + int(src[s])]) * int(key[i][s if bc else p * N + s]) for i in range(k))
+                want.append((t + (int(c[p * N + s]) if flags & gm.ACCUMULATE else 0)) % q)
+        assert got.tolist() == want, "component %d" % j
+
+
+def test_exports_the_six_symbols_and_the_header_declares_them(lib):
+    out = subprocess.check_output(["nm", "-D", "--defined-only", lib.LIB_PATH], text=True)
+    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert set(SYMBOLS) <= names, sorted(set(SYMBOLS) - names)
+    with open(os.path.join(ROOT, "include", "ntt_mi355x.h")) as f:
+        header = f.read()
+    for s in SYMBOLS:
+        assert re.search(r"NTT_API int %s\(" % s, header), s
+        assert s in lib.EXPORTED_SYMBOLS
+    assert re.search(r"NTT_OPT_PAIR_FUSED\s*=\s*19\b", header)
+
+
+def test_python_wrappers_exist(lib):
+    for name in ("rns_fwd_mul_pair", "rns_mod_up_mul_pair", "rns_galois_dot_pair"):
+        assert callable(getattr(lib, name)), name
+    assert lib.OPT_PAIR_FUSED == 19
+
+
+def test_pair_example_builds_against_the_public_header(lib):
+    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
+    exe = os.path.join(ROOT, "build", "rns_key_switch_pair")
+    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "examples", "rns_key_switch_pair.c"), "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x",
+                           "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
+    assert os.path.exists(exe)
+
+
+def pair_kernels():
+    """{normalised name: metadata} of the kernels of the new translation units (or, where the objects are not
+    at hand, the same kernels of the linked library)"""
+    import check_spills
+    import kernel_inventory
+    objs = sorted(glob.glob(os.path.join(CSRC, "modup_mul2_*.o"))) + sorted(glob.glob(os.path.join(CSRC, "keypair_dot2.o")))
+    ks = [k for o in objs for k in check_spills.kernels_of(o)] if len(objs) == 5 else check_spills.kernels_of(LIB)
+    ks = [k for k in ks if "modup_mul2_kernel" in k["name"] or "keypair_dot2_kernel" in k["name"]]
+    names = [k["name"] for k in ks]
+    return {kernel_inventory.normalise(d): k for d, k in zip(kernel_inventory.demangle(names), ks)}
+
+
+def test_pair_objects_hold_exactly_the_expected_instances_without_spills():
+    ks = pair_kernels()
+    want = {"modup_mul2_kernel<%s,%d,%d>" % (pol, logn, k) for pol, k, logn in kp.launch_cases()} | {"keypair_dot2_kernel"}
+    assert len(want) == 37
+    assert set(ks) == want, ("missing %s, unexpected %s" % (sorted(want - set(ks))[:8], sorted(set(ks) - want)[:8]))
+    bad = {n: (k.get("vgpr_spill_count"), k.get("private_segment_fixed_size"), k.get("group_segment_fixed_size"))
+           for n, k in ks.items()
+           if k.get("vgpr_spill_count", 0) or k.get("private_segment_fixed_size", 0) or k.get("group_segment_fixed_size", 0) > 160 * 1024}
+    assert not bad, "spills / scratch / LDS: %s" % bad
