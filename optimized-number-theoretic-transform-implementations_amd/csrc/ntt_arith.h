@@ -816,6 +816,150 @@ template <class Base> struct WideF64 : Base {
 using ArithF64W = WideF64<ArithF64>;
 
 /* ------------------------------------------------------------------ */
+/* ArithF64S: ArithF64 with every working value carried at 2^-1074       */
+/* ------------------------------------------------------------------ */
+/*
+ * S = 2^-1074, v^ = v * S.  A stored word u < 2^53 read as a double IS u^ (see u64_to_f64_lt52), every integer |v| < 2^53 is
+ * exactly representable at scale (the subnormals are the multiples of S up to 2^52 S, the first normal binade has the same
+ * spacing), and sums and differences are exact while the result stays below 2^53 S.  Twiddles, w/q, q and 1/q stay at unit
+ * scale: tables and F64Consts are ArithF64's.  What the scale buys: a product by a unit-scale number whose true value lies
+ * below 2^53 S is rounded by the MULTIPLIER to the grid of spacing S -- to the nearest integer, ties to even, in one rounding --
+ * so the quotient estimate needs no v_rndne_f64, and words enter and leave without ldexp / scaling fma:
+ *   h = y^ * w           = fl(Y W) S      (|Y W| >= 2^52: a normal number, the 53-bit rounding of ArithF64::mulmod; below: exact)
+ *   l = fma(y^, w, -h)   exact            (an integer below 2^51, times S)
+ *   k = y^ * wq          = rint(Y wq) S   one rounding: |Y wq| <= B q / 2 < 2^53
+ *   d = fma(-k, q, h)    exact            ((h - K q) is an integer below 2^53)
+ *   r = d + l
+ * Five instructions instead of six, the butterfly seven instead of eight.  Only wq's own rounding is left in the estimate:
+ * |K - Y W / q| <= 1/2 + B theta2 / 2 for a full record (ArithF64: 1/2 + B theta2), 1/2 + B theta2 for a compact twiddle
+ * (k = h * qinv; ArithF64: 1/2 + 1.5 B theta2) -- every bound is at most ArithF64's, so its reduction schedules (f64_schedule,
+ * make_inv_red_plan) hold unchanged.  reduce is two instructions, to_canonical six, a lazy output one add.
+ * Two scaled values must never be multiplied (S^2 underflows to zero): the policy has NO product_*, dot_* or mul_out members,
+ * so a kernel that forms products of transform values does not compile with it.  Not for WideF64: mulmod_c2's h * qinv_lo
+ * falls below S at scale.
+ */
+struct ArithF64S {
+  using val    = double;
+  using tw     = TwF64;
+  using consts = F64Consts;
+  using ctw    = double;
+  static constexpr bool kTracksBounds = true;
+  static constexpr bool kCompact      = true;
+  static constexpr bool kRadix4       = false;
+  static constexpr bool kWide52       = false;
+  static constexpr bool kIntWide      = false;
+  static NTT_HD tw expand(ctw w, const consts &c) { return ArithF64::expand(w, c); }
+
+  /* the word u < 2^53 as the double u * 2^-1074, and back: no instruction */
+  static NTT_HD double word_to_val(uint64_t u)
+  {
+    union {
+      uint64_t u;
+      double   d;
+    } x;
+    x.u = u;
+    return x.d;
+  }
+  static NTT_HD uint64_t val_to_word(double d)
+  {
+    union {
+      double   d;
+      uint64_t u;
+    } x;
+    x.d = d;
+    return x.u;
+  }
+  /* v^ - q * rint(v / q)^: the product lands on the grid of S already rounded */
+  static NTT_HD double reduce(double v, const consts &c)
+  {
+    const double k = v * c.qinv;
+    return fma_(-k, c.q, v);
+  }
+  static NTT_HD double mulmod(const tw &t, double y, const consts &c)
+  {
+    const double h = y * t.w;
+    const double k = y * t.wq;
+    const double l = fma_(y, t.w, -h);
+    const double d = fma_(-k, c.q, h);
+    return d + l;
+  }
+  static NTT_HD double mulmod_c(ctw w, double y, const consts &c)
+  {
+    const double h = y * w;
+    const double k = h * c.qinv;
+    const double l = fma_(y, w, -h);
+    const double d = fma_(-k, c.q, h);
+    return d + l;
+  }
+  template <bool INV, bool WIDE> static NTT_HD val load(uint64_t raw, const consts &c)
+  {
+    if(WIDE) {
+      raw = raw < 4 * c.qi ? raw : raw - 4 * c.qi;
+      raw = raw < 2 * c.qi ? raw : raw - 2 * c.qi;
+      raw = raw < c.qi ? raw : raw - c.qi;
+    }
+    return word_to_val(raw);
+  }
+  template <bool RED> static NTT_HD void fwd_bfly(val &x, val &y, const tw &t, const consts &c)
+  {
+    const double xr = RED ? reduce(x, c) : x;
+    const double m  = mulmod(t, y, c);
+    x               = xr + m;
+    y               = xr - m;
+  }
+  template <bool RED> static NTT_HD void inv_bfly(val &x, val &y, const tw &t, const consts &c)
+  {
+    const double s = x + y;
+    const double d = x - y;
+    x              = RED ? reduce(s, c) : s;
+    y              = mulmod(t, d, c);
+  }
+  template <bool RED> static NTT_HD void fwd_bfly(val &x, val &y, ctw w, const consts &c)
+  {
+    const double xr = RED ? reduce(x, c) : x;
+    const double m  = mulmod_c(w, y, c);
+    x               = xr + m;
+    y               = xr - m;
+  }
+  template <bool RED> static NTT_HD void inv_bfly(val &x, val &y, ctw w, const consts &c)
+  {
+    const double s = x + y;
+    const double d = x - y;
+    x              = RED ? reduce(s, c) : s;
+    y              = mulmod_c(w, d, c);
+  }
+  static NTT_HD void inv_bfly_last(val &x, val &y, const consts &c)
+  {
+    const double s = x + y;
+    const double d = x - y;
+    x              = mulmod(c.ninv, s, c);
+    y              = mulmod(c.wninv, d, c);
+  }
+  /* balanced |v| < 2^53 -> canonical [0,q): r^ + (r < 0 ? q^ : 0), the bit pattern of the sum is the word.  The masked word is
+   * q or 0 from the sign bit (r is never -0.0: an fma whose exact result is zero returns +0, and reduce(-0.0) = +0 - 0). */
+  static NTT_HD uint64_t to_canonical(double v, const consts &c)
+  {
+    const double   r = reduce(v, c);
+    const uint64_t m = c.qi & (uint64_t)((int64_t)val_to_word(r) >> 63);
+    return val_to_word(r + word_to_val(m));
+  }
+  static NTT_HD uint64_t store_fwd(val v, const consts &c) { return to_canonical(v, c); }
+  static NTT_HD uint64_t store_inv(val v, const consts &c) { return to_canonical(v, c); }
+  /* v + 2q in [0,4q) for |v| <= kLazyBound * q (ArithF64::store_fwd_lazy): one add */
+  static NTT_HD uint64_t store_fwd_lazy(val v, const consts &c) { return val_to_word(v + c.q2_sub); }
+  static NTT_HD uint64_t store_inv_lazy(val v, const consts &c) { return to_canonical(v, c); }
+  static NTT_HD val      scale_ninv(val v, const consts &c) { return mulmod(c.ninv, v, c); }
+};
+
+/* the policy a transform kernel computes in: ArithF64's transforms run at scale (words in memory are the same integers) */
+template <class A> struct scaled_policy {
+  using type = A;
+};
+template <> struct scaled_policy<ArithF64> {
+  using type = ArithF64S;
+};
+
+/* ------------------------------------------------------------------ */
 /* compile-time reduction schedule for ArithF64                        */
 /* ------------------------------------------------------------------ */
 /*

@@ -188,8 +188,10 @@ inline uint64_t block_grid(uint64_t nblocks, uint32_t s0, uint64_t nl, int num_c
  * kernel is the single-set kernel it always was; a run-time limb index costs the register-tight kernels 2-4 spilled VGPRs
  * (measured: the 2^14 inverse, the 2^13 forward), which is why the host only uses the MULTI variants when one limb's share
  * alone cannot fill the chip. */
-template <class A, bool INV, bool MULTI>
-__device__ __forceinline__ Params<A> limb_params(const KArgs<A> &k, uint32_t &bid, uint32_t &gdim, uint32_t &limb)
+/* (AK: the policy the launch's arguments were built for; A, the policy the kernel computes in, may be its scaled form -- same
+ * tables and constants, ntt_arith.h scaled_policy) */
+template <class A, bool INV, bool MULTI, class AK>
+__device__ __forceinline__ Params<A> limb_params(const KArgs<AK> &k, uint32_t &bid, uint32_t &gdim, uint32_t &limb)
 {
   if constexpr(MULTI) {
     /* A two-dimensional grid: blockIdx.y is the limb, blockIdx.x the block id inside the limb's share -- both arrive in scalar
@@ -206,8 +208,8 @@ __device__ __forceinline__ Params<A> limb_params(const KArgs<A> &k, uint32_t &bi
     bid  = blockIdx.x;
     gdim = gridDim.x;
   }
-  const LimbRec<A> &r = k.limbs[limb];
-  Params<A>         p;
+  const LimbRec<AK> &r = k.limbs[limb];
+  Params<A>          p;
   p.a       = k.a + (uint64_t)limb * k.limb_stride;
   p.tw      = INV ? r.tw_i : r.tw_f;
   p.tw8     = INV ? r.tw8_i : r.tw8_f;
@@ -446,9 +448,13 @@ __device__ __forceinline__ void fill_lds_tables(typename A::ctw *tabl, const Par
 /* LAZY (forward, FP64 policy): outputs in [0,4q) instead of [0,q) -- a kernel variant of its own because
  * the reduction schedule has to bound the last stage (fused_mask); the integer policies take the run-time
  * flag Params::lazy instead. */
-template <class A, int LOGN, bool INV, int KSH, bool LASTINV = false, bool LAZY = false, bool MULTI = false>
-__global__ void __launch_bounds__((Geom<LOGN, INV, flavor_of<A>()>::WG), (Geom<LOGN, INV, flavor_of<A>()>::WPS)) fused_kernel(const KArgs<A> k)
+/* AK = ArithF64 computes in ArithF64S (every working value at 2^-1074: seven FP64 instructions per butterfly, no conversions on
+ * the way in or out); the words in memory, the tables, the constants and the reduction masks are the same, so the launch layer
+ * and the kernel's name know nothing of it. */
+template <class AK, int LOGN, bool INV, int KSH, bool LASTINV = false, bool LAZY = false, bool MULTI = false>
+__global__ void __launch_bounds__((Geom<LOGN, INV, flavor_of<AK>()>::WG), (Geom<LOGN, INV, flavor_of<AK>()>::WPS)) fused_kernel(const KArgs<AK> k)
 {
+  using A = typename scaled_policy<AK>::type;
   uint32_t        bid, gdim, limb_;
   const Params<A> p = limb_params<A, INV, MULTI>(k, bid, gdim, limb_);
   using P                 = Plan<LOGN>;

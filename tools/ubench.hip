@@ -3,13 +3,17 @@
  *   1. issue cost (cycles per wave64 instruction per SIMD) of the integer-multiply and FP64
  *      instructions the two arithmetic policies are made of;
  *   2. register-resident butterfly throughput of ArithU64 and ArithF64 as compiled;
- *   3. plain HBM copy bandwidth (the practical ceiling for the roofline fraction).
- * Build: make ubench   Run (GPU box): build/ubench
+ *   3. plain HBM copy bandwidth (the practical ceiling for the roofline fraction);
+ *   4. (build/ubench scaled -- only this part) the premise of ArithF64S: issue cost of v_mul/v_fma/v_add_f64 on SUBNORMAL operands
+ *      beside the normal-range rows, and the register-resident radix-16 tile of ArithF64S beside ArithF64's, alternating, in
+ *      launches long enough to sit at the board's power cap, with the clock the kernel itself saw.
+ * Build: make ubench   Run (GPU box): build/ubench [scaled]
  */
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "ntt_core.h"
@@ -74,6 +78,14 @@ OP_KERNEL(rndne_f64, DECL_F64, INIT_F64, asm volatile("v_rndne_f64 %0, %0" : "+v
 OP_KERNEL(floor_f64, DECL_F64, INIT_F64, asm volatile("v_floor_f64 %0, %0" : "+v"(a[c])), SINK_F64)
 OP_KERNEL(min_f64, DECL_F64, INIT_F64, asm volatile("v_min_f64 %0, %0, %1" : "+v"(a[c]) : "v"(b)), SINK_F64)
 OP_KERNEL(cmp_gt_f64, DECL_F64, INIT_F64, asm volatile("v_cmp_gt_f64 vcc, %0, %1" : : "v"(a[c]), "v"(b) : "vcc"), SINK_F64)
+/* the same three with operands and results in the subnormal range (a: ~2^40 * 2^-1074, growing by at most 5 % / by 2^12 * 2^25 units of
+ * 2^-1074 over the run; b stays 1 + 1e-5: the unit-scale factor of a scaled product) */
+#define DECL_F64S double a[CHAINS]; double b = 1.0 + seed * 1e-9, d = __longlong_as_double((long long)(seed | 1u) << 12)
+#define INIT_F64S _Pragma("unroll") for(int c = 0; c < CHAINS; c++) a[c] = __longlong_as_double((1ll << 40) + c * 977 + threadIdx.x)
+#define SINK_F64S s += (uint64_t)__double_as_longlong(a[c])
+OP_KERNEL(fma_f64_sub, DECL_F64S, INIT_F64S, asm volatile("v_fma_f64 %0, %0, %1, %2" : "+v"(a[c]) : "v"(b), "v"(d)), SINK_F64S)
+OP_KERNEL(mul_f64_sub, DECL_F64S, INIT_F64S, asm volatile("v_mul_f64 %0, %0, %1" : "+v"(a[c]) : "v"(b)), SINK_F64S)
+OP_KERNEL(add_f64_sub, DECL_F64S, INIT_F64S, asm volatile("v_add_f64 %0, %0, %1" : "+v"(a[c]) : "v"(d)), SINK_F64S)
 OP_KERNEL(fma_f32, DECL_U32, INIT_U32, asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(a[c]) : "v"(b), "v"(d)), SINK_U32)
 OP_KERNEL(pk_fma_f32, DECL_U64, INIT_U64, asm volatile("v_pk_fma_f32 %0, %0, %1, %1" : "+v"(a[c]) : "v"(e)), SINK_U64)
 
@@ -141,6 +153,39 @@ template <class A, uint32_t MASK> __global__ void __launch_bounds__(256) k_bfly(
   uint64_t s = 0;
   for(int i = 0; i < 16; i++) s += A::store_fwd(x[i], c);
   out[blockIdx.x * 256 + threadIdx.x] = s;
+}
+
+/* the same tile in a launch of seconds, with the clocks the kernel saw: clk[0..1] = shader cycle counter, clk[2..3] = the constant
+ * 100 MHz counter, at the start and the end of block 0's first wave */
+template <class A, uint32_t MASK> __global__ void __launch_bounds__(256) k_bfly_clk(uint64_t *out, uint64_t *clk, typename A::consts c, typename A::tw w0, int reps)
+{
+  typename A::val x[16];
+  typename A::tw  w[4];
+  const uint64_t  c0 = clock64(), r0 = wall_clock64();
+  for(int i = 0; i < 16; i++) x[i] = A::template load<false, false>((uint64_t)(threadIdx.x * 16 + i + 1), c);
+  for(int i = 0; i < 4; i++) {
+    w[i] = w0;
+  }
+  for(int r = 0; r < reps; r++) {
+    static_for<0, 4>([&](auto jj) {
+      constexpr int  J   = decltype(jj)::value;
+      constexpr int  AB  = 3 - J;
+      constexpr bool RED = (MASK >> J) & 1u;
+      static_for<0, 16>([&](auto ee) {
+        constexpr int E0 = decltype(ee)::value;
+        if constexpr(((E0 >> AB) & 1) == 0) A::template fwd_bfly<RED>(x[E0], x[E0 | (1 << AB)], w[J], c);
+      });
+    });
+  }
+  uint64_t s = 0;
+  for(int i = 0; i < 16; i++) s += A::store_fwd(x[i], c);
+  out[blockIdx.x * 256 + threadIdx.x] = s;
+  if(blockIdx.x == 0 && threadIdx.x == 0) {
+    clk[0] = c0;
+    clk[1] = clock64();
+    clk[2] = r0;
+    clk[3] = wall_clock64();
+  }
 }
 
 __global__ void __launch_bounds__(256) k_copy(uint4 *dst, const uint4 *src, size_t n)
@@ -257,7 +302,60 @@ template <class K> static void run_op(const char *name, K kernel, uint64_t *d_ou
   printf("%-16s %8.3f ms  %6.2f cycles/wave-instr/SIMD (at %.2f GHz)\n", name, ms, cyc, clock_ghz);
 }
 
-int main()
+/* part 4: see the head of the file */
+static void scaled_gate(uint64_t *d_out)
+{
+#define RUN(N) run_op(#N, k_##N, d_out)
+  for(int rep = 0; rep < 2; rep++) {
+    RUN(fma_f64); RUN(fma_f64_sub); RUN(mul_f64); RUN(mul_f64_sub); RUN(add_f64); RUN(add_f64_sub); RUN(rndne_f64);
+  }
+#undef RUN
+  const uint64_t        q = 0x7fffffffe0001ULL;
+  std::vector<uint64_t> wi(2, 1);
+  const auto            cf = h_consts_f64(q, 1 << 14, wi);
+  const auto            w  = h_tw_f64(123456789012345ULL, q);
+  uint64_t *            clk;
+  CK(hipHostMalloc(&clk, 4 * sizeof(uint64_t)));
+  const int  blocks = 256 * 8; /* 8 waves per SIMD */
+  hipEvent_t e0, e1;
+  CK(hipEventCreate(&e0));
+  CK(hipEventCreate(&e1));
+  auto tile = [&](bool scaled, int reps, const char *tag) {
+    float ms;
+    CK(hipEventRecord(e0));
+    if(scaled) hipLaunchKernelGGL((k_bfly_clk<ArithF64S, 0x5>), dim3(blocks), dim3(256), 0, 0, d_out, clk, cf, w, reps);
+    else hipLaunchKernelGGL((k_bfly_clk<ArithF64, 0x5>), dim3(blocks), dim3(256), 0, 0, d_out, clk, cf, w, reps);
+    CK(hipEventRecord(e1));
+    CK(hipEventSynchronize(e1));
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    uint64_t sum = 0;
+    CK(hipMemcpy(&sum, d_out, 8, hipMemcpyDeviceToHost));
+    const double bf  = (double)blocks * 256 * 32.0 * reps;
+    const double ghz = (double)(clk[1] - clk[0]) / ((double)(clk[3] - clk[2]) * 10.0); /* cycles per ns */
+    printf("%-22s %-6s %9.2f ms  %8.2f Gbutterfly/s  in-kernel clock %.3f GHz  (checksum %016llx)\n", tag, scaled ? "scaled" : "unit", ms,
+           bf / ms * 1e-6, ghz, (unsigned long long)sum);
+    fflush(stdout);
+    return bf / ms * 1e-6;
+  };
+  /* both tiles compute the same residues: short launches first, whose checksums must agree */
+  tile(false, 256, "tile check");
+  tile(true, 256, "tile check");
+  const int reps = 256 * 1200; /* about 1.5 s per launch */
+  tile(false, reps, "tile warm-up");
+  double lo[2] = {1e30, 1e30}, hi[2] = {0, 0};
+  for(int round = 0; round < 5; round++) {
+    for(int sc = 0; sc < 2; sc++) {
+      const double g = tile(sc != 0, reps, "tile at the power cap");
+      lo[sc] = g < lo[sc] ? g : lo[sc];
+      hi[sc] = g > hi[sc] ? g : hi[sc];
+    }
+  }
+  printf("unit   tile: %.2f .. %.2f Gbutterfly/s (spread %.3f %%)\n", lo[0], hi[0], (hi[0] / lo[0] - 1) * 100);
+  printf("scaled tile: %.2f .. %.2f Gbutterfly/s (spread %.3f %%)\n", lo[1], hi[1], (hi[1] / lo[1] - 1) * 100);
+  printf("scaled slowest / unit fastest = %.4f\n", lo[1] / hi[0]);
+}
+
+int main(int argc, char **argv)
 {
   hipDeviceProp_t prop;
   CK(hipGetDeviceProperties(&prop, 0));
@@ -265,11 +363,15 @@ int main()
   printf("device %s, %d CUs, clock %.2f GHz, wave %d\n", prop.name, prop.multiProcessorCount, clock_ghz, prop.warpSize);
   uint64_t *d_out;
   CK(hipMalloc(&d_out, 1 << 22));
+  if(argc > 1 && !strcmp(argv[1], "scaled")) {
+    scaled_gate(d_out);
+    return 0;
+  }
 #define RUN(N) run_op(#N, k_##N, d_out)
   RUN(add_u32); RUN(mul_lo_u32); RUN(mul_hi_u32); RUN(mul_u32_u24); RUN(mul_hi_u32_u24); RUN(mad_u32_u24);
   RUN(mad_u64_u32); RUN(lshl_add_u64); RUN(cmp_lt_u64); RUN(cndmask); RUN(mov_dpp);
   RUN(bpermute);
-  RUN(fma_f32); RUN(pk_fma_f32); RUN(fma_f64); RUN(mul_f64); RUN(add_f64); RUN(rndne_f64); RUN(floor_f64); RUN(min_f64);
+  RUN(fma_f32); RUN(pk_fma_f32); RUN(fma_f64); RUN(mul_f64); RUN(add_f64); RUN(fma_f64_sub); RUN(mul_f64_sub); RUN(add_f64_sub); RUN(rndne_f64); RUN(floor_f64); RUN(min_f64);
   RUN(cmp_gt_f64); RUN(cvt_f64_u32); RUN(cvt_u32_f64);
 
   /* butterfly throughput */
