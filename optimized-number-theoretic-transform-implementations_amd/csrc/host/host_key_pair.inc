@@ -2,8 +2,9 @@
  * ntt_rns_mod_up_mul_pair_batch and their strided forms,
  *     c0^ (+)= fwd(x) (.) key0^,   c1^ (+)= fwd(x) (.) key1^,   x = the operand (fwd_mul_pair) or ModUp(digit) (mod_up_mul_pair),
  * the shared operand read, converted and transformed ONCE.  A section of ntt_host.hip (one translation unit, included from there in
- * order); not compiled by itself.  The fused kernel is in the modup_mul2_f64*.hip units, the two-output element-wise kernel in
- * keypair_dot2.hip; this section sees their launchers only (ntt_keyswitch.h, ntt_galois.h).  The pair form of the rotation key
+ * order); not compiled by itself.  The fused kernel is in the modup_mul2_f64*.hip units (launched by host_modup_mul.inc's
+ * modup_mul_launch with two components), the two-output element-wise kernel in keypair_dot2.hip; this section sees their launchers
+ * only (ntt_keyswitch.h, ntt_galois.h).  The pair form of the rotation key
  * product is in host_galois.inc.
  *
  * Per run of compatible limbs (rns_runs):
@@ -65,46 +66,6 @@ struct KeyPair {
   void *          stream;
   Layout          lay;
 };
-
-static int modup_mul2_launch(ntt_plan *const *plans, int rf, int rn, const KeyPair &kp, const BconvSrc *sl)
-{
-  const std::vector<unsigned char> recs = rns_records(plans, rf, rn);
-  ModUpMul2Args                    ma{};
-  ma.a   = kp.x + (uint64_t)rf * kp.lay.limb;
-  ma.dig = kp.x + (uint64_t)kp.first * kp.lay.limb;
-  for(int j = 0; j < 2; j++) {
-    ma.b[j]   = kp.key[j] + (uint64_t)rf * kp.bslab;
-    ma.out[j] = kp.c[j] + (uint64_t)rf * kp.lay.limb;
-  }
-  ma.limbs         = recs.data();
-  ma.nlimbs        = rn;
-  ma.count         = kp.count ? kp.count : 1;
-  ma.limb_stride   = kp.lay.limb;
-  ma.poly_stride   = kp.lay.poly;
-  ma.b_limb_stride = kp.bslab;
-  ma.batch         = kp.batch;
-  ma.logn          = (uint32_t)plans[rf]->m;
-  ma.lazy_in       = (kp.flags & NTT_MUL_LAZY_IN) != 0;
-  ma.b_bcast       = (kp.flags & NTT_MUL_B_BROADCAST) != 0;
-  ma.accumulate    = (kp.flags & NTT_MUL_ACCUMULATE) != 0;
-  for(int i = 0; i < kp.count; i++) ma.sl[i] = sl[i];
-  for(int l = 0; l < rn; l++) {
-    ma.dl[l] = bconv_dst(plans[rf + l]->q);
-    if(!kp.count || (rf + l >= kp.first && rf + l < kp.first + kp.count)) ma.own |= 1u << l;
-  }
-  ma.max_grid = plans[rf]->max_grid;
-  ma.num_cus  = plans[rf]->num_cus;
-  ma.stream   = (hipStream_t)kp.stream;
-  /* the run's coarsest headroom class (rns_for_runs); a run of 52-bit primes is all of the wide policy (rns_compatible) */
-  int kc = plans[rf]->kcls;
-  for(int l = rf + 1; l < rf + rn; l++) kc = plans[l]->kcls < kc ? plans[l]->kcls : kc;
-  const hipError_t e = kc == kWideClass ? launch_modup_mul2<ArithF64W, 0>(ma)
-                       : kc == 18       ? launch_modup_mul2<ArithF64, 18>(ma)
-                       : kc == 1        ? launch_modup_mul2<ArithF64, 1>(ma)
-                                        : launch_modup_mul2<ArithF64, 0>(ma);
-  if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("modup_mul2_kernel: ") + hipGetErrorString(e));
-  return NTT_OK;
-}
 
 /* c_j^ (+)= x^ (.) key_j^ over limbs [rf, rf + rn): keypair_dot2_kernel with the identity permutation, one launch per 16 limbs */
 static int pair_products(ntt_plan *const *plans, int rf, int rn, const KeyPair &kp)
@@ -177,7 +138,8 @@ static int rns_key_pair(int nlimbs, ntt_plan *const *plans, KeyPair kp)
     rc                                         = modup_launches(plans, b, ba, dst.data(), dst.size());
   }
   for(size_t r = 0; !rc && r < runs.size(); r++) {
-    if(fused[r]) rc = modup_mul2_launch(plans, runs[r].first, runs[r].second, kp, ba.sl);
+    if(fused[r])
+      rc = modup_mul_launch(plans, runs[r].first, runs[r].second, first, count, 2, kp.c, kp.x, kp.key, kp.bslab, kp.batch, kp.flags, kp.stream, kp.lay, ba.sl);
   }
   for(size_t r = 0; !rc && r < runs.size(); r++) {
     if(fused[r]) continue;

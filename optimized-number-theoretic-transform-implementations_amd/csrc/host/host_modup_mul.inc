@@ -1,7 +1,7 @@
 /* host/host_modup_mul.inc -- one digit's term of the key-switching inner product in one call: ntt_rns_mod_up_mul_batch and its strided
  * form, c^ (+)= fwd(ModUp(digit)) (.) key^ over every limb of the extended basis.  A section of ntt_host.hip (one translation unit,
  * included from there in order); not compiled by itself.  The kernel is in the modup_mul_f64*.hip units; this section sees its
- * launchers only (ntt_keyswitch.h).
+ * launchers only (ntt_keyswitch.h).  modup_mul_launch also serves the pair form of host_key_pair.inc.
  *
  * Per run of compatible limbs (rns_runs):
  *   fused        FP64 policies, N = 2^6..2^14, where NTT_OPT_MODUP_FUSED on plans[0] allows it: ONE modup_mul_kernel launch -- the base
@@ -42,18 +42,25 @@ static bool modup_fused_applies(const ntt_plan *p0, const ntt_plan *p, int count
   return modup_fused_pays(count);
 }
 
-static int modup_mul_launch(ntt_plan *const *plans, int rf, int rn, int first, int count, uint64_t *d_c, uint64_t *d_ext, const uint64_t *d_keyhat,
-                            uint64_t bslab, uint64_t batch, unsigned flags, void *stream, const Layout &lay, const BconvSrc *sl)
+/* ONE launch of the fused kernel over the run [rf, rf + rn): ncomp = 1 modup_mul_kernel (c[0] (+)= .. key[0]), ncomp = 2 modup_mul2_kernel
+ * (both components; host_key_pair.inc).  x is the extended operand, the digit its limbs [first, first + count).  count = 0 is
+ * host_key_pair.inc's fwd_mul_pair: no conversion, every limb of the run is its own digit limb and the kernel's count is 1. */
+static int modup_mul_launch(ntt_plan *const *plans, int rf, int rn, int first, int count, int ncomp, uint64_t *const *c, uint64_t *x,
+                            const uint64_t *const *key, uint64_t bslab, uint64_t batch, unsigned flags, void *stream, const Layout &lay,
+                            const BconvSrc *sl)
 {
   const std::vector<unsigned char> recs = rns_records(plans, rf, rn);
   ModUpMulArgs                     ma{};
-  ma.a             = d_ext + (uint64_t)rf * lay.limb;
-  ma.dig           = d_ext + (uint64_t)first * lay.limb;
-  ma.b             = d_keyhat + (uint64_t)rf * bslab;
-  ma.out           = d_c + (uint64_t)rf * lay.limb;
+  ma.a     = x + (uint64_t)rf * lay.limb;
+  ma.dig   = x + (uint64_t)first * lay.limb;
+  ma.ncomp = ncomp;
+  for(int j = 0; j < ncomp; j++) {
+    ma.b[j]   = key[j] + (uint64_t)rf * bslab;
+    ma.out[j] = c[j] + (uint64_t)rf * lay.limb;
+  }
   ma.limbs         = recs.data();
   ma.nlimbs        = rn;
-  ma.count         = count;
+  ma.count         = count ? count : 1;
   ma.limb_stride   = lay.limb;
   ma.poly_stride   = lay.poly;
   ma.b_limb_stride = bslab;
@@ -65,7 +72,7 @@ static int modup_mul_launch(ntt_plan *const *plans, int rf, int rn, int first, i
   for(int i = 0; i < count; i++) ma.sl[i] = sl[i];
   for(int l = 0; l < rn; l++) {
     ma.dl[l] = bconv_dst(plans[rf + l]->q);
-    if(rf + l >= first && rf + l < first + count) ma.own |= 1u << l;
+    if(!count || (rf + l >= first && rf + l < first + count)) ma.own |= 1u << l;
   }
   ma.max_grid = plans[rf]->max_grid;
   ma.num_cus  = plans[rf]->num_cus;
@@ -73,11 +80,14 @@ static int modup_mul_launch(ntt_plan *const *plans, int rf, int rn, int first, i
   /* the run's coarsest headroom class (rns_for_runs); a run of 52-bit primes is all of the wide policy (rns_compatible) */
   int kc = plans[rf]->kcls;
   for(int l = rf + 1; l < rf + rn; l++) kc = plans[l]->kcls < kc ? plans[l]->kcls : kc;
-  const hipError_t e = kc == kWideClass ? launch_modup_mul<ArithF64W, 0>(ma)
-                       : kc == 18       ? launch_modup_mul<ArithF64, 18>(ma)
-                       : kc == 1        ? launch_modup_mul<ArithF64, 1>(ma)
-                                        : launch_modup_mul<ArithF64, 0>(ma);
-  if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("modup_mul_kernel: ") + hipGetErrorString(e));
+  const hipError_t e = with_int<1, 2>(ncomp, hipErrorInvalidValue, [&](auto nc) {
+    constexpr int NC = decltype(nc)::value;
+    return kc == kWideClass ? launch_modup_mul<ArithF64W, 0, NC>(ma)
+           : kc == 18       ? launch_modup_mul<ArithF64, 18, NC>(ma)
+           : kc == 1        ? launch_modup_mul<ArithF64, 1, NC>(ma)
+                            : launch_modup_mul<ArithF64, 0, NC>(ma);
+  });
+  if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string(ncomp == 2 ? "modup_mul2_kernel: " : "modup_mul_kernel: ") + hipGetErrorString(e));
   return NTT_OK;
 }
 
@@ -112,7 +122,7 @@ static int rns_mod_up_mul(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, uin
   const std::vector<std::pair<int, int>> dst = modup_dst_ranges(runs, fused, first, count);
   rc = modup_launches(plans, b, ba, dst.data(), dst.size());
   for(size_t r = 0; !rc && r < runs.size(); r++) {
-    if(fused[r]) rc = modup_mul_launch(plans, runs[r].first, runs[r].second, first, count, d_c, d_ext, d_keyhat, bslab, batch, flags, stream, lay, ba.sl);
+    if(fused[r]) rc = modup_mul_launch(plans, runs[r].first, runs[r].second, first, count, 1, &d_c, d_ext, &d_keyhat, bslab, batch, flags, stream, lay, ba.sl);
   }
   for(size_t r = 0; !rc && r < runs.size(); r++) {
     if(fused[r]) continue;

@@ -1,6 +1,6 @@
-/* modup_mul2_f64w.hip -- instantiates the pair form of the ModUp-times-key kernels (modup_mul2_kernel, N = 2^6..2^14) for (ArithF64W, headroom class 0). */
-#include "ntt_kernels_modup_mul2.h"
+/* modup_mul2_f64w.hip -- instantiates the pair form of the ModUp-times-key kernels (modup_mul2_kernel: ntt_kernels_modup_mul.h's body with two components, N = 2^6..2^14) for (ArithF64W, headroom class 0). */
+#include "ntt_kernels_modup_mul.h"
 
 namespace ntt {
-NTT_DEFINE_LAUNCH_MODUP_MUL2(ArithF64W, 0)
+NTT_DEFINE_LAUNCH_MODUP_MUL(ArithF64W, 0, 2)
 } /* namespace ntt */

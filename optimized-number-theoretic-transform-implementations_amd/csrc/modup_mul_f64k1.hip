@@ -2,5 +2,5 @@
 #include "ntt_kernels_modup_mul.h"
 
 namespace ntt {
-NTT_DEFINE_LAUNCH_MODUP_MUL(ArithF64, 1)
+NTT_DEFINE_LAUNCH_MODUP_MUL(ArithF64, 1, 1)
 } /* namespace ntt */

@@ -182,6 +182,15 @@ inline uint64_t block_grid(uint64_t nblocks, uint32_t s0, uint64_t nl, int num_c
   return wgs < cap ? wgs : cap;
 }
 
+/* a run-time value as a template argument: f(std::integral_constant<int, v>{}) for v in LO..HI, `otherwise` outside (here, not in
+ * ntt_kernels_launch.h: the launchers of the stand-alone kernel headers -- rescale, ModDown, ModUp products -- pick their size with it too) */
+template <int LO, int HI, class F> inline hipError_t with_int(int v, hipError_t otherwise, F &&f)
+{
+  if(v == LO) return f(std::integral_constant<int, LO>{});
+  if constexpr(LO < HI) return with_int<LO + 1, HI>(v, otherwise, f);
+  else return otherwise;
+}
+
 /* the launch's Params for this workgroup's limb; bid = its block id inside the limb's share of the grid */
 /* MULTI is a compile-time property of the kernel: with it off the limb is 0, every record field sits at a fixed offset of
  * the kernel-argument segment (the compiler re-loads such values at will instead of keeping them in registers) and the

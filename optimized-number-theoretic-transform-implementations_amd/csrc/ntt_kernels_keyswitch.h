@@ -21,7 +21,7 @@
 #include "ntt_core.h"
 #include "ntt_passplan.h"
 #include "ntt_kernels_block.h"
-#include "ntt_keyswitch.h"
+#include "ntt_kernels_bconv.h"
 
 namespace ntt {
 
@@ -54,19 +54,7 @@ __global__ void __launch_bounds__((Geom<LOGN, false, flavor_of<A>()>::WG), (Geom
   const int            np  = kr.np;
   const lds_ctw_ptr<A> gtw = (lds_ctw_ptr<A>)reinterpret_cast<typename A::ctw *>(lds_all + G::BPW * P::LDS_ELEMS);
   if constexpr(LDS_TW > 0) fill_lds_tables<A, LOGN, false>(reinterpret_cast<typename A::ctw *>(lds_all + G::BPW * P::LDS_ELEMS), p, 0u, tid);
-  if(np > 1) {
-    if(tid < (uint32_t)np) {
-      /* prod_{k != j} p_k mod q_l: g < q_l and p_k < 2^61, each product below 2^122 (bconv_reduce takes any 128-bit word) */
-      uint64_t g = 1;
-      for(int k = 0; k < np; k++) {
-        if(k == (int)tid) continue;
-        const uint64_t pk = kr.pl[k].p;
-        g                 = bconv_reduce(mulhi64(g, pk), g * pk, ql);
-        g                 = g >= ql.q ? g - ql.q : g;
-      }
-      ghat[tid] = g;
-    }
-  }
+  if(np > 1) bconv_ghat(ghat, kr.pl, np, ql, tid);
   if constexpr(LDS_TW > 0) __syncthreads();
   else if(np > 1) __syncthreads();
   /* P^-1 mod q_l as a balanced double, |.| <= q/2 (the multiplier of every product of this workgroup) */
@@ -91,39 +79,11 @@ __global__ void __launch_bounds__((Geom<LOGN, false, flavor_of<A>()>::WG), (Geom
           raw[E]              = moddown_digit1(stream_load(coef_at(row, tg)), s0, ql);
         });
       } else {
-        /* half a tile at a time: the 128-bit sums of 8 words stay in registers beside nothing else (x is not live yet) */
-        static_for<0, 2>([&](auto hh) {
-          constexpr int H = decltype(hh)::value;
-          uint64_t      hi[kE / 2], lo[kE / 2];
-          static_for<0, kE / 2>([&](auto ee) {
-            hi[decltype(ee)::value] = 0;
-            lo[decltype(ee)::value] = 0;
-          });
-          const uint64_t *tj = tblk;
-          for(int j = 0; j < np; j++) {
-            const BconvSrc s = kr.pl[j];
-            const uint64_t g = ghat[j];
-            static_for<0, kE / 2>([&](auto ee) {
-              constexpr int   E   = decltype(ee)::value;
-              const uint64_t *row = tj + ((uint32_t)(H * kE / 2 + E) << P::LT);
-              bconv_mac(hi[E], lo[E], bconv_digit(stream_load(coef_at(row, tg)), s), g);
-            });
-            tj += kr.k.limb_stride;
-          }
-          static_for<0, kE / 2>([&](auto ee) {
-            constexpr int E     = decltype(ee)::value;
-            raw[H * kE / 2 + E] = moddown_digit(hi[E], lo[E], ql);
-          });
-        });
+        bconv_tile<P::LT>(raw, tblk, kr.k.limb_stride, kr.pl, ghat, np, tg, [&](uint64_t hi, uint64_t lo) { return moddown_digit(hi, lo, ql); });
       }
       convert_inputs<A, false>(x, raw, false, p.c);
     }
-    run_group<A, LOGN, 0, false, MASK, (G::TBL(0) > 0)>(x, tg, 0u, p, gtw);
-    static_for<0, P::NG - 1>([&](auto gg) {
-      constexpr int GI = decltype(gg)::value;
-      exchange<A, LOGN, GI, GI + 1>(x, tg, lds);
-      run_group<A, LOGN, GI + 1, false, MASK, (G::TBL(GI + 1) > 0)>(x, tg, 0u, p, gtw + G::TBL_OFF(GI + 1));
-    });
+    fwd_block_stages<A, LOGN, MASK>(x, tg, p, lds, gtw);
     static_for<0, 4>([&](auto qq) {
       constexpr int Q = decltype(qq)::value;
       uint64_t      rc[kE], u[kE];
@@ -160,19 +120,10 @@ template <class A, int LOGN, int KSH> hipError_t launch_moddown_fwd_n(const ModD
   return hipGetLastError();
 }
 
-template <class A, int KSH> hipError_t launch_moddown_fwd_impl(const ModDownFwdArgs &ma)
-{
-  switch(ma.logn) {
-#define NTT_MODDOWN_CASE(LN) \
-  case LN: return launch_moddown_fwd_n<A, LN, KSH>(ma);
-    NTT_MODDOWN_CASE(6) NTT_MODDOWN_CASE(7) NTT_MODDOWN_CASE(8) NTT_MODDOWN_CASE(9) NTT_MODDOWN_CASE(10) NTT_MODDOWN_CASE(11)
-    NTT_MODDOWN_CASE(12) NTT_MODDOWN_CASE(13) NTT_MODDOWN_CASE(14)
-#undef NTT_MODDOWN_CASE
-    default: return hipErrorNotSupported;
+#define NTT_DEFINE_LAUNCH_MODDOWN_FWD(A, KSH)                                                                                                   \
+  template <> hipError_t launch_moddown_fwd<A, KSH>(const ModDownFwdArgs &ma)                                                                   \
+  {                                                                                                                                             \
+    return with_int<6, 14>((int)ma.logn, hipErrorNotSupported, [&](auto ln) { return launch_moddown_fwd_n<A, decltype(ln)::value, KSH>(ma); }); \
   }
-}
-
-#define NTT_DEFINE_LAUNCH_MODDOWN_FWD(A, KSH) \
-  template <> hipError_t launch_moddown_fwd<A, KSH>(const ModDownFwdArgs &ma) { return launch_moddown_fwd_impl<A, KSH>(ma); }
 
 } // namespace ntt

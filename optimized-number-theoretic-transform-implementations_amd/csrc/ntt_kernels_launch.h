@@ -158,13 +158,7 @@ template <class F, class... B> inline hipError_t with_bools(F &&f, bool b, B... 
   return b ? with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
            : with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
 }
-/* a run-time value as a template argument: f(std::integral_constant<int, v>{}) for v in LO..HI, `otherwise` outside */
-template <int LO, int HI, class F> inline hipError_t with_int(int v, hipError_t otherwise, F &&f)
-{
-  if(v == LO) return f(std::integral_constant<int, LO>{});
-  if constexpr(LO < HI) return with_int<LO + 1, HI>(v, otherwise, f);
-  else return otherwise;
-}
+/* (with_int, a run-time value as a template argument: ntt_kernels_block.h) */
 
 /* The pointer-table form of a launch (separately held polynomials): the kernel's PTRS variant reads every operand pointer as a
  * DEVICE table of polynomial addresses; k.ptab is the table behind k.a's operand and k.a what is left of the address -- the words

@@ -21,6 +21,7 @@
 #include "ntt_passplan.h"
 #include "ntt_kernels_block.h"
 #include "ntt_rescale.h"
+#include "ntt_kernels_bconv.h"
 
 namespace ntt {
 
@@ -74,12 +75,7 @@ __global__ void __launch_bounds__((Geom<LOGN, false, flavor_of<A>()>::WG), (Geom
       });
       convert_inputs<A, false>(x, raw, false, p.c);
     }
-    run_group<A, LOGN, 0, false, MASK, (G::TBL(0) > 0)>(x, tg, 0u, p, gtw);
-    static_for<0, P::NG - 1>([&](auto gg) {
-      constexpr int GI = decltype(gg)::value;
-      exchange<A, LOGN, GI, GI + 1>(x, tg, lds);
-      run_group<A, LOGN, GI + 1, false, MASK, (G::TBL(GI + 1) > 0)>(x, tg, 0u, p, gtw + G::TBL_OFF(GI + 1));
-    });
+    fwd_block_stages<A, LOGN, MASK>(x, tg, p, lds, gtw);
     static_for<0, 4>([&](auto qq) {
       constexpr int Q = decltype(qq)::value;
       uint64_t      rc[kE], u[kE];
@@ -116,19 +112,10 @@ template <class A, int LOGN, int KSH> hipError_t launch_rescale_fwd_n(const Resc
   return hipGetLastError();
 }
 
-template <class A, int KSH> hipError_t launch_rescale_fwd_impl(const RescaleFwdArgs &ra)
-{
-  switch(ra.logn) {
-#define NTT_RESCALE_CASE(LN) \
-  case LN: return launch_rescale_fwd_n<A, LN, KSH>(ra);
-    NTT_RESCALE_CASE(6) NTT_RESCALE_CASE(7) NTT_RESCALE_CASE(8) NTT_RESCALE_CASE(9) NTT_RESCALE_CASE(10) NTT_RESCALE_CASE(11)
-    NTT_RESCALE_CASE(12) NTT_RESCALE_CASE(13) NTT_RESCALE_CASE(14)
-#undef NTT_RESCALE_CASE
-    default: return hipErrorNotSupported;
+#define NTT_DEFINE_LAUNCH_RESCALE_FWD(A, KSH)                                                                                                   \
+  template <> hipError_t launch_rescale_fwd<A, KSH>(const RescaleFwdArgs &ra)                                                                   \
+  {                                                                                                                                             \
+    return with_int<6, 14>((int)ra.logn, hipErrorNotSupported, [&](auto ln) { return launch_rescale_fwd_n<A, decltype(ln)::value, KSH>(ra); }); \
   }
-}
-
-#define NTT_DEFINE_LAUNCH_RESCALE_FWD(A, KSH) \
-  template <> hipError_t launch_rescale_fwd<A, KSH>(const RescaleFwdArgs &ra) { return launch_rescale_fwd_impl<A, KSH>(ra); }
 
 } // namespace ntt

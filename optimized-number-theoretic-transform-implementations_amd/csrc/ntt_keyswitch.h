@@ -2,8 +2,9 @@
  * ntt_keyswitch.h -- launchers of the RNS base-conversion kernels of hybrid key switching (ntt_rns_mod_up_batch,
  * ntt_rns_mod_down_batch): the host layer's view of them, and the integer arithmetic they share.
  *
- * The kernel templates live in ntt_kernels_keyswitch.h (moddown_fwd_kernel, instantiated in keyswitch_f64*.hip) and in
- * keyswitch_coef.hip (bconv_kernel, moddown_coef_kernel); this header declares the argument records and the launchers, nothing
+ * The kernel templates live in ntt_kernels_keyswitch.h (moddown_fwd_kernel, instantiated in keyswitch_f64*.hip), in
+ * ntt_kernels_modup_mul.h (modup_mul_kernel, modup_mul2_kernel; modup_mul_f64*.hip, modup_mul2_f64*.hip) and in keyswitch_coef.hip
+ * (bconv_kernel, moddown_coef_kernel); this header declares the argument records and the launchers, nothing
  * that the host translation unit would instantiate.
  *
  * Fast base conversion from a basis B = {b_i} (product B, b^_i = B / b_i) to a prime q:
@@ -170,13 +171,18 @@ template <> hipError_t launch_moddown_fwd<ArithF64, 18>(const ModDownFwdArgs &);
 template <> hipError_t launch_moddown_fwd<ArithF64W, 0>(const ModDownFwdArgs &);
 
 /* ModUp fused into the key product, FP64 policies, N = 2^6..2^14: c_l^ (+)= fwd(FastBConv_{digit->q_l}) (.) key_l^ in ONE launch over a
- * run of limbs of the extended basis (modup_mul_kernel; modup_mul_f64*.hip); a digit limb inside the run is transformed as it stands.
- * The extended digit is never written.  [b^_i]_{q_l} is formed by each workgroup, as in moddown_fwd_kernel. */
+ * run of limbs of the extended basis; a digit limb inside the run is transformed as it stands.  The extended digit is never written.
+ * [b^_i]_{q_l} is formed by each workgroup, as in moddown_fwd_kernel.
+ *   ncomp = 1   one component (modup_mul_kernel; modup_mul_f64*.hip);
+ *   ncomp = 2   the pair form: c0_l^ (+)= fwd(.) (.) key0_l^ and c1_l^ (+)= fwd(.) (.) key1_l^ from ONE conversion and ONE set of forward
+ *               stages (modup_mul2_kernel; modup_mul2_f64*.hip).  own = all ones (count = 1, dig = a): every limb is transformed as it
+ *               stands, the pair form of the forward-multiply. */
 struct ModUpMulArgs {
   uint64_t *      a;      /* the run's first limb of the extended operand (read only: the digit's own limbs)  */
   const uint64_t *dig;    /* the digit's first limb, coefficients                                             */
-  const uint64_t *b;      /* key^, the run's first limb                                                       */
-  uint64_t *      out;    /* c^, the run's first limb                                                         */
+  const uint64_t *b[2];   /* key_j^, the run's first limb (j < ncomp)                                         */
+  uint64_t *      out[2]; /* c_j^, the run's first limb                                                       */
+  int             ncomp;  /* 1 or 2: the launcher's NC                                                        */
   const void *    limbs;  /* HOST array of the run's LimbRec<A>                                               */
   int             nlimbs; /* 1 .. kBconvLimbs                                                                 */
   int             count;  /* 1 .. kBconvLimbs                                                                 */
@@ -189,36 +195,14 @@ struct ModUpMulArgs {
   int             max_grid, num_cus;
   hipStream_t     stream;
 };
-template <class A, int KSH> hipError_t launch_modup_mul(const ModUpMulArgs &ma);
-template <> hipError_t launch_modup_mul<ArithF64, 0>(const ModUpMulArgs &);
-template <> hipError_t launch_modup_mul<ArithF64, 1>(const ModUpMulArgs &);
-template <> hipError_t launch_modup_mul<ArithF64, 18>(const ModUpMulArgs &);
-template <> hipError_t launch_modup_mul<ArithF64W, 0>(const ModUpMulArgs &);
-
-/* The pair form of the above: c0_l^ (+)= fwd(.) (.) key0_l^ and c1_l^ (+)= fwd(.) (.) key1_l^ from ONE conversion and ONE set of forward
- * stages (modup_mul2_kernel; modup_mul2_f64*.hip).  own = all ones (count = 1, dig = a): every limb is transformed as it stands, the
- * pair form of the forward-multiply. */
-struct ModUpMul2Args {
-  uint64_t *      a;      /* the run's first limb of the extended operand (read only: the digit's own limbs)  */
-  const uint64_t *dig;    /* the digit's first limb, coefficients                                             */
-  const uint64_t *b[2];   /* key0^, key1^, the run's first limb                                               */
-  uint64_t *      out[2]; /* c0^, c1^, the run's first limb                                                   */
-  const void *    limbs;  /* HOST array of the run's LimbRec<A>                                               */
-  int             nlimbs; /* 1 .. kBconvLimbs                                                                 */
-  int             count;  /* 1 .. kBconvLimbs                                                                 */
-  uint32_t        own;    /* bit l: limb l of the run belongs to the digit                                    */
-  uint64_t        limb_stride, poly_stride, b_limb_stride, batch;
-  uint32_t        logn;
-  bool            lazy_in, b_bcast, accumulate;
-  BconvSrc        sl[kBconvLimbs];
-  BconvDst        dl[kBconvLimbs];
-  int             max_grid, num_cus;
-  hipStream_t     stream;
-};
-template <class A, int KSH> hipError_t launch_modup_mul2(const ModUpMul2Args &ma);
-template <> hipError_t launch_modup_mul2<ArithF64, 0>(const ModUpMul2Args &);
-template <> hipError_t launch_modup_mul2<ArithF64, 1>(const ModUpMul2Args &);
-template <> hipError_t launch_modup_mul2<ArithF64, 18>(const ModUpMul2Args &);
-template <> hipError_t launch_modup_mul2<ArithF64W, 0>(const ModUpMul2Args &);
+template <class A, int KSH, int NC> hipError_t launch_modup_mul(const ModUpMulArgs &ma);
+template <> hipError_t launch_modup_mul<ArithF64, 0, 1>(const ModUpMulArgs &);
+template <> hipError_t launch_modup_mul<ArithF64, 1, 1>(const ModUpMulArgs &);
+template <> hipError_t launch_modup_mul<ArithF64, 18, 1>(const ModUpMulArgs &);
+template <> hipError_t launch_modup_mul<ArithF64W, 0, 1>(const ModUpMulArgs &);
+template <> hipError_t launch_modup_mul<ArithF64, 0, 2>(const ModUpMulArgs &);
+template <> hipError_t launch_modup_mul<ArithF64, 1, 2>(const ModUpMulArgs &);
+template <> hipError_t launch_modup_mul<ArithF64, 18, 2>(const ModUpMulArgs &);
+template <> hipError_t launch_modup_mul<ArithF64W, 0, 2>(const ModUpMulArgs &);
 
 } // namespace ntt
