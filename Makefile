@@ -21,7 +21,8 @@ OBJS     = $(CSRC)/inst_f64k0.o $(CSRC)/inst_f64k1.o $(CSRC)/inst_f64k18.o $(CSR
            $(CSRC)/keyswitch_f64k0.o $(CSRC)/keyswitch_f64k1.o $(CSRC)/keyswitch_f64k18.o $(CSRC)/keyswitch_f64w.o $(CSRC)/keyswitch_coef.o \
            $(CSRC)/modup_mul_f64k0.o $(CSRC)/modup_mul_f64k1.o $(CSRC)/modup_mul_f64k18.o $(CSRC)/modup_mul_f64w.o \
            $(CSRC)/modup_mul2_f64k0.o $(CSRC)/modup_mul2_f64k1.o $(CSRC)/modup_mul2_f64k18.o $(CSRC)/modup_mul2_f64w.o \
-           $(CSRC)/galois_coef.o $(CSRC)/keypair_dot2.o \
+           $(CSRC)/ksfold_f64k0.o $(CSRC)/ksfold_f64k1.o $(CSRC)/ksfold_f64k18.o $(CSRC)/ksfold_f64w.o \
+           $(CSRC)/galois_coef.o $(CSRC)/keypair_dot2.o $(CSRC)/ct_elem.o \
            $(CSRC)/ntt_host.o
 # the kernel translation units see the kernel headers only; the host layer also the public headers
 KHDRS    = $(wildcard $(CSRC)/*.h)
@@ -67,6 +68,13 @@ build/skel: tools/skel.hip
 	mkdir -p build
 	$(HIPCC) -O3 --offload-arch=$(ARCH) -std=c++17 -ffp-contract=off -o $@ tools/skel.hip
 .PHONY: skel
+
+# tensor_kernel's body with 8- and with 16-byte accesses beside a 16-byte copy (run on the GPU box: build/tensor_width [logn] [polynomials])
+tensor-width: build/tensor_width
+build/tensor_width: tools/tensor_width.hip $(HDRS)
+	mkdir -p build
+	$(HIPCC) -O3 --offload-arch=$(ARCH) -std=c++17 -ffp-contract=off -Iinclude -Iinclude/internal -I$(CSRC) -o $@ tools/tensor_width.hip
+.PHONY: tensor-width
 
 # ASAN + UBSAN run of the CPU-side code (oracle, host table/pass planning, kernel templates in the emulator)
 sanitize:

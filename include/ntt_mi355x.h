@@ -134,6 +134,13 @@ typedef enum ntt_option {
                           * place, one two-output element-wise product); -1 (default) = the fused kernel where the recorded
                           * measurement says it is not slower (the rule is quoted at ntt_rns_mod_up_mul_pair_batch).  Read from
                           * plans[0]; results are identical */
+  NTT_OPT_MODDOWN_ADD_FUSED = 20, /* ntt_rns_mod_down_add_batch in the NTT domain: 1 = every run of Q limbs the fused kernel is built for
+                          * (FP64 policies, N = 2^6..2^14) takes it: one forward-transform launch with the base conversion in its
+                          * prologue, whose epilogue reads the accumulator and stores into the ciphertext; 0 = every run takes the
+                          * composition (ntt_rns_mod_down_batch's route in place on the accumulator, then one element-wise launch per
+                          * 16 limbs; NTT_OPT_RESCALE_FUSED keeps selecting that route); -1 (default) = the fused kernel where the
+                          * recorded measurement says it is not slower (the rule is quoted at ntt_rns_mod_down_add_batch).  Read from
+                          * plans[0]; results are identical */
   NTT_OPT_FUSED_PRODUCT = 5 /* N = 2^8..2^17, FP64: 1 (default) = ntt_negacyclic_mul_batch as ONE launch that takes both
                           * operands through the forward stages, multiplies in registers and runs the inverse: 24N bytes up to
                           * 2^14; from 2^23 coefficients per operand of N >= 2^15 on likewise one launch (all limbs of an RNS set
@@ -426,6 +433,60 @@ NTT_API int ntt_rns_mod_up_mul_pair_batch(int nlimbs, ntt_plan *const *plans, ui
 NTT_API int ntt_rns_mod_up_mul_pair_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_c0, uint64_t *d_c1, uint64_t *d_ext,
                                                   int first, int count, const uint64_t *d_key0hat, const uint64_t *d_key1hat,
                                                   uint64_t limb_stride, uint64_t poly_stride, uint64_t batch, unsigned flags, void *stream);
+
+/* ---- The first and the last step of a homomorphic multiplication on ciphertexts held in the NTT domain.
+ * ntt_rns_tensor_batch: for ciphertexts (a0, a1) and (b0, b1), per limb l and word s,
+ *     c0 = a0 b0,   c1 = a0 b1 + a1 b0,   c2 = a1 b1   (mod q_l),
+ * outputs canonical.  Element-wise, so any domain; meant for NTT-domain operands.  All seven operands share one layout ([limb][batch][N];
+ * _strided: any strides the RNS forms accept).  Integer arithmetic for every policy and every N >= 2: the products are exact 128-bit
+ * integers, one Barrett reduction and one conditional subtraction per output word.  NTT_MUL_LAZY_IN allows input words anywhere in
+ * [0, 4q) (2 (4q)^2 < 2^127 for q < 2^61); no other flag is accepted.  One launch per 16 limbs: 32N bytes read and 24N written per
+ * limb-polynomial; when d_b0 == d_a0 and d_b1 == d_a1 (a squaring) every input word is loaded once, 16N read -- the result is bit for
+ * bit that of the general path.  An output may BE an input (the same pointer: c0 = a0, c1 = a1 works in place; every thread reads its
+ * four words before it stores its three); any other overlap of an output's span of words under the layout (first word to last) with an
+ * input's or with another output's is refused.  NTT_ERR_ARG, nothing written: nlimbs < 1, a null pointer, plans that differ in N or
+ * device, an unknown flag, overlapping strides, the overlaps above.
+ * ntt_rns_mod_down_add_batch: ModDown of an accumulator INTO a ciphertext.  d_a is an operand over Q u P exactly as for
+ * ntt_rns_mod_down_batch ([nq + np][batch][N]; _strided: a_limb_stride, a_poly_stride); d_c is an operand over the nq Q limbs with strides of
+ * its own ([nq][batch][N]; c_limb_stride, c_poly_stride).  With r_l what ntt_rns_mod_down_batch with the same NTT_MODDOWN_TRANSFORMED /
+ * NTT_MODDOWN_FLOOR flags leaves in Q limb l of a copy of d_a:
+ *     c_l = r_l                       without NTT_MODDOWN_ACCUMULATE (an out-of-place ModDown: a rotation's c1'),
+ *     c_l = (c_l + r_l) mod q_l       with it (c canonical on entry: relinearisation's (d0, d1) += ModDown(acc0, acc1), batch 2),
+ * bit for bit the existing call followed by the addition.  Afterwards d_a's Q limbs are scratch (where the fused kernel serves every
+ * run they are not written); its P limbs follow ModDown's rule (coefficients after a TRANSFORMED call, unchanged after a coefficient
+ * call).  Per run of compatible Q limbs: TRANSFORMED, FP64 policies, N = 2^6..2^14 -- ONE launch of the forward block kernel with the
+ * base conversion in its prologue, whose epilogue reads c^ from d_a, (when accumulating) the addend from d_c, adds in integer arithmetic
+ * and stores to d_c: 8N np + 16N bytes per Q limb-polynomial (24N when accumulating); anything else (integer policies, N < 2^6,
+ * N >= 2^15, coefficients) -- the composition: ntt_rns_mod_down_batch's route of that run in place on d_a, then one element-wise launch
+ * per 16 limbs.  NTT_OPT_MODDOWN_ADD_FUSED on plans[0]: 1 / 0 force the fused kernel (where built) / the composition for every run; the
+ * default, -1, applies the rule recorded in profiles/r14/ct_mul_bench.txt:
+ *     fused wherever the kernel is built.
+ * (Call rate of the fused route over the composition route, 24 50-bit Q limbs, accumulating, 2^14 x 2 / 64 / 1024 polynomials, ranges over
+ * five rounds of alternating processes: np 1: 1.08 / 1.27-1.32 / 1.51-1.52; np 2: 1.05-1.06 / 1.17-1.19 / 1.29-1.30; np 4: 1.04 /
+ * 1.15-1.16 / 1.21-1.22; 2^13 likewise, 0.99-1.06 at 2 polynomials.  The fused kernel is not slower at both 64 and 1024 polynomials for
+ * every np measured.  Over the parent commit's ntt_rns_mod_down_batch followed by the addition with torch integer ops, parent's own
+ * spread 1.01-1.02: fused np 1: 1.30-1.31 / 2.34-2.42 / 2.79-2.81; np 2: 1.19-1.20 / 1.88-1.91 / 2.05-2.07; np 4: 1.15 / 1.66-1.69 /
+ * 1.76-1.79; the composition 1.11-1.22 / 1.43-1.85 / 1.44-1.86.  The fused call takes 6-16 % longer than the parent's ModDown alone at
+ * 1024 polynomials, 20-37 % longer at 2^14 x 64.)
+ * The tensor against 4 L ntt_pointwise_mul_batch calls plus the sum with torch integer ops, the same shape: 34-41 / 3.37-3.46 / 2.80-2.88
+ * x at 2^14 (squaring by aliasing: 3.69-3.88 / 3.76-3.80 x at 64 / 1024); its time is 3.8-4.1 x ntt_copy_probe of one operand at 1024
+ * polynomials (3.5 by the algorithmic bytes), the squaring's 3.0-3.1 x (2.5).  A two-words-per-lane form with 16-byte accesses measured
+ * 3-5 % SLOWER than the one-word form (squaring: within 1.5 %), so one form ships (profiles/r14/tensor_width.txt).
+ * NTT_ERR_ARG, nothing written: everything ntt_rns_mod_down_batch refuses, a null d_c, overlapping strides in either layout, d_c's span
+ * of words overlapping d_a's, a table the chosen route needs that a plan lacks.
+ * All four: allocate nothing, do not synchronise the host, issue no memset: capturable. ---- */
+enum { NTT_MODDOWN_ACCUMULATE = 4 }; /* ntt_rns_mod_down_add_batch only (ntt_rns_mod_down_batch refuses it): c += ..., c canonical on entry */
+NTT_API int ntt_rns_tensor_batch(int nlimbs, ntt_plan *const *plans, uint64_t *d_c0, uint64_t *d_c1, uint64_t *d_c2, const uint64_t *d_a0,
+                                 const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1, uint64_t batch, unsigned flags,
+                                 void *stream);
+NTT_API int ntt_rns_tensor_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_c0, uint64_t *d_c1, uint64_t *d_c2,
+                                         const uint64_t *d_a0, const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1,
+                                         uint64_t limb_stride, uint64_t poly_stride, uint64_t batch, unsigned flags, void *stream);
+NTT_API int ntt_rns_mod_down_add_batch(int nq, int np, ntt_plan *const *plans, uint64_t *d_c, uint64_t *d_a, uint64_t batch, unsigned flags,
+                                       void *stream);
+NTT_API int ntt_rns_mod_down_add_batch_strided(int nq, int np, ntt_plan *const *plans, uint64_t *d_c, uint64_t *d_a, uint64_t c_limb_stride,
+                                               uint64_t c_poly_stride, uint64_t a_limb_stride, uint64_t a_poly_stride, uint64_t batch,
+                                               unsigned flags, void *stream);
 
 /* ---- Galois automorphisms (rotation, conjugation) and the rotation key product.  For odd g, 0 < g < 2N,
  *     sigma_g(a)(X) = a(X^g)  in Z_q[X] / (X^N + 1).

@@ -46,9 +46,10 @@ OPT_RNS_LAUNCH, OPT_DOT_FUSED, OPT_MAX_BATCH_HINT, OPT_CTL_ALLOCATIONS, OPT_ONE_
 OPT_RESCALE_FUSED = 17
 OPT_MODUP_FUSED = 18
 OPT_PAIR_FUSED = 19
+OPT_MODDOWN_ADD_FUSED = 20
 RESCALE_TRANSFORMED, RESCALE_FLOOR = 1, 2
 MODUP_TRANSFORMED = 1
-MODDOWN_TRANSFORMED, MODDOWN_FLOOR = 1, 2
+MODDOWN_TRANSFORMED, MODDOWN_FLOOR, MODDOWN_ACCUMULATE = 1, 2, 4
 GALOIS_TRANSFORMED, GALOIS_ACCUMULATE, GALOIS_KEY_BROADCAST = 1, 2, 4
 
 #: every symbol include/ntt_mi355x.h and the reference-named headers declare
@@ -66,6 +67,7 @@ EXPORTED_SYMBOLS = [
     "ntt_rns_mod_up_mul_batch", "ntt_rns_mod_up_mul_batch_strided",
     "ntt_rns_fwd_mul_pair_batch", "ntt_rns_fwd_mul_pair_batch_strided", "ntt_rns_mod_up_mul_pair_batch", "ntt_rns_mod_up_mul_pair_batch_strided",
     "ntt_rns_galois_dot_pair_batch", "ntt_rns_galois_dot_pair_batch_strided",
+    "ntt_rns_tensor_batch", "ntt_rns_tensor_batch_strided", "ntt_rns_mod_down_add_batch", "ntt_rns_mod_down_add_batch_strided",
     "ntt_galois_rotation", "ntt_galois_batch", "ntt_rns_galois_batch", "ntt_rns_galois_batch_strided", "ntt_rns_galois_dot_batch",
     "ntt_rns_galois_dot_batch_strided",
     "ntt_transform_batch_strided", "ntt_transform_ptrs", "ntt_rns_transform_ptrs", "ntt_transform_dev_ptrs", "ntt_rns_transform_dev_ptrs", "ntt_inv_dot_dev_ptrs", "ntt_fwd_mul_dev_ptrs", "ntt_negacyclic_mul_dev_ptrs",
@@ -164,6 +166,12 @@ _sig("ntt_rns_galois_dot_pair_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP,
      C.POINTER(VOIDP), C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_galois_dot_pair_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_int, C.POINTER(VOIDP), C.POINTER(VOIDP),
      C.POINTER(VOIDP), C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_tensor_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, VOIDP, VOIDP, VOIDP, VOIDP, VOIDP, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_tensor_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, VOIDP, VOIDP, VOIDP, VOIDP, VOIDP, C.c_uint64, C.c_uint64,
+     C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_mod_down_add_batch", C.c_int, C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_mod_down_add_batch_strided", C.c_int, C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint64,
+     C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_galois_rotation", C.c_uint64, C.c_uint64, C.c_int64)
 _sig("ntt_galois_batch", C.c_int, VOIDP, VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_galois_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
@@ -616,6 +624,28 @@ def rns_mod_down(plans, np_, dptr, batch, flags=0, stream=None, layout=None):
     if layout:
         _check(_lib.ntt_rns_mod_down_batch_strided(nq, np_, _plan_array(plans), dptr, layout[0], layout[1], batch, flags, stream))
     else: _check(_lib.ntt_rns_mod_down_batch(nq, np_, _plan_array(plans), dptr, batch, flags, stream))
+
+
+def rns_tensor(plans, dc0, dc1, dc2, da0, da1, db0, db1, batch, flags=0, stream=None, layout=None):
+    """the ciphertext tensor product per limb and word: c0 = a0 b0, c1 = a0 b1 + a1 b0, c2 = a1 b1, canonical (MUL_LAZY_IN: input words
+    in [0, 4q)); db0 == da0 and db1 == da1 is a squaring (every input word loaded once); an output may be an input; all operands laid
+    out [limb][batch][N], layout = (limb_stride, poly_stride) in words otherwise"""
+    if layout:
+        _check(_lib.ntt_rns_tensor_batch_strided(len(plans), _plan_array(plans), dc0, dc1, dc2, da0, da1, db0, db1, layout[0], layout[1],
+                                                 batch, flags, stream))
+    else: _check(_lib.ntt_rns_tensor_batch(len(plans), _plan_array(plans), dc0, dc1, dc2, da0, da1, db0, db1, batch, flags, stream))
+
+
+def rns_mod_down_add(plans, np_, dc, da, batch, flags=0, stream=None, layout=None):
+    """ModDown of the accumulator da (over Q u P, the last np_ plans are P) into the ciphertext dc (over Q): c = ModDown(a), or
+    c += ModDown(a) with MODDOWN_ACCUMULATE; MODDOWN_TRANSFORMED / MODDOWN_FLOOR as rns_mod_down.  da's Q limbs are scratch afterwards
+    (untouched where the fused kernel serves every run: OPT_MODDOWN_ADD_FUSED on plans[0]).  dc is [nq][batch][N] and da
+    [nq + np_][batch][N]; layout = (c_limb_stride, c_poly_stride, a_limb_stride, a_poly_stride) in words otherwise"""
+    nq = len(plans) - np_
+    if layout:
+        _check(_lib.ntt_rns_mod_down_add_batch_strided(nq, np_, _plan_array(plans), dc, da, layout[0], layout[1], layout[2], layout[3],
+                                                       batch, flags, stream))
+    else: _check(_lib.ntt_rns_mod_down_add_batch(nq, np_, _plan_array(plans), dc, da, batch, flags, stream))
 
 
 def galois_rotation(n, steps):

@@ -23,6 +23,7 @@
 #include "ntt_passplan.h"
 #include "ntt_galois.h"
 #include "ntt_keyswitch.h"
+#include "ntt_ct_mul.h"
 #include "ntt_rescale.h"
 #include "ntt_tables.h"
 
@@ -139,5 +140,6 @@ static int check_device(int device)
 #include "host/host_galois.inc"
 #include "host/host_modup_mul.inc"
 #include "host/host_key_pair.inc"
+#include "host/host_ct_mul.inc"
 #include "host/host_runtime.inc"
 #include "host/host_compat.inc"
