@@ -488,6 +488,57 @@ NTT_API int ntt_rns_mod_down_add_batch_strided(int nq, int np, ntt_plan *const *
                                                uint64_t c_poly_stride, uint64_t a_limb_stride, uint64_t a_poly_stride, uint64_t batch,
                                                unsigned flags, void *stream);
 
+/* ---- Exact RNS base conversion and scaled ModDown: what BFV multiplication (Halevi, Polyakov, Shoup) needs beyond the approximate
+ * conversions above, which leave x + u B and round(x / P) - v.  For a basis B = {b_i} of n <= 16 primes, b^_i = B / b_i and
+ * z_i = [x_i b^_i^-1]_{b_i}:
+ *     ExactBConv_{B->q}(x) = ( sum_i z_i [b^_i]_q  -  v [B]_q ) mod q,      v = rint(s),
+ *     s = ((fl(z_0) rho_0 + fl(z_1) rho_1) + ...) left to right,            rho_i = 1.0 / (double)b_i,
+ * every operation one IEEE double operation rounded to nearest (no fused multiply-add), rint to even.  The FP64 error of s is below
+ * 2^-44 (at most 2^-51 per term, 2^-49 per sum of a partial sum below 16; n <= 16), so for x in [0, B) with |2x - B| > 2^-43 B the
+ * result is the CENTRED representative of x -- x below B / 2, x - B above -- reduced mod q; inside that band it is x or x - B, the
+ * same choice in every destination limb of the call (v depends on the source words only).
+ * ntt_rns_mod_up_exact_batch: ntt_rns_mod_up_batch with ExactBConv_{digit->q_l} for FastBConv: the same operand, layouts, in-place
+ * rule, 1 <= count <= 16, flag (NTT_MODUP_TRANSFORMED only), routes (coefficients: one launch per 16 destination limbs, 8N(count + ndst)
+ * bytes per polynomial; NTT domain: the inverse of the digit, those launches, the forward of every limb) and refusals.
+ * ntt_rns_mod_down_exact_batch: the operand of ntt_rns_mod_down_batch (plans[0 .. nq-1] kept, plans[nq .. nq+np-1] divided out,
+ * 1 <= np <= 16) and a multiplier 1 <= mult < 2^61, reduced per prime on the host.  With t the P limbs' coefficients,
+ *     c_l <- ( mult c_l - ExactBConv_{P->q_l}([mult t]_P) ) P^-1  mod q_l,
+ * which for the x in [0, QP) behind the operand is round(mult x / P) mod Q exactly (P is odd: no ties; floor or ceiling inside the band
+ * above, taken for [mult x]_P).  With BFV's Q as the divided-out basis and mult = t this is BFV's scaling round(t x / Q); mult = 1 is an exact ModDown.  The multiplier costs
+ * nothing in the conversion (it is folded into [mult b^_j^-1]_{p_j}) and one more modular product per word at the end.  Flags:
+ * NTT_MODDOWN_TRANSFORMED only.  The P slots follow ModDown's rule (coefficients after a TRANSFORMED call, unchanged otherwise).
+ * Routes: coefficients -- one launch per 16 Q limbs, 8N(2nq + np) bytes per polynomial; NTT domain -- the inverse of the P limbs, then per
+ * run of compatible Q limbs: FP64 policies at N = 2^6..2^14 -- ONE launch of the forward block kernel with the exact conversion in its
+ * prologue (the FP64 sum beside the 128-bit sum of every word) and (c^ [mult]_q - x) P^-1 in its epilogue: 8N np + 16N bytes per Q
+ * limb-polynomial, as for ntt_rns_mod_down_batch; anything else (integer-policy limbs, N < 2^6, N >= 2^15: no fused kernel is built for
+ * those) -- the sandwich of the inverse, the coefficient launch and the forward.  NTT_OPT_RESCALE_FUSED on plans[0] selects the route as
+ * for ntt_rns_mod_down_batch (0: the sandwich everywhere), under the rule recorded in profiles/r15/exact_bench.txt:
+ *     fused wherever the kernel is built, for np <= 4; the sandwich for np >= 5.
+ * (The fused kernel redoes the conversion in every Q limb's workgroup.  Call rate of the fused route over its own sandwich, 24 50-bit Q
+ * limbs, mult 65537, 2 / 64 / 1024 polynomials, ranges over five rounds of alternating processes, 2^13 then 2^14: np 1: 1.12-1.14 /
+ * 1.78-1.80 / 1.85-1.86, 1.17-1.19 / 1.64-1.65 / 1.51-1.52; np 2: 0.98-0.99 / 1.55-1.57 / 1.57-1.58, 1.03-1.06 / 1.41-1.42 / 1.26; np 4:
+ * 0.79-0.80 / 1.26-1.29 / 1.23, 0.84-0.85 / 1.12-1.13 / 0.97-0.98; np 8: 0.58-0.60 / 0.95-0.97 / 0.89-0.90, 0.63 / 0.84 / 0.72-0.73: slower
+ * at both 64 and 1024 polynomials at np 8 only; np 5..7 were not measured and go with 8.  Over the parent commit's approximate
+ * ntt_rns_mod_down_batch at the same shape, parent's own spread 1.00-1.03: fused np 1: 0.66-0.75 -- the approximate call has the rescale's
+ * one-prime path, the exact one the general path --, np 2 / 4: 0.91-0.97 at 2 and 64 polynomials, 0.95-1.03 at 1024.  The exact ModUp in
+ * coefficients over the parent's ntt_rns_mod_up_batch, 24 limbs, count 1 / 4 / 8: 0.91-0.98 at 2 polynomials, 0.79-0.86 / 0.84-0.89 /
+ * 0.89-0.95 at 64 and 1024 (spread 1.00-1.05): the correction costs 5-21 %.  The four-call sequence below, 16 / 256 multiplications at
+ * 2^13 and 2^14, over the same sequence from the parent's approximate calls plus the multiplication by t with torch integer ops:
+ * 1.36-1.47 x, one multiplication 1.21-1.29 x (spread 1.01-1.05).)
+ * NTT_ERR_ARG, nothing written: everything the approximate call refuses, mult == 0 or mult >= 2^61, NTT_MODDOWN_FLOOR,
+ * NTT_MODDOWN_ACCUMULATE, any other flag.  All four: allocate nothing (ntt_plan_reserve covers the transforms they issue), do not
+ * synchronise the host, issue no memset: capturable.
+ * A BFV tensor-and-scale over buffers [R limbs][Q limbs] (R FIRST, so that the ModDown keeps it): exact ModUp of the operands Q -> R,
+ * ntt_rns_tensor_batch over all limbs, ntt_rns_mod_down_exact_batch(nr, nq, mult = t), exact ModUp R -> Q (examples/rns_bfv_mul.c). ---- */
+NTT_API int ntt_rns_mod_up_exact_batch(int nlimbs, ntt_plan *const *plans, uint64_t *d_a, int first, int count, uint64_t batch,
+                                       unsigned flags, void *stream);
+NTT_API int ntt_rns_mod_up_exact_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_a, int first, int count,
+                                               uint64_t limb_stride, uint64_t poly_stride, uint64_t batch, unsigned flags, void *stream);
+NTT_API int ntt_rns_mod_down_exact_batch(int nq, int np, ntt_plan *const *plans, uint64_t *d_a, uint64_t mult, uint64_t batch,
+                                         unsigned flags, void *stream);
+NTT_API int ntt_rns_mod_down_exact_batch_strided(int nq, int np, ntt_plan *const *plans, uint64_t *d_a, uint64_t mult,
+                                                 uint64_t limb_stride, uint64_t poly_stride, uint64_t batch, unsigned flags, void *stream);
+
 /* ---- Galois automorphisms (rotation, conjugation) and the rotation key product.  For odd g, 0 < g < 2N,
  *     sigma_g(a)(X) = a(X^g)  in Z_q[X] / (X^N + 1).
  * g = 5^steps mod 2N rotates the CKKS / BGV slots by `steps` (ntt_galois_rotation; negative steps: the inverse power),

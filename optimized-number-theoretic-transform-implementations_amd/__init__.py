@@ -68,6 +68,7 @@ EXPORTED_SYMBOLS = [
     "ntt_rns_fwd_mul_pair_batch", "ntt_rns_fwd_mul_pair_batch_strided", "ntt_rns_mod_up_mul_pair_batch", "ntt_rns_mod_up_mul_pair_batch_strided",
     "ntt_rns_galois_dot_pair_batch", "ntt_rns_galois_dot_pair_batch_strided",
     "ntt_rns_tensor_batch", "ntt_rns_tensor_batch_strided", "ntt_rns_mod_down_add_batch", "ntt_rns_mod_down_add_batch_strided",
+    "ntt_rns_mod_up_exact_batch", "ntt_rns_mod_up_exact_batch_strided", "ntt_rns_mod_down_exact_batch", "ntt_rns_mod_down_exact_batch_strided",
     "ntt_galois_rotation", "ntt_galois_batch", "ntt_rns_galois_batch", "ntt_rns_galois_batch_strided", "ntt_rns_galois_dot_batch",
     "ntt_rns_galois_dot_batch_strided",
     "ntt_transform_batch_strided", "ntt_transform_ptrs", "ntt_rns_transform_ptrs", "ntt_transform_dev_ptrs", "ntt_rns_transform_dev_ptrs", "ntt_inv_dot_dev_ptrs", "ntt_fwd_mul_dev_ptrs", "ntt_negacyclic_mul_dev_ptrs",
@@ -172,6 +173,12 @@ _sig("ntt_rns_tensor_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, 
 _sig("ntt_rns_mod_down_add_batch", C.c_int, C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_mod_down_add_batch_strided", C.c_int, C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint64,
      C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_mod_up_exact_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_int, C.c_int, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_mod_up_exact_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64,
+     C.c_uint, VOIDP)
+_sig("ntt_rns_mod_down_exact_batch", C.c_int, C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_mod_down_exact_batch_strided", C.c_int, C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+     C.c_uint, VOIDP)
 _sig("ntt_galois_rotation", C.c_uint64, C.c_uint64, C.c_int64)
 _sig("ntt_galois_batch", C.c_int, VOIDP, VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_galois_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
@@ -646,6 +653,24 @@ def rns_mod_down_add(plans, np_, dc, da, batch, flags=0, stream=None, layout=Non
         _check(_lib.ntt_rns_mod_down_add_batch_strided(nq, np_, _plan_array(plans), dc, da, layout[0], layout[1], layout[2], layout[3],
                                                        batch, flags, stream))
     else: _check(_lib.ntt_rns_mod_down_add_batch(nq, np_, _plan_array(plans), dc, da, batch, flags, stream))
+
+
+def rns_mod_up_exact(plans, dptr, first, count, batch, flags=0, stream=None, layout=None):
+    """exact ModUp in place: every limb outside the digit [first, first + count) of plans gets the CENTRED value of the digit (x, or
+    x - B from B / 2 on: the HPS floating-point correction of FastBConv); flags and layout as rns_mod_up"""
+    if layout:
+        _check(_lib.ntt_rns_mod_up_exact_batch_strided(len(plans), _plan_array(plans), dptr, first, count, layout[0], layout[1], batch,
+                                                       flags, stream))
+    else: _check(_lib.ntt_rns_mod_up_exact_batch(len(plans), _plan_array(plans), dptr, first, count, batch, flags, stream))
+
+
+def rns_mod_down_exact(plans, np_, dptr, mult, batch, flags=0, stream=None, layout=None):
+    """exact scaled ModDown in place: the last np_ plans are P; the Q limbs become round(mult * x / P) exactly (1 <= mult < 2^61; BFV's
+    round(t x / Q) with mult = t), in the NTT domain with MODDOWN_TRANSFORMED (the only flag); layout as rns_mod_down"""
+    nq = len(plans) - np_
+    if layout:
+        _check(_lib.ntt_rns_mod_down_exact_batch_strided(nq, np_, _plan_array(plans), dptr, mult, layout[0], layout[1], batch, flags, stream))
+    else: _check(_lib.ntt_rns_mod_down_exact_batch(nq, np_, _plan_array(plans), dptr, mult, batch, flags, stream))
 
 
 def galois_rotation(n, steps):
