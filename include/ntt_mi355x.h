@@ -141,6 +141,13 @@ typedef enum ntt_option {
                           * 16 limbs; NTT_OPT_RESCALE_FUSED keeps selecting that route); -1 (default) = the fused kernel where the
                           * recorded measurement says it is not slower (the rule is quoted at ntt_rns_mod_down_add_batch).  Read from
                           * plans[0]; results are identical */
+  NTT_OPT_BGV_FUSED = 21, /* ntt_rns_mod_down_bgv_batch, ntt_rns_mod_down_bgv_add_batch in the NTT domain: 1 = every run of Q limbs the
+                          * fused kernel is built for (FP64 policies, N = 2^6..2^14) takes it, at any np <= 16: one forward-transform
+                          * launch with the BGV conversion in its prologue; 0 = every run takes the sandwich (inverse, the coefficient
+                          * launch, forward; the add form then one element-wise launch per 16 limbs); -1 (default) = the fused kernel
+                          * where the recorded measurement says it is not slower (the rule is quoted at ntt_rns_mod_down_bgv_batch).
+                          * Read from plans[0]; results are identical.  NTT_OPT_RESCALE_FUSED and NTT_OPT_MODDOWN_ADD_FUSED keep their
+                          * meaning for the other calls; the BGV calls do not read them */
   NTT_OPT_FUSED_PRODUCT = 5 /* N = 2^8..2^17, FP64: 1 (default) = ntt_negacyclic_mul_batch as ONE launch that takes both
                           * operands through the forward stages, multiplies in registers and runs the inverse: 24N bytes up to
                           * 2^14; from 2^23 coefficients per operand of N >= 2^15 on likewise one launch (all limbs of an RNS set
@@ -538,6 +545,64 @@ NTT_API int ntt_rns_mod_down_exact_batch(int nq, int np, ntt_plan *const *plans,
                                          unsigned flags, void *stream);
 NTT_API int ntt_rns_mod_down_exact_batch_strided(int nq, int np, ntt_plan *const *plans, uint64_t *d_a, uint64_t mult,
                                                  uint64_t limb_stride, uint64_t poly_stride, uint64_t batch, unsigned flags, void *stream);
+
+/* ---- BGV modulus switching: ModDown that keeps the plaintext mod T.  The tensor, the approximate ModUp, the key products and the
+ * Galois calls above are scheme-agnostic (for BGV the ModUp overshoot u D cancels mod QP and the key noise is T e); what BGV needs
+ * beyond them is a division by primes whose correction is = x mod P and = 0 mod T -- ntt_rns_rescale_batch and ntt_rns_mod_down_batch
+ * subtract [x]_P, which scrambles the plaintext, and ntt_rns_mod_down_exact_batch's one multiplier cannot express [T^-1]_{p_j}.
+ * Operand as for ntt_rns_mod_down_batch: plans[0 .. nq-1] kept (Q), plans[nq .. nq+np-1] divided out (P), 1 <= np <= 16, product P,
+ * p^_j = P / p_j, h = (P - 1) / 2; a plaintext modulus 1 <= t < 2^61 that no P prime divides (it need not be coprime to the kept primes:
+ * [t]_{q_l} = 0 is legal).  With t_j the coefficients of P limb j:
+ *     z_j = [ ( t_j [t^-1]_{p_j} + [h]_{p_j} ) [p^_j^-1]_{p_j} ]_{p_j}         canonical, [h]_{p_j} = (p_j - 1) / 2
+ *     F_l = ( sum_j z_j [p^_j]_{q_l} ) mod q_l                                 the exact integer sum, reduced once
+ *     c_l <- ( c_l - [t]_{q_l} (F_l - [h]_{q_l}) ) [P^-1]_{q_l}  mod q_l       canonical
+ * Every output word is unique: all intermediates are canonical residues, so the routes below agree bit for bit.  For the x in [0, QP)
+ * behind the operand, w the centred residue of x t^-1 mod P and y = (x - t w) / P (an integer, y = x P^-1 mod t), the Q limbs hold
+ * y - v t mod Q with ONE integer 0 <= v < np for all limbs (v = 0 for np = 1): the deviation is a multiple of t, the plaintext is
+ * untouched and the noise grows by at most (np - 1) t.  THE CALLER OWNS THE FACTOR P^-1 mod t that the plaintext picks up: choose
+ * primes = 1 mod t, or track a correction factor per ciphertext.  t = 1 gives ntt_rns_mod_down_batch's words, word for word.
+ * ntt_rns_mod_down_bgv_batch: in place on d_a ([nq + np][batch][N]; _strided: the strides of ntt_rns_mod_down_batch).  np = 1 is BGV's
+ * modulus switch by the last prime, np > 1 drops several levels at once.  Flags: NTT_MODDOWN_TRANSFORMED only.
+ * ntt_rns_mod_down_bgv_add_batch: into a ciphertext d_c over the nq Q limbs with strides of its own, exactly as
+ * ntt_rns_mod_down_add_batch: c_l = r_l, or c_l = (c_l + r_l) mod q_l with NTT_MODDOWN_ACCUMULATE (c canonical on entry), r_l what the
+ * in-place form leaves in Q limb l of a copy of d_a -- the last step of a BGV relinearisation or rotation.  Flags:
+ * NTT_MODDOWN_TRANSFORMED, NTT_MODDOWN_ACCUMULATE.  Afterwards d_a's Q limbs are scratch (not written where the fused kernel serves
+ * every run).  Both: the P slots hold coefficients after a TRANSFORMED call and are unchanged otherwise; NTT_MODDOWN_FLOOR is refused
+ * (the correction is centred).
+ * Routes.  Coefficients: ntt_rns_mod_down_batch's coefficient kernel with the constants folded on the host ([h t]_{p_j},
+ * [t^-1 p^_j^-1]_{p_j}, [t p^_j]_{q_l}, [t h]_{q_l}), one launch per 16 Q limbs, the P limbs read once per launch, np = 1 on the general
+ * path; the add form then one element-wise launch per 16 limbs.  NTT domain: the inverse of the P limbs, then per run of compatible Q
+ * limbs: FP64 policies at N = 2^6..2^14 -- ONE launch of the forward block kernel (moddown_bgv_fwd_kernel, one template for both forms)
+ * with the conversion in its prologue: [t]_{q_l} is multiplied into the np table entries [p^_j]_{q_l} and into [h]_{q_l} once per
+ * workgroup, so the per-word work is that of ntt_rns_mod_down_add_batch's kernel (np = 1: no table, one more Shoup product per word);
+ * anything else (integer-policy limbs, N < 2^6, N >= 2^15) -- the sandwich of the inverse, the coefficient launch and the forward.
+ * NTT_OPT_BGV_FUSED on plans[0]: 1 / 0 force the fused kernel (where built, any np) / the sandwich for every run; the default, -1,
+ * applies the rule recorded in profiles/r16/bgv_bench.txt:
+ *     in place: fused for np <= 4 up to N = 2^13 and for np <= 2 at 2^14; into a ciphertext: fused for np <= 4; the sandwich beyond.
+ * (The fused kernel redoes the conversion in every Q limb's workgroup, the sandwich once per 16 Q limbs.  Call rate of the fused route
+ * over its own sandwich, 24 50-bit Q limbs, T = 65537, 64 / 1024 polynomials, ranges over five rounds of alternating processes, 2^13
+ * then 2^14.  In place: np 1: 1.99-2.08 / 2.19-2.21, 1.86-1.93 / 1.87-1.88; np 2: 1.56-1.57 / 1.42-1.43, 1.40-1.42 / 1.26; np 4:
+ * 1.26-1.27 / 1.11, 1.13-1.14 / 0.98; np 8: 0.97 / 0.82-0.83, 0.88 / 0.73-0.74.  Add form: np 1: 2.25-2.32 / 2.54-2.56, 1.86-1.93 /
+ * 2.26-2.27; np 2: 1.78-1.81 / 1.65-1.68, 1.48-1.50 / 1.54-1.55; np 4: 1.46-1.48 / 1.30-1.32, 1.23-1.24 / 1.21-1.22; np 8: 1.11-1.12 /
+ * 0.97, 0.95 / 0.89.  The default takes the fused kernel for exactly those np at which it is not slower at both 64 and 1024
+ * polynomials; np 3 goes with 4 and 5..7 with 8, sizes below 2^13 with 2^13.  At 2 polynomials the fused kernel reads 1.27-1.47 at
+ * np 1, 1.00-1.16 at np 2, 0.82-0.94 at np 4.  Cost of the correction, fused over the parent commit's approximate
+ * ntt_rns_mod_down_batch / ntt_rns_mod_down_add_batch at the same shape, parent's own spread 1.00-1.06: np 2, 4, 8: 0.95-1.04 at every
+ * batch size; np 1: 0.81-0.92 -- the approximate calls have the rescale's one-prime path, which skips the source product and the
+ * product by [t]_q.)
+ * NTT_ERR_ARG, nothing written: everything ntt_rns_mod_down_batch / ntt_rns_mod_down_add_batch refuse, t == 0, t >= 2^61, a P prime that
+ * divides t, NTT_MODDOWN_FLOOR, NTT_MODDOWN_ACCUMULATE in the in-place form, any other flag.  All four: allocate nothing
+ * (ntt_plan_reserve covers the transforms they issue), do not synchronise the host, issue no memset: capturable.
+ * A BGV multiplication with relinearisation and one modulus switch through public calls: examples/rns_bgv_mul.c. ---- */
+NTT_API int ntt_rns_mod_down_bgv_batch(int nq, int np, ntt_plan *const *plans, uint64_t *d_a, uint64_t t, uint64_t batch, unsigned flags,
+                                       void *stream);
+NTT_API int ntt_rns_mod_down_bgv_batch_strided(int nq, int np, ntt_plan *const *plans, uint64_t *d_a, uint64_t t, uint64_t limb_stride,
+                                               uint64_t poly_stride, uint64_t batch, unsigned flags, void *stream);
+NTT_API int ntt_rns_mod_down_bgv_add_batch(int nq, int np, ntt_plan *const *plans, uint64_t *d_c, uint64_t *d_a, uint64_t t, uint64_t batch,
+                                           unsigned flags, void *stream);
+NTT_API int ntt_rns_mod_down_bgv_add_batch_strided(int nq, int np, ntt_plan *const *plans, uint64_t *d_c, uint64_t *d_a, uint64_t t,
+                                                   uint64_t c_limb_stride, uint64_t c_poly_stride, uint64_t a_limb_stride,
+                                                   uint64_t a_poly_stride, uint64_t batch, unsigned flags, void *stream);
 
 /* ---- Galois automorphisms (rotation, conjugation) and the rotation key product.  For odd g, 0 < g < 2N,
  *     sigma_g(a)(X) = a(X^g)  in Z_q[X] / (X^N + 1).

@@ -47,6 +47,7 @@ OPT_RESCALE_FUSED = 17
 OPT_MODUP_FUSED = 18
 OPT_PAIR_FUSED = 19
 OPT_MODDOWN_ADD_FUSED = 20
+OPT_BGV_FUSED = 21
 RESCALE_TRANSFORMED, RESCALE_FLOOR = 1, 2
 MODUP_TRANSFORMED = 1
 MODDOWN_TRANSFORMED, MODDOWN_FLOOR, MODDOWN_ACCUMULATE = 1, 2, 4
@@ -69,6 +70,7 @@ EXPORTED_SYMBOLS = [
     "ntt_rns_galois_dot_pair_batch", "ntt_rns_galois_dot_pair_batch_strided",
     "ntt_rns_tensor_batch", "ntt_rns_tensor_batch_strided", "ntt_rns_mod_down_add_batch", "ntt_rns_mod_down_add_batch_strided",
     "ntt_rns_mod_up_exact_batch", "ntt_rns_mod_up_exact_batch_strided", "ntt_rns_mod_down_exact_batch", "ntt_rns_mod_down_exact_batch_strided",
+    "ntt_rns_mod_down_bgv_batch", "ntt_rns_mod_down_bgv_batch_strided", "ntt_rns_mod_down_bgv_add_batch", "ntt_rns_mod_down_bgv_add_batch_strided",
     "ntt_galois_rotation", "ntt_galois_batch", "ntt_rns_galois_batch", "ntt_rns_galois_batch_strided", "ntt_rns_galois_dot_batch",
     "ntt_rns_galois_dot_batch_strided",
     "ntt_transform_batch_strided", "ntt_transform_ptrs", "ntt_rns_transform_ptrs", "ntt_transform_dev_ptrs", "ntt_rns_transform_dev_ptrs", "ntt_inv_dot_dev_ptrs", "ntt_fwd_mul_dev_ptrs", "ntt_negacyclic_mul_dev_ptrs",
@@ -179,6 +181,12 @@ _sig("ntt_rns_mod_up_exact_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), V
 _sig("ntt_rns_mod_down_exact_batch", C.c_int, C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_mod_down_exact_batch_strided", C.c_int, C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
      C.c_uint, VOIDP)
+_sig("ntt_rns_mod_down_bgv_batch", C.c_int, C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_mod_down_bgv_batch_strided", C.c_int, C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+     C.c_uint, VOIDP)
+_sig("ntt_rns_mod_down_bgv_add_batch", C.c_int, C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_mod_down_bgv_add_batch_strided", C.c_int, C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint64,
+     C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_galois_rotation", C.c_uint64, C.c_uint64, C.c_int64)
 _sig("ntt_galois_batch", C.c_int, VOIDP, VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_galois_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
@@ -671,6 +679,27 @@ def rns_mod_down_exact(plans, np_, dptr, mult, batch, flags=0, stream=None, layo
     if layout:
         _check(_lib.ntt_rns_mod_down_exact_batch_strided(nq, np_, _plan_array(plans), dptr, mult, layout[0], layout[1], batch, flags, stream))
     else: _check(_lib.ntt_rns_mod_down_exact_batch(nq, np_, _plan_array(plans), dptr, mult, batch, flags, stream))
+
+
+def rns_mod_down_bgv(plans, np_, dptr, t, batch, flags=0, stream=None, layout=None):
+    """BGV ModDown in place: the last np_ plans are P; the Q limbs become (x - t w) / P - v t, w the centred residue of x t^-1 mod P,
+    0 <= v < np_: the plaintext mod t is multiplied by P^-1 mod t and nothing else (1 <= t < 2^61, no P prime divides t).  np_ = 1 is
+    BGV's modulus switch.  MODDOWN_TRANSFORMED is the only flag; layout as rns_mod_down; OPT_BGV_FUSED on plans[0] selects the route"""
+    nq = len(plans) - np_
+    if layout:
+        _check(_lib.ntt_rns_mod_down_bgv_batch_strided(nq, np_, _plan_array(plans), dptr, t, layout[0], layout[1], batch, flags, stream))
+    else: _check(_lib.ntt_rns_mod_down_bgv_batch(nq, np_, _plan_array(plans), dptr, t, batch, flags, stream))
+
+
+def rns_mod_down_bgv_add(plans, np_, dc, da, t, batch, flags=0, stream=None, layout=None):
+    """BGV ModDown of the accumulator da (over Q u P) into the ciphertext dc (over Q): c = ModDown_t(a), or c += ModDown_t(a) with
+    MODDOWN_ACCUMULATE (the last step of a BGV relinearisation or rotation); operands and layout as rns_mod_down_add, t as
+    rns_mod_down_bgv.  da's Q limbs are scratch afterwards (untouched where the fused kernel serves every run)"""
+    nq = len(plans) - np_
+    if layout:
+        _check(_lib.ntt_rns_mod_down_bgv_add_batch_strided(nq, np_, _plan_array(plans), dc, da, t, layout[0], layout[1], layout[2], layout[3],
+                                                           batch, flags, stream))
+    else: _check(_lib.ntt_rns_mod_down_bgv_add_batch(nq, np_, _plan_array(plans), dc, da, t, batch, flags, stream))
 
 
 def galois_rotation(n, steps):

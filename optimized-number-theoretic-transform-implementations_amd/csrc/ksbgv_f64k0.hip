@@ -1,0 +1,6 @@
+/* ksbgv_f64k0.hip -- instantiates the BGV ModDown kernels (moddown_bgv_fwd_kernel, N = 2^6..2^14) for (ArithF64, headroom class 0). */
+#include "ntt_kernels_bgv.h"
+
+namespace ntt {
+NTT_DEFINE_LAUNCH_MODDOWN_BGV_FWD(ArithF64, 0)
+} /* namespace ntt */
