@@ -662,6 +662,63 @@ NTT_API int ntt_rns_galois_dot_pair_batch_strided(int nlimbs, ntt_plan *const *p
                                                   const uint64_t *const *d_key1hat, uint64_t g, uint64_t limb_stride, uint64_t poly_stride,
                                                   uint64_t batch, unsigned flags, void *stream);
 
+/* ---- the linear layer: linear combinations of RNS operands with a Galois map and a multiplier per term.
+ * ntt_rns_lincomb_batch: per limb l, polynomial p and storage slot s (m = log2 N),
+ *     c[l,p,s] = ( [ACCUMULATE: c[l,p,s]] + bias_l + sum_{i<k} a_i[l,p,src_{g_i}(s)] * mu_i(l,p,s) ) mod q_l,   canonical,
+ *     mu_i     = m_i[l,p,s]  (m_i[l,s] with NTT_LINCOMB_M_BROADCAST)   if d_m && d_m[i]
+ *              = s_{i,l} = h_s[i * nlimbs + l]                         otherwise (h_s NULL: 1)
+ *     src_g(s) = bitrev_m((g bitrev_m(s) + (g - 1) / 2) mod N)         (the NTT-domain map of ntt_rns_galois_batch; g = 1: s).
+ * In the NTT domain (bit-reversed storage, as ntt_fwd_batch leaves it) this is c (+)= bias + sum_i sigma_{g_i}(a_i) * mu_i; the
+ * multiplier is read unpermuted, as the key of ntt_rns_galois_dot_batch.  With every g = 1 the call is element-wise and serves
+ * either domain.  The bias is added to EVERY word: it is the constant polynomial bias_l only in the NTT domain (in coefficients a
+ * constant is one word, position 0).
+ * d_a and d_m are HOST arrays of k device pointers (entries of d_m may be NULL, and d_m itself); h_s ([k][nlimbs], read only where
+ * term i has no polynomial multiplier), h_g (k Galois elements, NULL: all 1) and h_bias (nlimbs words, NULL: none) are host arrays,
+ * copied into the launch: they may be reused as soon as the call returns.  Every operand is in the call's layout ([limb][batch][N];
+ * _strided: any strides the other RNS forms accept), except that with NTT_LINCOMB_M_BROADCAST every polynomial multiplier is ONE
+ * polynomial per limb ([limb][N]) shared by the batch.
+ * The sum is the exact integer in 128 bits, reduced once, then one conditional subtraction: every output word is the one canonical
+ * residue.  1 <= k <= 16 with canonical inputs (16 (2^61)^2 + 2^61 + 2^61 < 2^127).  With NTT_LINCOMB_LAZY_IN the a_i words may lie
+ * anywhere in [0, 4q) (< 2^63; ntt_fwd_batch_lazy's words), the multipliers, scalars, bias and c stay canonical, and 1 <= k <= 8
+ * (8 2^63 2^61 = 2^127).
+ * One launch per 16 limbs, integer arithmetic for every policy and every N >= 2; NTT_OPT_MAX_GRID of plans[0] is honoured.  Allocates
+ * nothing, does not synchronise the host, issues no memset: capturable.
+ * d_c may be the same pointer as an a_i with g_i = 1, or as an m_i in c's layout (not a broadcast one): every thread reads all its
+ * words before it stores its own position.  Any other overlap between d_c's span of words under the layout (first word to last) and
+ * an input's is refused, an a_i with g_i != 1 that is d_c included; inputs may overlap each other.
+ * NTT_ERR_ARG, nothing written: nlimbs < 1; k out of range for the flags; a null d_c, d_a or d_a[i]; a g_i that is even, 0 or >= 2N;
+ * a scalar that is read, or a bias, not below its q_l; plans that differ in N or device; an unknown flag; NTT_LINCOMB_M_BROADCAST
+ * without a polynomial multiplier; strides under which two (limb, polynomial) ranges overlap; the overlaps above.
+ * Bytes moved per limb and polynomial: 8N(k + n_m + 1) for n_m polynomial multipliers, 8N(k + 1) with broadcast multipliers, 8N
+ * more when accumulating.  Recipes (everything not named is NULL / 0; q_l the limb's prime):
+ *     add          c = a + b            k = 2, d_a = {a, b}                                         24N
+ *     sub          c = a - b            k = 2, h_s = {1.., (q_l - 1)..}                             24N
+ *     negate       c = -a               k = 1, h_s = {(q_l - 1)..}                                  16N
+ *     scale        c = w a              k = 1, h_s = {[w]_q_l..}                                    16N
+ *     axpy         c += w a             k = 1, h_s = {[w]_q_l..}, ACCUMULATE                        24N
+ *     add constant c = a + w            k = 1, h_bias = {[w]_q_l..}        (NTT domain)             16N
+ *     polynomial   c = sum w_i ct_i + w_0   k terms, h_s, h_bias                                    8N(k + 1)
+ *     plaintext multiply-accumulate  c += pt (.) a     k = 1, d_m = {pt}, ACCUMULATE                32N (24N: M_BROADCAST)
+ *     hoisted transform   c0 = sum_i pt_i (.) sigma_{g_i}(a)   d_a = {a..}, d_m = {pt_i}, h_g = {g_i}, M_BROADCAST   8N(k + 1)
+ *     inner sum    c = sum_i sigma_{g_i}(a)                    d_a = {a..}, h_g = {g_i}                              8N(k + 1)
+ * (a listed k times is read k times through different permutations: the count is of requests, most of them served on chip.)
+ * Measured: 24 x 50-bit limbs, 2^13 / 2^14, ranges over five rounds of alternating processes (profiles/r17/lincomb_bench.txt; the parent's own spread
+ * 1.00-1.05 at 64 and 1024 polynomials).  The addition runs at 0.87-0.88 of ntt_copy_probe's rate at the same bytes at 1024 polynomials
+ * (0.72-0.83 at 64), the 4-term scalar combination with bias at 0.89-0.93; against torch integer ops beside the parent commit's library
+ * 2.16-2.97 x and 2.58-3.14 x.  sum_i pt_i (.) sigma_{g_i}(a), broadcast multipliers, distinct g: 2.18-2.27 x (k = 3) and 3.27-3.55 x (k = 8)
+ * k accumulating ntt_rns_galois_dot_batch calls of the parent; all g equal, against ONE such call: 0.95-1.15 x at k = 3, 0.86-1.00 x at
+ * k = 8 (1.00 at 1024 polynomials).  2 polynomials are launch-bound.  The addition's ratio lies inside the tensor kernel's 0.86-0.92, so no
+ * +-1 specialisation (additions with conditional subtractions) was built: one general kernel ships. ---- */
+enum { NTT_LINCOMB_ACCUMULATE = 1,   /* c += ... (c canonical on entry) */
+       NTT_LINCOMB_M_BROADCAST = 2,  /* every polynomial multiplier is ONE polynomial per limb ([limb][N]) shared by the batch */
+       NTT_LINCOMB_LAZY_IN = 4       /* a_i words anywhere in [0, 4q) */ };
+NTT_API int ntt_rns_lincomb_batch(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, int k, const uint64_t *const *d_a,
+                                  const uint64_t *const *d_m, const uint64_t *h_s, const uint64_t *h_g, const uint64_t *h_bias,
+                                  uint64_t batch, unsigned flags, void *stream);
+NTT_API int ntt_rns_lincomb_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, int k, const uint64_t *const *d_a,
+                                          const uint64_t *const *d_m, const uint64_t *h_s, const uint64_t *h_g, const uint64_t *h_bias,
+                                          uint64_t limb_stride, uint64_t poly_stride, uint64_t batch, unsigned flags, void *stream);
+
 /* ---- caller-native layouts (round 5).  The entry points above take RNS operands as [limb][batch][N].  SURVEY 8(d) config 5
  * -- and every FHE library -- keeps a polynomial's limbs side by side: [batch][prime][N].  The *_strided forms take the two
  * distances in WORDS instead of assuming either:

@@ -52,6 +52,7 @@ RESCALE_TRANSFORMED, RESCALE_FLOOR = 1, 2
 MODUP_TRANSFORMED = 1
 MODDOWN_TRANSFORMED, MODDOWN_FLOOR, MODDOWN_ACCUMULATE = 1, 2, 4
 GALOIS_TRANSFORMED, GALOIS_ACCUMULATE, GALOIS_KEY_BROADCAST = 1, 2, 4
+LINCOMB_ACCUMULATE, LINCOMB_M_BROADCAST, LINCOMB_LAZY_IN = 1, 2, 4
 
 #: every symbol include/ntt_mi355x.h and the reference-named headers declare
 EXPORTED_SYMBOLS = [
@@ -72,7 +73,7 @@ EXPORTED_SYMBOLS = [
     "ntt_rns_mod_up_exact_batch", "ntt_rns_mod_up_exact_batch_strided", "ntt_rns_mod_down_exact_batch", "ntt_rns_mod_down_exact_batch_strided",
     "ntt_rns_mod_down_bgv_batch", "ntt_rns_mod_down_bgv_batch_strided", "ntt_rns_mod_down_bgv_add_batch", "ntt_rns_mod_down_bgv_add_batch_strided",
     "ntt_galois_rotation", "ntt_galois_batch", "ntt_rns_galois_batch", "ntt_rns_galois_batch_strided", "ntt_rns_galois_dot_batch",
-    "ntt_rns_galois_dot_batch_strided",
+    "ntt_rns_galois_dot_batch_strided", "ntt_rns_lincomb_batch", "ntt_rns_lincomb_batch_strided",
     "ntt_transform_batch_strided", "ntt_transform_ptrs", "ntt_rns_transform_ptrs", "ntt_transform_dev_ptrs", "ntt_rns_transform_dev_ptrs", "ntt_inv_dot_dev_ptrs", "ntt_fwd_mul_dev_ptrs", "ntt_negacyclic_mul_dev_ptrs",
     "ntt_rns_inv_dot_dev_ptrs", "ntt_rns_fwd_mul_dev_ptrs", "ntt_rns_negacyclic_mul_dev_ptrs", "ntt_dev_malloc", "ntt_dev_free", "ntt_dev_mem_info",
     "ntt_h2d", "ntt_d2h", "ntt_stream_create", "ntt_stream_destroy", "ntt_stream_sync",
@@ -195,6 +196,10 @@ _sig("ntt_rns_galois_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, 
 _sig("ntt_rns_galois_dot_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_int, C.POINTER(VOIDP), C.POINTER(VOIDP), C.c_uint64,
      C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_galois_dot_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_int, C.POINTER(VOIDP), C.POINTER(VOIDP), C.c_uint64,
+     C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_lincomb_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_int, C.POINTER(VOIDP), C.POINTER(VOIDP), U64P, U64P, U64P,
+     C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_lincomb_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_int, C.POINTER(VOIDP), C.POINTER(VOIDP), U64P, U64P, U64P,
      C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_transform_batch_strided", C.c_int, VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_transform_ptrs", C.c_int, VOIDP, C.POINTER(VOIDP), C.c_uint64, C.c_uint, VOIDP)
@@ -740,6 +745,48 @@ def rns_galois_dot_pair(plans, dc0, dc1, dahats, dkey0hats, dkey1hats, g, batch,
     else:
         _check(_lib.ntt_rns_galois_dot_pair_batch(len(plans), _plan_array(plans), dc0, dc1, k, arrs[0], arrs[1], arrs[2], g, batch, flags,
                                                   stream))
+
+
+def rns_lincomb(plans, dc, das, dms=None, scalars=None, gs=None, bias=None, batch=1, flags=0, stream=None, layout=None):
+    """c (+)= bias + sum_i sigma_{g_i}(a_i) * mu_i per limb and word, mu_i the polynomial dms[i] or, where that is None, the per-limb
+    scalars[i][l] (None: 1).  gs: one Galois element per term (None: 1), bias: one constant per limb (None: 0).  LINCOMB_ACCUMULATE:
+    c += ...; LINCOMB_M_BROADCAST: every polynomial multiplier is [limb][N], shared by the batch; LINCOMB_LAZY_IN: a_i words in [0, 4q)"""
+    k, nl = len(das), len(plans)
+    a = (VOIDP * k)(*das)
+    m = None
+    if dms is not None:
+        assert len(dms) == k
+        m = (VOIDP * k)(*dms)
+    s = None
+    if scalars is not None:
+        assert len(scalars) == k and all(len(row) == nl for row in scalars)
+        s = (C.c_uint64 * (k * nl))(*[int(v) for row in scalars for v in row])
+    g = None
+    if gs is not None:
+        assert len(gs) == k
+        g = (C.c_uint64 * k)(*gs)
+    b = None
+    if bias is not None:
+        assert len(bias) == nl
+        b = (C.c_uint64 * nl)(*bias)
+    if layout:
+        _check(_lib.ntt_rns_lincomb_batch_strided(nl, _plan_array(plans), dc, k, a, m, s, g, b, layout[0], layout[1], batch, flags, stream))
+    else: _check(_lib.ntt_rns_lincomb_batch(nl, _plan_array(plans), dc, k, a, m, s, g, b, batch, flags, stream))
+
+
+def rns_add(plans, dc, da, db, batch, stream=None, layout=None):
+    """c = a + b per limb and word (either domain); c may be a or b"""
+    rns_lincomb(plans, dc, [da, db], batch=batch, stream=stream, layout=layout)
+
+
+def rns_sub(plans, dc, da, db, batch, stream=None, layout=None):
+    """c = a - b per limb and word (either domain); c may be a or b"""
+    rns_lincomb(plans, dc, [da, db], scalars=[[1] * len(plans), [p.q - 1 for p in plans]], batch=batch, stream=stream, layout=layout)
+
+
+def rns_neg(plans, dc, da, batch, stream=None, layout=None):
+    """c = -a per limb and word (either domain); c may be a"""
+    rns_lincomb(plans, dc, [da], scalars=[[p.q - 1 for p in plans]], batch=batch, stream=stream, layout=layout)
 
 
 def batch_multi(plans, dptrs, batches, inverse=False):

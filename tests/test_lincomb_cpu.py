@@ -1,0 +1,217 @@
+"""CPU: the RNS linear combination (ntt_rns_lincomb_batch) without a GPU -- the model of tests/lincomb_model.py against its meaning in
+coefficients (sigma_g by galois_model.coef_model, the oracle's forward transform, a schoolbook negacyclic product for the polynomial
+multipliers), its two routes against each other, the host side of csrc/ntt_lincomb.h under the address and undefined-behaviour
+sanitizers against 128-bit integers and the model (tests/lincomb_host_check.cpp), the exported symbols, the flags, the plain-C example
+against the public header alone and the kernel of the new translation unit."""
+import glob
+import os
+import random
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import galois_model as gm
+import lincomb_model as lm
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_amd")
+CSRC = os.path.join(PKG, "csrc")
+LIB = os.path.join(PKG, "libntt_mi355x.so")
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+SYMBOLS = {"ntt_rns_lincomb_batch", "ntt_rns_lincomb_batch_strided"}
+
+
+def _primes(orc, n):
+    primes = [orc.find_prime(30, n), orc.find_prime(60, n)]
+    return primes, [orc.min_root(q, n) for q in primes]
+
+
+def _gs(n):
+    return [g % (2 * n) for g in (1, 5, 2 * n - 1, 25)]
+
+
+# ---------------------------------------------------------------- the model against its meaning
+
+@pytest.mark.parametrize("n", [64, 256])
+def test_scalar_terms_are_the_transform_of_the_combination_in_coefficients(oracle, n):
+    """fwd(bias + sum_i s_i sigma_{g_i}(a_i)), formed in coefficients, is what the model gives on the transformed operands -- with a
+    different g per term, accumulating and not"""
+    primes, roots = _primes(oracle, n)
+    gs = _gs(n)
+    k, batch = len(gs), 3
+    scalars, bias = lm.distinct_scalars(primes, k, n)
+    for flags in (0, lm.ACCUMULATE):
+        for l, (q, w) in enumerate(zip(primes, roots)):
+            cx = oracle.ctx(n, q, w)
+            coef = [oracle.fill_uniform(batch * n, q, 10 * i + l) for i in range(k)]
+            c_coef = oracle.fill_uniform(batch * n, q, 99 + l)
+            want = np.zeros(batch * n, dtype=object)
+            want.reshape(batch, n)[:, 0] = bias[l]  # the constant polynomial
+            if flags:
+                want = want + c_coef.astype(object)
+            for i in range(k):
+                want = want + gm.coef_model(coef[i], n, gs[i], q).astype(object) * scalars[i][l]
+            want = cx.fwd((want % q).astype(np.uint64))
+            got = lm.limb_model(cx.fwd(c_coef), [cx.fwd(a) for a in coef], [None] * k, [scalars[i][l] for i in range(k)], gs, bias[l], n, q, flags)
+            assert np.array_equal(got, want), (n, q, flags)
+
+
+@pytest.mark.parametrize("n", [64, 256])
+@pytest.mark.parametrize("bcast", [False, True])
+def test_polynomial_multipliers_are_schoolbook_products(oracle, n, bcast):
+    """sum_i pt_i * sigma_{g_i}(a_i) with negacyclic schoolbook products in coefficients, transformed, is what the model gives on the
+    transformed operands and multipliers (the multiplier read unpermuted)"""
+    primes, roots = _primes(oracle, n)
+    gs = _gs(n)
+    k, batch = len(gs), 2
+    flags = lm.M_BROADCAST if bcast else 0
+    for l, (q, w) in enumerate(zip(primes, roots)):
+        cx = oracle.ctx(n, q, w)
+        coef = [oracle.fill_uniform(batch * n, q, 10 * i + l) for i in range(k)]
+        pt = [oracle.fill_uniform(n if bcast else batch * n, q, 10 * i + 5 + l) for i in range(k)]
+        want = np.zeros(batch * n, dtype=np.uint64)
+        for i in range(k):
+            s = gm.coef_model(coef[i], n, gs[i], q)
+            for p in range(batch):
+                mp = pt[i] if bcast else pt[i][p * n:(p + 1) * n]
+                prod = oracle.schoolbook(np.ascontiguousarray(s[p * n:(p + 1) * n]), np.ascontiguousarray(mp), n, q)
+                want[p * n:(p + 1) * n] = (want[p * n:(p + 1) * n] + prod) % np.uint64(q)
+        got = lm.limb_model(None, [cx.fwd(a) for a in coef], [cx.fwd(m) for m in pt], [0] * k, gs, 0, n, q, flags)
+        assert np.array_equal(got, cx.fwd(want)), (n, q, bcast)
+
+
+@pytest.mark.parametrize("flags", [0, lm.ACCUMULATE, lm.M_BROADCAST, lm.LAZY_IN | lm.ACCUMULATE])
+def test_the_two_routes_of_the_model_agree(oracle, flags):
+    """the Python-integer definition and the route through the oracle's modular product (used for the large GPU shapes), on random
+    words and on the extremes"""
+    n, batch = 64, 3
+    primes, _ = _primes(oracle, n)
+    lazy = bool(flags & lm.LAZY_IN)
+    k = 8 if lazy else 16
+    gs = [(5 ** i) % (2 * n) for i in range(k)]
+    scalars, bias = lm.distinct_scalars(primes, k, 3)
+    for fill in (None, "top"):
+        for l, q in enumerate(primes):
+            top = 4 * q if lazy else q
+            a = [oracle.fill_uniform(batch * n, top, 10 * i + l) if fill is None else np.full(batch * n, top - 1, dtype=np.uint64) for i in range(k)]
+            m = [None if i % 3 else (oracle.fill_uniform(n if flags & lm.M_BROADCAST else batch * n, q, 7 * i + l) if fill is None else
+                                     np.full(n if flags & lm.M_BROADCAST else batch * n, q - 1, dtype=np.uint64)) for i in range(k)]
+            c = oracle.fill_uniform(batch * n, q, 77) if fill is None else np.full(batch * n, q - 1, dtype=np.uint64)
+            s = [scalars[i][l] if fill is None else q - 1 for i in range(k)]
+            b = bias[l] if fill is None else q - 1
+            assert np.array_equal(lm.limb_model(c, a, m, s, gs, b, n, q, flags), lm.limb_fast(oracle, c, a, m, s, gs, b, n, q, flags)), (q, fill)
+
+
+# ---------------------------------------------------------------- the host side of csrc/ntt_lincomb.h
+
+@pytest.fixture(scope="module")
+def host_check():
+    exe = os.path.join(ROOT, "build", "lincomb_host_check")
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    # host code only, every sanitizer flag bound to the host side: nothing is built for the GPU
+    flags = "--cuda-host-only -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=all"
+    subprocess.check_call([hipcc] + flags.split() + ["-I" + CSRC, os.path.join(ROOT, "tests", "lincomb_host_check.cpp"), "-o", exe])
+    return exe
+
+
+def _host_rows(host_check, tmp_path, primes, k, rows):
+    """rows[r][l] = (c, bias, [x_i], [mu_i]); the program's words as [row][limb]"""
+    path = os.path.join(str(tmp_path), "vec.txt")
+    with open(path, "w") as f:
+        f.write("%d %d %d\n%s\n" % (len(primes), k, len(rows), " ".join(map(str, primes))))
+        for row in rows:
+            f.write(" ".join(" ".join(map(str, [c, b] + list(x) + list(mu))) for c, b, x, mu in row) + "\n")
+    r = subprocess.run([host_check, path], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-500:] + r.stderr[-3000:]
+    return [[int(v) for v in line.split()] for line in r.stdout.splitlines()]
+
+
+def _model_rows(primes, k, rows, lazy):
+    """the same words from lincomb_model.limb_model: the rows are the slots of one polynomial, every g = 1, every multiplier a polynomial"""
+    n = len(rows)
+    out = []
+    for l, q in enumerate(primes):
+        c = np.array([row[l][0] for row in rows], dtype=np.uint64)
+        assert len({row[l][1] for row in rows}) == 1
+        a = [np.array([row[l][2][i] for row in rows], dtype=np.uint64) for i in range(k)]
+        m = [np.array([row[l][3][i] for row in rows], dtype=np.uint64) for i in range(k)]
+        out.append(lm.limb_model(c, a, m, [0] * k, [1] * k, rows[0][l][1], n, q, lm.ACCUMULATE | (lm.LAZY_IN if lazy else 0)))
+    return out
+
+
+@pytest.mark.parametrize("k,lazy", [(16, False), (8, True), (1, False), (5, True)], ids=["k16", "k8_lazy", "k1", "k5_lazy"])
+def test_host_statement_equals_int128_and_the_model(oracle, host_check, tmp_path, k, lazy):
+    """lincomb_word of csrc/ntt_lincomb.h, compiled for the host with the sanitizers: the overflow corners (every word at its maximum,
+    c and the bias at q - 1, q the largest prime below 2^61 that serves N = 64 beside a 30-, a 50- and a 52-bit one) and random draws;
+    the program compares with 128-bit integers, this test its output with the model"""
+    n = 64
+    primes = [oracle.find_prime(61, n), oracle.find_prime(60, n), oracle.find_prime(30, n), oracle.find_prime(50, n), oracle.find_prime(52, n)]
+    assert all(q < 1 << 61 for q in primes) and primes[0] > (1 << 61) - (1 << 40)
+    rng = random.Random(k + 100 * lazy)
+    for bias_of in (lambda q: q - 1, lambda q: 0, lambda q: rng.randrange(q)):
+        biases = [bias_of(q) for q in primes]
+        rows = []
+        for r in range(n):
+            row = []
+            for q, b in zip(primes, biases):
+                top = 4 * q if lazy else q
+                if r == 0:    # the overflow corner
+                    row.append((q - 1, b, [top - 1] * k, [q - 1] * k))
+                elif r == 1:  # all zero
+                    row.append((0, b, [0] * k, [0] * k))
+                else:
+                    row.append((rng.randrange(q), b, [rng.randrange(top) for _ in range(k)], [rng.randrange(q) for _ in range(k)]))
+            rows.append(row)
+        got = _host_rows(host_check, tmp_path, primes, k, rows)
+        want = _model_rows(primes, k, rows, lazy)
+        for l in range(len(primes)):
+            assert [row[l] for row in got] == want[l].tolist(), (l, biases[l])
+
+
+# ---------------------------------------------------------------- build checks
+
+def test_exports_the_two_symbols(lib):
+    out = subprocess.check_output(["nm", "-D", "--defined-only", lib.LIB_PATH], text=True)
+    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert SYMBOLS <= names, SYMBOLS - names
+    assert SYMBOLS <= set(lib.EXPORTED_SYMBOLS)
+    assert all(callable(f) for f in (lib.rns_lincomb, lib.rns_add, lib.rns_sub, lib.rns_neg))
+
+
+def test_header_declares_the_flags_as_c_and_cxx(lib):
+    header = open(os.path.join(ROOT, "include", "ntt_mi355x.h")).read()
+    for name, val in (("NTT_LINCOMB_ACCUMULATE", 1), ("NTT_LINCOMB_M_BROADCAST", 2), ("NTT_LINCOMB_LAZY_IN", 4)):
+        assert re.search(r"%s\s*=\s*%d\b" % (name, val), header)
+    assert (lib.LINCOMB_ACCUMULATE, lib.LINCOMB_M_BROADCAST, lib.LINCOMB_LAZY_IN) == (1, 2, 4)
+    for comp, std, lang in (("gcc", "-std=gnu11", "c"), ("g++", "-std=c++17", "c++")):
+        src = ('#include "ntt_mi355x.h"\nint main(void){return (NTT_LINCOMB_ACCUMULATE == 1 && NTT_LINCOMB_M_BROADCAST == 2 && NTT_LINCOMB_LAZY_IN == 4 && '
+               "ntt_rns_lincomb_batch && ntt_rns_lincomb_batch_strided) ? 0 : 1;}\n")
+        subprocess.run([comp, std, "-Wall", "-Wextra", "-Werror", "-Wno-address", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), "-x", lang, "-"],
+                       input=src, text=True, check=True)
+
+
+def test_example_builds_against_the_public_header(lib):
+    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
+    exe = os.path.join(ROOT, "build", "rns_lincomb")
+    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "examples", "rns_lincomb.c"), "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x",
+                           "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
+    assert os.path.exists(exe)
+
+
+def test_new_object_holds_one_kernel_without_spills():
+    """lincomb.o (or, where the objects are not at hand, the linked library): exactly lincomb_kernel, no spilled register, no scratch,
+    no LDS (the kernel-argument record's size is a static_assert of lincomb.hip)"""
+    import check_spills
+    import kernel_inventory
+    objs = glob.glob(os.path.join(CSRC, "lincomb.o"))
+    ks = check_spills.kernels_of(objs[0]) if objs else [k for k in check_spills.kernels_of(LIB) if "lincomb" in k["name"]]
+    names = [kernel_inventory.normalise(d) for d in kernel_inventory.demangle([k["name"] for k in ks])]
+    assert names == ["lincomb_kernel"], names
+    k = ks[0]
+    assert not k.get("vgpr_spill_count", 0) and not k.get("private_segment_fixed_size", 0) and not k.get("group_segment_fixed_size", 0), k
+    assert "static_assert(sizeof(KLincomb) < 4096" in open(os.path.join(CSRC, "lincomb.hip")).read()
