@@ -24,7 +24,7 @@ OBJS     = $(CSRC)/inst_f64k0.o $(CSRC)/inst_f64k1.o $(CSRC)/inst_f64k18.o $(CSR
            $(CSRC)/ksfold_f64k0.o $(CSRC)/ksfold_f64k1.o $(CSRC)/ksfold_f64k18.o $(CSRC)/ksfold_f64w.o \
            $(CSRC)/ksexact_f64k0.o $(CSRC)/ksexact_f64k1.o $(CSRC)/ksexact_f64k18.o $(CSRC)/ksexact_f64w.o \
            $(CSRC)/ksbgv_f64k0.o $(CSRC)/ksbgv_f64k1.o $(CSRC)/ksbgv_f64k18.o $(CSRC)/ksbgv_f64w.o \
-           $(CSRC)/galois_coef.o $(CSRC)/keypair_dot2.o $(CSRC)/ct_elem.o $(CSRC)/exact_coef.o $(CSRC)/lincomb.o \
+           $(CSRC)/galois_coef.o $(CSRC)/keypair_dot2.o $(CSRC)/ct_elem.o $(CSRC)/exact_coef.o $(CSRC)/lincomb.o $(CSRC)/plain.o \
            $(CSRC)/ntt_host.o
 # the kernel translation units see the kernel headers only; the host layer also the public headers
 KHDRS    = $(wildcard $(CSRC)/*.h)

@@ -719,6 +719,61 @@ NTT_API int ntt_rns_lincomb_batch_strided(int nlimbs, ntt_plan *const *plans, ui
                                           const uint64_t *const *d_m, const uint64_t *h_s, const uint64_t *h_g, const uint64_t *h_bias,
                                           uint64_t limb_stride, uint64_t poly_stride, uint64_t batch, unsigned flags, void *stream);
 
+/* ---- out of the RNS: the last step of a decryption.  d_a holds nlimbs limbs in COEFFICIENTS, canonical ([limb][batch][N]); x in
+ * [0, Q) is the integer behind the nlimbs words of one coefficient, Q = prod q_l, x_c its centred representative (x, or x - Q from
+ * Q / 2 on).  Every q_l < 2^61, the primes pairwise distinct.
+ *
+ * ntt_rns_to_plain_batch: d_m ([batch][N]) receives one word in [0, t) per coefficient, 1 <= nlimbs <= 16, 2 <= t < 2^61, t ANY
+ * integer (powers of two and composites included):
+ *     flags = 0 (BGV)          m = [x_c]_t.  The exact base conversion of ntt_rns_mod_up_exact_batch with t for the destination
+ *                              prime; nothing has to be coprime.  Exact for |2x - Q| > 2^-43 Q; inside that band [x]_t or [x - Q]_t.
+ *     NTT_PLAIN_SCALE (BFV)    m = round(t x / Q) mod t; every q_l coprime to t.  Q is odd: no ties.  With rho = t x mod Q exact for
+ *                              |2 rho - Q| > 2^-43 Q; inside that band one of the two neighbouring integers (mod t).
+ * The band is that of the exact conversions: one FP64 sum of at most 16 terms below 1 decides the rounding, with an error below
+ * 2^-44.  A decryption's noise keeps x (rho) far from Q / 2 -- it is where decryption fails anyway.  The FP64 operations and their
+ * order are fixed (csrc/ntt_plain.h), so the result is a function of the input words alone, on every device and in the tests' model.
+ *
+ * ntt_rns_to_double_batch: d_y ([batch][N] doubles) receives y = fl(x_c) * scale, nlimbs 1 or 2 (Q < 2^122: where CKKS decrypts): fl
+ * is the round-to-nearest-even conversion of the exact signed integer -- one rounding, also above 2^64 --, then one IEEE product.
+ * No band: the two-limb reconstruction is exact in 128 bits.  x_c = 0 gives +0.0 * scale.  What follows is the decoding FFT.
+ *
+ * _strided: the source's limbs a_limb_stride and polynomials a_poly_stride words apart (any strides the other RNS forms accept), the
+ * output's polynomials m_poly_stride (y_poly_stride) >= N words apart.
+ * The output may be d_a itself -- limb 0's slots, with the source's polynomial stride: every thread reads all its words before its
+ * one store.  Any other overlap between the output's span of words (first to last) and the source's is the caller's error, refused.
+ * ONE launch per call, integer and FP64 arithmetic of its own for every policy and every N >= 2; NTT_OPT_MAX_GRID of plans[0] is
+ * honoured.  Allocates nothing, does not synchronise the host, issues no memset: capturable.  8N(nlimbs + 1) bytes per polynomial.
+ * NTT_ERR_ARG, nothing written: nlimbs outside 1..16 (to_double: 1..2); plans that differ in N or device; a prime >= 2^61 or listed
+ * twice; t < 2 or t >= 2^61; NTT_PLAIN_SCALE with a prime that divides t; any other flag; a null d_m / d_y or d_a with batch > 0;
+ * strides under which two (limb, polynomial) ranges overlap, or an output stride below N; the overlap above.
+ *
+ * Decryption is two calls.  With the secret key s^ and the constant polynomial 1^ (every word 1) in the NTT domain, [limb][N], and the
+ * ciphertext (c0^, c1^) in the NTT domain, the phase c0 + c1 s in coefficients is
+ *     ntt_rns_inv_dot_batch(L, plans, d_x, 2, {c0^, c1^}, {1^, s^}, batch, NTT_MUL_B_BROADCAST, stream)
+ * and then
+ *     BFV    ntt_rns_to_plain_batch(L, plans, d_m, d_x, t, batch, NTT_PLAIN_SCALE, stream)      m = round(t [c0 + c1 s]_Q / Q) mod t
+ *     BGV    ntt_rns_to_plain_batch(L, plans, d_m, d_x, t, batch, 0, stream)                    m = [[c0 + c1 s]_Q centred]_t
+ *     CKKS   ntt_rns_to_double_batch(L <= 2, plans, d_y, d_x, 1 / Delta, batch, stream)         y = [c0 + c1 s]_Q centred / Delta
+ * (examples/rns_decrypt.c).  A ciphertext held in coefficients takes ntt_rns_negacyclic_mul_batch and an addition instead of the dot.
+ * Measured (profiles/r18/plain_bench.txt: 50-bit primes, t = 65537, 2^13 / 2^14, ranges over five rounds of alternating processes; the
+ * parent's own spread 1.00-1.03): at 1024 polynomials the call runs at 0.49-0.52 (L = 1), 0.63-0.75 (L = 4) and 0.74-0.80 (L = 16) of
+ * ntt_copy_probe's rate at the same bytes, both modes alike (0.39-0.76 at 64 polynomials, 5-36 us calls) -- below the 0.86-0.92 of the
+ * other element-wise kernels: the waves spend 72-75 % of their cycles issuing or stalled at issue and 25-28 % waiting for memory (the
+ * probe: 96 %), about 57 vector instructions per limb and 114 per output word, nearly all of them the 64-bit integer products.  Against
+ * the detour the parent commit can express (exact ModUp onto an auxiliary prime, exact ModDown with mult = t, a centred reduction with
+ * torch integer ops) the SCALE mode is 8.2-8.9 x (L = 1), 3.7-6.2 x (L = 4) and 2.2-3.6 x (L = 16) faster. ---- */
+enum { NTT_PLAIN_SCALE = 1 /* m = round(t x / Q) mod t (BFV) instead of [x_c]_t (BGV) */ };
+NTT_API int ntt_rns_to_plain_batch(int nlimbs, ntt_plan *const *plans, uint64_t *d_m, const uint64_t *d_a, uint64_t t, uint64_t batch,
+                                   unsigned flags, void *stream);
+NTT_API int ntt_rns_to_plain_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_m, const uint64_t *d_a, uint64_t t,
+                                           uint64_t a_limb_stride, uint64_t a_poly_stride, uint64_t m_poly_stride, uint64_t batch,
+                                           unsigned flags, void *stream);
+NTT_API int ntt_rns_to_double_batch(int nlimbs, ntt_plan *const *plans, double *d_y, const uint64_t *d_a, double scale, uint64_t batch,
+                                    void *stream);
+NTT_API int ntt_rns_to_double_batch_strided(int nlimbs, ntt_plan *const *plans, double *d_y, const uint64_t *d_a, double scale,
+                                            uint64_t a_limb_stride, uint64_t a_poly_stride, uint64_t y_poly_stride, uint64_t batch,
+                                            void *stream);
+
 /* ---- caller-native layouts (round 5).  The entry points above take RNS operands as [limb][batch][N].  SURVEY 8(d) config 5
  * -- and every FHE library -- keeps a polynomial's limbs side by side: [batch][prime][N].  The *_strided forms take the two
  * distances in WORDS instead of assuming either:

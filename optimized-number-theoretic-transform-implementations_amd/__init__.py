@@ -53,6 +53,7 @@ MODUP_TRANSFORMED = 1
 MODDOWN_TRANSFORMED, MODDOWN_FLOOR, MODDOWN_ACCUMULATE = 1, 2, 4
 GALOIS_TRANSFORMED, GALOIS_ACCUMULATE, GALOIS_KEY_BROADCAST = 1, 2, 4
 LINCOMB_ACCUMULATE, LINCOMB_M_BROADCAST, LINCOMB_LAZY_IN = 1, 2, 4
+PLAIN_SCALE = 1
 
 #: every symbol include/ntt_mi355x.h and the reference-named headers declare
 EXPORTED_SYMBOLS = [
@@ -74,6 +75,7 @@ EXPORTED_SYMBOLS = [
     "ntt_rns_mod_down_bgv_batch", "ntt_rns_mod_down_bgv_batch_strided", "ntt_rns_mod_down_bgv_add_batch", "ntt_rns_mod_down_bgv_add_batch_strided",
     "ntt_galois_rotation", "ntt_galois_batch", "ntt_rns_galois_batch", "ntt_rns_galois_batch_strided", "ntt_rns_galois_dot_batch",
     "ntt_rns_galois_dot_batch_strided", "ntt_rns_lincomb_batch", "ntt_rns_lincomb_batch_strided",
+    "ntt_rns_to_plain_batch", "ntt_rns_to_plain_batch_strided", "ntt_rns_to_double_batch", "ntt_rns_to_double_batch_strided",
     "ntt_transform_batch_strided", "ntt_transform_ptrs", "ntt_rns_transform_ptrs", "ntt_transform_dev_ptrs", "ntt_rns_transform_dev_ptrs", "ntt_inv_dot_dev_ptrs", "ntt_fwd_mul_dev_ptrs", "ntt_negacyclic_mul_dev_ptrs",
     "ntt_rns_inv_dot_dev_ptrs", "ntt_rns_fwd_mul_dev_ptrs", "ntt_rns_negacyclic_mul_dev_ptrs", "ntt_dev_malloc", "ntt_dev_free", "ntt_dev_mem_info",
     "ntt_h2d", "ntt_d2h", "ntt_stream_create", "ntt_stream_destroy", "ntt_stream_sync",
@@ -201,6 +203,12 @@ _sig("ntt_rns_lincomb_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_int
      C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_lincomb_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_int, C.POINTER(VOIDP), C.POINTER(VOIDP), U64P, U64P, U64P,
      C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_to_plain_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_to_plain_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+     C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_to_double_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_double, C.c_uint64, VOIDP)
+_sig("ntt_rns_to_double_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_double, C.c_uint64, C.c_uint64, C.c_uint64,
+     C.c_uint64, VOIDP)
 _sig("ntt_transform_batch_strided", C.c_int, VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_transform_ptrs", C.c_int, VOIDP, C.POINTER(VOIDP), C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_transform_ptrs", C.c_int, C.c_int, C.POINTER(VOIDP), C.POINTER(VOIDP), C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
@@ -787,6 +795,25 @@ def rns_sub(plans, dc, da, db, batch, stream=None, layout=None):
 def rns_neg(plans, dc, da, batch, stream=None, layout=None):
     """c = -a per limb and word (either domain); c may be a"""
     rns_lincomb(plans, dc, [da], scalars=[[p.q - 1 for p in plans]], batch=batch, stream=stream, layout=layout)
+
+
+def rns_to_plain(plans, dm, da, t, batch, flags=0, stream=None, layout=None):
+    """out of the RNS: dm ([batch][N]) = [x_c]_t of the coefficients da ([limb][batch][N], canonical), x_c the centred representative mod
+    Q (BGV); PLAIN_SCALE: round(t x / Q) mod t (BFV; every prime coprime to t).  2 <= t < 2^61, up to 16 limbs.  layout =
+    (a_limb_stride, a_poly_stride, m_poly_stride) in words for any other placement; dm may be da (limb 0's slots)"""
+    if layout:
+        _check(_lib.ntt_rns_to_plain_batch_strided(len(plans), _plan_array(plans), dm, da, t, layout[0], layout[1], layout[2], batch, flags,
+                                                   stream))
+    else: _check(_lib.ntt_rns_to_plain_batch(len(plans), _plan_array(plans), dm, da, t, batch, flags, stream))
+
+
+def rns_to_double(plans, dy, da, scale, batch, stream=None, layout=None):
+    """out of the RNS: dy ([batch][N] doubles) = fl(x_c) * scale for one or two limbs (CKKS, before the decoding FFT); layout =
+    (a_limb_stride, a_poly_stride, y_poly_stride)"""
+    if layout:
+        _check(_lib.ntt_rns_to_double_batch_strided(len(plans), _plan_array(plans), dy, da, scale, layout[0], layout[1], layout[2], batch,
+                                                    stream))
+    else: _check(_lib.ntt_rns_to_double_batch(len(plans), _plan_array(plans), dy, da, scale, batch, stream))
 
 
 def batch_multi(plans, dptrs, batches, inverse=False):

@@ -27,6 +27,7 @@
 #include "ntt_exact.h"
 #include "ntt_bgv.h"
 #include "ntt_lincomb.h"
+#include "ntt_plain.h"
 #include "ntt_rescale.h"
 #include "ntt_tables.h"
 
@@ -147,5 +148,6 @@ static int check_device(int device)
 #include "host/host_exact.inc"
 #include "host/host_bgv.inc"
 #include "host/host_lincomb.inc"
+#include "host/host_plain.inc"
 #include "host/host_runtime.inc"
 #include "host/host_compat.inc"

@@ -1,0 +1,175 @@
+"""CPU: the conversions out of the RNS (ntt_rns_to_plain_batch, ntt_rns_to_double_batch) without a GPU -- the formula model of
+tests/plain_model.py against the two big-integer definitions (every word outside the band; one of the two neighbours inside it), the
+host side of csrc/ntt_plain.h under the address and undefined-behaviour sanitizers against the model (tests/plain_host_check.cpp, a
+stand-alone program), the exported symbols, the flag, the plain-C example against the public header alone and the kernels of the new
+translation unit."""
+import glob
+import os
+import random
+import re
+import subprocess
+import sys
+from math import prod
+
+import numpy as np
+import pytest
+
+import plain_model as pm
+import rescale_model as rm
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_amd")
+CSRC = os.path.join(PKG, "csrc")
+LIB = os.path.join(PKG, "libntt_mi355x.so")
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+SYMBOLS = {"ntt_rns_to_plain_batch", "ntt_rns_to_plain_batch_strided", "ntt_rns_to_double_batch", "ntt_rns_to_double_batch_strided"}
+TS = [2, 3, 256, 65537, 1 << 32, 1 << 60, (1 << 61) - 1, 1032193, 10 ** 18 + 9]
+CHAINS = {"L1_50": [50], "L2_60": [60, 60], "L3_30": [30] * 3, "L4_mixed": [60, 50, 30, 52], "L9_60": [60] * 9, "L16_60": [60] * 16,
+          "L16_mixed": [60, 50, 30, 50] * 4}
+
+
+# ---------------------------------------------------------------- the model against the definitions
+
+@pytest.mark.parametrize("flags", [0, pm.SCALE], ids=["centred", "scale"])
+@pytest.mark.parametrize("chain", sorted(CHAINS))
+def test_formula_is_the_definition_outside_the_band(lib, chain, flags):
+    """random words (none of which may lie in the band: its share is 2^-42 per word) and the constructed corners, for every t: the
+    formula with its FP64 sum equals the big-integer definition outside the band and is one of the two neighbours inside it"""
+    n = 16
+    primes, _ = rm.chain(lib, n, CHAINS[chain])
+    Q = prod(primes)
+    rng = random.Random(len(primes) * 7 + flags)
+    for t in TS:
+        if flags and any(t % q == 0 for q in primes):
+            continue
+        rand = [rng.randrange(Q) for _ in range(150)]
+        assert not any(pm.in_band(x, Q, t, flags) for x in rand)
+        xs = rand + pm.corner_values(Q, t, flags)
+        got = pm.formula(pm.to_rns(xs, primes), primes, t, flags).tolist()
+        for x, w in zip(xs, got):
+            assert 0 <= w < t
+            if pm.in_band(x, Q, t, flags):
+                assert w in pm.neighbours(x, Q, t, flags), (t, x, w)
+            else:
+                assert w == pm.definition(x, Q, t, flags), (t, x, w)
+
+
+def test_corners_cover_both_sides_of_the_band():
+    """the constructed words contain band words and their nearest outside neighbours' cases: (Q -+ 1) / 2 are inside the band for any
+    Q >= 2^43 and decide differently in the definition"""
+    Q, t = 1152921504606846883 * 1125899906842597, 65537  # any odd Q
+    lo, hi = (Q - 1) // 2, (Q + 1) // 2
+    assert pm.in_band(lo, Q, t) and pm.in_band(hi, Q, t) and not pm.in_band(0, Q, t) and not pm.in_band(Q - 1, Q, t)
+    assert pm.definition(lo, Q, t) == lo % t and pm.definition(hi, Q, t) == (hi - Q) % t
+    assert pm.definition(Q - 1, Q, t) == t - 1 and pm.definition(1, Q, t, pm.SCALE) == 0
+
+
+def test_double_model_rounds_once():
+    """the model of to_double on the constructed values: ties to even at 2^53, one rounding above 2^64, the sign of zero"""
+    primes = [1152921504606846883, 1152921504606846819]  # any two odd coprime moduli below 2^61 (the model is plain CRT)
+    Q = prod(primes)
+    for xc, want in ((2 ** 53 + 1, 2.0 ** 53), (2 ** 53 + 3, 2.0 ** 53 + 4), (-(2 ** 53 + 1), -(2.0 ** 53)), (2 ** 100 + 2 ** 47, 2.0 ** 100),
+                     (2 ** 100 + 2 ** 47 + 1, 2.0 ** 100 + 2.0 ** 48), (0, 0.0)):
+        got = pm.double_model(pm.to_rns([xc % Q], primes), primes, 1.0)
+        assert got.view(np.float64)[0] == want and got[0] == np.float64(want).view(np.uint64), xc
+
+
+# ---------------------------------------------------------------- the host side of csrc/ntt_plain.h
+
+@pytest.fixture(scope="module")
+def host_check():
+    exe = os.path.join(ROOT, "build", "plain_host_check")
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    # host code only, every sanitizer flag bound to the host side: nothing is built for the GPU
+    flags = "--cuda-host-only -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=all"
+    subprocess.check_call([hipcc] + flags.split() + ["-I" + CSRC, os.path.join(ROOT, "tests", "plain_host_check.cpp"), "-o", exe])
+    return exe
+
+
+def _run(host_check, tmp_path, text):
+    path = os.path.join(str(tmp_path), "vec.txt")
+    with open(path, "w") as f:
+        f.write(text)
+    r = subprocess.run([host_check, path], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-500:] + r.stderr[-3000:]
+    return [int(v) for v in r.stdout.split()]
+
+
+@pytest.mark.parametrize("flags", [0, pm.SCALE], ids=["centred", "scale"])
+@pytest.mark.parametrize("t", [(1 << 61) - 1, 2, 1 << 60, 65537])
+def test_host_statement_equals_the_model(lib, host_check, tmp_path, t, flags):
+    """plain_word of csrc/ntt_plain.h, compiled for the host with the sanitizers: 16 limbs of 60-bit primes with every digit
+    z_i = q_i - 1 (the largest 128-bit sum and the largest FP64 sum), every digit 0, the corner words and random draws; the program
+    compares bconv_reduce's word with 128-bit integers, this test its output with the model word for word"""
+    primes, _ = rm.chain(lib, 16, [60] * 16)
+    Q = prod(primes)
+    c, g, _, h = pm.constants(primes, t, flags)
+    rng = random.Random(t % 1000 + flags)
+    top = [(q - 1) * pow(ci, -1, q) % q for q, ci in zip(primes, c)]  # x_i with [x_i c_i]_{q_i} = q_i - 1
+    rows = [top, [0] * 16] + [[x % q for q in primes] for x in pm.corner_values(Q, t, flags) + [rng.randrange(Q) for _ in range(200)]]
+    assert all(xi * ci % q == q - 1 for xi, ci, q in zip(top, c, primes))
+    text = "P %d %d %d %d\n" % (16, t, h, len(rows)) + "".join("%d %d %d\n" % v for v in zip(primes, c, g))
+    text += "".join(" ".join(map(str, r)) + "\n" for r in rows)
+    got = _run(host_check, tmp_path, text)
+    want = pm.formula([np.array(col, dtype=np.uint64) for col in zip(*rows)], primes, t, flags)
+    assert got == want.tolist()
+
+
+@pytest.mark.parametrize("bits", [[60, 60], [30], [60], [50, 30]], ids=["60_60", "30", "60", "50_30"])
+@pytest.mark.parametrize("scale", [2.0 ** -40, 1.0 / 3.0])
+def test_host_double_equals_the_model(lib, host_check, tmp_path, bits, scale):
+    """plain_double on the constructed values (ties at 2^53, a tie and a sticky bit above 2^100, zero, -+(Q - 1) / 2) and random words"""
+    primes, _ = rm.chain(lib, 16, bits)
+    Q = prod(primes)
+    xs = pm.double_values(Q) + [random.Random(len(bits)).randrange(Q) for _ in range(200)]
+    limbs = pm.to_rns(xs, primes)
+    cs = [pow(primes[1], -1, primes[0]), pow(primes[0], -1, primes[1])] if len(primes) == 2 else [0]
+    text = "D %d %d %d\n" % (len(primes), int(np.float64(scale).view(np.uint64)), len(xs)) + "".join("%d %d\n" % v for v in zip(primes, cs))
+    text += "".join(" ".join(str(int(w)) for w in row) + "\n" for row in zip(*limbs))
+    got = _run(host_check, tmp_path, text)
+    assert got == pm.double_model(limbs, primes, scale).tolist()
+
+
+# ---------------------------------------------------------------- build checks
+
+def test_exports_the_four_symbols(lib):
+    out = subprocess.check_output(["nm", "-D", "--defined-only", lib.LIB_PATH], text=True)
+    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert SYMBOLS <= names, SYMBOLS - names
+    assert SYMBOLS <= set(lib.EXPORTED_SYMBOLS)
+    assert callable(lib.rns_to_plain) and callable(lib.rns_to_double)
+
+
+def test_header_declares_the_flag_as_c_and_cxx(lib):
+    header = open(os.path.join(ROOT, "include", "ntt_mi355x.h")).read()
+    assert re.search(r"NTT_PLAIN_SCALE\s*=\s*1\b", header) and lib.PLAIN_SCALE == 1 == pm.SCALE
+    for comp, std, lang in (("gcc", "-std=gnu11", "c"), ("g++", "-std=c++17", "c++")):
+        src = ('#include "ntt_mi355x.h"\nint main(void){return (NTT_PLAIN_SCALE == 1 && ntt_rns_to_plain_batch && ntt_rns_to_plain_batch_strided && '
+               "ntt_rns_to_double_batch && ntt_rns_to_double_batch_strided) ? 0 : 1;}\n")
+        subprocess.run([comp, std, "-Wall", "-Wextra", "-Werror", "-Wno-address", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), "-x", lang, "-"],
+                       input=src, text=True, check=True)
+
+
+def test_example_builds_against_the_public_header(lib):
+    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
+    exe = os.path.join(ROOT, "build", "rns_decrypt")
+    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "examples", "rns_decrypt.c"), "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x",
+                           "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
+    assert os.path.exists(exe)
+
+
+def test_new_object_holds_two_kernels_without_spills():
+    """plain.o (or, where the objects are not at hand, the linked library): exactly plain_kernel and plain_double_kernel, no spilled
+    register, no scratch, no LDS (the kernel-argument record's size is a static_assert of plain.hip)"""
+    import check_spills
+    import kernel_inventory
+    objs = glob.glob(os.path.join(CSRC, "plain.o"))
+    ks = check_spills.kernels_of(objs[0]) if objs else [k for k in check_spills.kernels_of(LIB) if "plain_" in k["name"]]
+    names = sorted(kernel_inventory.normalise(d) for d in kernel_inventory.demangle([k["name"] for k in ks]))
+    assert names == ["plain_double_kernel", "plain_kernel"], names
+    for k in ks:
+        assert not k.get("vgpr_spill_count", 0) and not k.get("sgpr_spill_count", 0) and not k.get("private_segment_fixed_size", 0) \
+            and not k.get("group_segment_fixed_size", 0), k
+    assert "static_assert(sizeof(KPlain) < 4096" in open(os.path.join(CSRC, "plain.hip")).read()
