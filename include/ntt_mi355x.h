@@ -148,6 +148,11 @@ typedef enum ntt_option {
                           * where the recorded measurement says it is not slower (the rule is quoted at ntt_rns_mod_down_bgv_batch).
                           * Read from plans[0]; results are identical.  NTT_OPT_RESCALE_FUSED and NTT_OPT_MODDOWN_ADD_FUSED keep their
                           * meaning for the other calls; the BGV calls do not read them */
+  NTT_OPT_LIFT_FUSED = 22, /* ntt_rns_from_plain_batch, ntt_rns_from_double_batch with NTT_LIFT_TRANSFORMED: 1 = every run of limbs the
+                          * fused kernel is built for (FP64 policies, N = 2^6..2^14) takes it: one forward-transform launch with the
+                          * lift in its prologue; 0 = every run takes the composition (the element-wise launch, then the forward
+                          * transform; accumulating, the inverse transform first); -1 (default) = the rule quoted at
+                          * ntt_rns_from_plain_batch.  Read from plans[0]; results are identical */
   NTT_OPT_FUSED_PRODUCT = 5 /* N = 2^8..2^17, FP64: 1 (default) = ntt_negacyclic_mul_batch as ONE launch that takes both
                           * operands through the forward stages, multiplies in registers and runs the inverse: 24N bytes up to
                           * 2^14; from 2^23 coefficients per operand of N >= 2^15 on likewise one launch (all limbs of an RNS set
@@ -773,6 +778,67 @@ NTT_API int ntt_rns_to_double_batch(int nlimbs, ntt_plan *const *plans, double *
 NTT_API int ntt_rns_to_double_batch_strided(int nlimbs, ntt_plan *const *plans, double *d_y, const uint64_t *d_a, double scale,
                                             uint64_t a_limb_stride, uint64_t a_poly_stride, uint64_t y_poly_stride, uint64_t batch,
                                             void *stream);
+
+/* ---- into the RNS: the first step of an encryption, and every plaintext operand.  One plaintext word per coefficient ([batch][N])
+ * becomes one canonical word per limb in d_c ([limb][batch][N]); any limb count (16 limbs per launch), every q_l < 2^61.  Integer
+ * arithmetic only: every definition fixes every output word, on every route (csrc/ntt_lift.h).
+ *
+ * ntt_rns_from_plain_batch: d_m holds words in [0, t), 2 <= t < 2^61, t ANY integer:
+ *     flags = 0 (BGV; plaintext operands of every scheme; a signed integer v passed as v mod t)
+ *                              c_l = [m_c]_{q_l},  m_c = m for 2m < t, else m - t: the centred representative, in [-ceil(t/2), t/2).
+ *     NTT_LIFT_SCALE (BFV)     c_l = [floor((Q m + floor(t/2)) / t)]_{q_l} = [round(Q m / t)]_{q_l} (ties up), Q the product of the given
+ *                              primes, every prime coprime to t.  It is Delta m + floor((r m + floor(t/2)) / t) with Delta = floor(Q / t)
+ *                              and r = Q mod t: the rounding term that Delta m alone drops.
+ *   A word m >= t is the caller's error: the result word is unspecified, but lies in [0, q_l).
+ * ntt_rns_from_double_batch (CKKS): d_y holds doubles; p = fl(y * scale), one IEEE product; v = rint(p), ties to even; c_l = [v]_{q_l}.
+ *   v = 0 for NaN, +-inf and |p| >= 2^127 (defined, not a precondition); below that the integer is exact in 128 bits.  What precedes
+ *   it is the encoding FFT.
+ * Flags:
+ *     NTT_LIFT_SCALE         from_plain only (see above)
+ *     NTT_LIFT_TRANSFORMED   the output is in the NTT domain, canonical words
+ *     NTT_LIFT_ACCUMULATE    c_l <- c_l + the lift (mod q_l); c canonical and in the domain the call writes
+ * _strided: d_c's limbs c_limb_stride and polynomials c_poly_stride words apart (any strides the other RNS forms accept), the
+ * plaintext's polynomials m_poly_stride (y_poly_stride) >= N words apart.  batch = 1 yields the [limb][N] shape that
+ * NTT_LINCOMB_M_BROADCAST and NTT_MUL_B_BROADCAST read.  Any overlap of the plaintext's span of words with d_c's is refused.
+ * Routes: coefficients -- one element-wise launch per 16 limbs (every policy, every N >= 2, NTT_OPT_MAX_GRID of plans[0] honoured),
+ * 8N(L + 1) bytes per polynomial (8N(2L + 1) accumulating).  NTT_LIFT_TRANSFORMED -- per run of compatible limbs ONE launch of the
+ * forward transform with the lift in its prologue and the addition in its epilogue (FP64 policies, N = 2^6..2^14; the plaintext is
+ * read once per run, nothing else but the output moves), or the composition: the element-wise launch and the run's forward transform
+ * in place; accumulating: the run's inverse transform, the accumulating element-wise launch, the forward transform.  Both give the
+ * same words.  NTT_OPT_LIFT_FUSED on plans[0]: 1 / 0 force the fused kernel (where built) / the composition for every run; the
+ * default, -1, follows the measurement (profiles/r19/lift_bench.txt; the rule with its figures: csrc/host/host_lift.inc): the fused
+ * kernel when accumulating (1.13-2.27 x the composition's rate) and for the centred lift through N = 2^13 (1.06-1.37 x), the
+ * composition otherwise (storing, the scaled and double modes and the centred one at 2^14 are 0.73-0.97 x somewhere).
+ * Allocates nothing, does not synchronise the host, issues no memset: capturable.
+ * NTT_ERR_ARG, nothing written: plans that differ in N or device; a prime >= 2^61; t < 2 or t >= 2^61; NTT_LIFT_SCALE with a prime
+ * that divides t, or on from_double; any other flag; a null d_c or plaintext with batch > 0; strides under which two (limb,
+ * polynomial) ranges overlap, or a plaintext stride below N; the overlap above; NTT_LIFT_TRANSFORMED with a plan that lacks the
+ * forward table (composition with NTT_LIFT_ACCUMULATE: or the inverse table).
+ *
+ * Recipes (Delta = floor(Q / t) for BFV, the scale for CKKS; u, e0, e1 sampled by the caller; pk^ in the NTT domain):
+ *     BFV encrypt    c0^ = pk0^ (.) u^ + e0^ by the products above, then
+ *                    ntt_rns_from_plain_batch(L, plans, d_c0, d_m, t, batch, NTT_LIFT_SCALE | NTT_LIFT_TRANSFORMED | NTT_LIFT_ACCUMULATE, s)
+ *     BGV encrypt    c0^ = pk0^ (.) u^ + t e0^, then from_plain(.., NTT_LIFT_TRANSFORMED | NTT_LIFT_ACCUMULATE, s)
+ *     CKKS encrypt   c0^ likewise, then ntt_rns_from_double_batch(L, plans, d_c0, d_y, Delta, batch, NTT_LIFT_TRANSFORMED | NTT_LIFT_ACCUMULATE, s)
+ *     ct + pt        the same call on c0^ (BFV: NTT_LIFT_SCALE; BGV: none; CKKS: from_double)
+ *     ct (.) pt      pt^ = from_plain(.., batch = 1, NTT_LIFT_TRANSFORMED) into a [limb][N] buffer, then ntt_rns_lincomb_batch with pt^ as
+ *                    a multiplier and NTT_LINCOMB_M_BROADCAST
+ * (examples/rns_encrypt.c). ---- */
+enum {
+  NTT_LIFT_SCALE       = 1, /* from_plain: round(Q m / t) (BFV) instead of the centred [m_c] (BGV, plaintext operands) */
+  NTT_LIFT_TRANSFORMED = 2, /* the output is in the NTT domain */
+  NTT_LIFT_ACCUMULATE  = 4  /* c_l <- c_l + the lift */
+};
+NTT_API int ntt_rns_from_plain_batch(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, const uint64_t *d_m, uint64_t t, uint64_t batch,
+                                     unsigned flags, void *stream);
+NTT_API int ntt_rns_from_plain_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, const uint64_t *d_m, uint64_t t,
+                                             uint64_t c_limb_stride, uint64_t c_poly_stride, uint64_t m_poly_stride, uint64_t batch,
+                                             unsigned flags, void *stream);
+NTT_API int ntt_rns_from_double_batch(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, const double *d_y, double scale, uint64_t batch,
+                                      unsigned flags, void *stream);
+NTT_API int ntt_rns_from_double_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, const double *d_y, double scale,
+                                              uint64_t c_limb_stride, uint64_t c_poly_stride, uint64_t y_poly_stride, uint64_t batch,
+                                              unsigned flags, void *stream);
 
 /* ---- caller-native layouts (round 5).  The entry points above take RNS operands as [limb][batch][N].  SURVEY 8(d) config 5
  * -- and every FHE library -- keeps a polynomial's limbs side by side: [batch][prime][N].  The *_strided forms take the two

@@ -48,12 +48,14 @@ OPT_MODUP_FUSED = 18
 OPT_PAIR_FUSED = 19
 OPT_MODDOWN_ADD_FUSED = 20
 OPT_BGV_FUSED = 21
+OPT_LIFT_FUSED = 22
 RESCALE_TRANSFORMED, RESCALE_FLOOR = 1, 2
 MODUP_TRANSFORMED = 1
 MODDOWN_TRANSFORMED, MODDOWN_FLOOR, MODDOWN_ACCUMULATE = 1, 2, 4
 GALOIS_TRANSFORMED, GALOIS_ACCUMULATE, GALOIS_KEY_BROADCAST = 1, 2, 4
 LINCOMB_ACCUMULATE, LINCOMB_M_BROADCAST, LINCOMB_LAZY_IN = 1, 2, 4
 PLAIN_SCALE = 1
+LIFT_SCALE, LIFT_TRANSFORMED, LIFT_ACCUMULATE = 1, 2, 4
 
 #: every symbol include/ntt_mi355x.h and the reference-named headers declare
 EXPORTED_SYMBOLS = [
@@ -76,6 +78,7 @@ EXPORTED_SYMBOLS = [
     "ntt_galois_rotation", "ntt_galois_batch", "ntt_rns_galois_batch", "ntt_rns_galois_batch_strided", "ntt_rns_galois_dot_batch",
     "ntt_rns_galois_dot_batch_strided", "ntt_rns_lincomb_batch", "ntt_rns_lincomb_batch_strided",
     "ntt_rns_to_plain_batch", "ntt_rns_to_plain_batch_strided", "ntt_rns_to_double_batch", "ntt_rns_to_double_batch_strided",
+    "ntt_rns_from_plain_batch", "ntt_rns_from_plain_batch_strided", "ntt_rns_from_double_batch", "ntt_rns_from_double_batch_strided",
     "ntt_transform_batch_strided", "ntt_transform_ptrs", "ntt_rns_transform_ptrs", "ntt_transform_dev_ptrs", "ntt_rns_transform_dev_ptrs", "ntt_inv_dot_dev_ptrs", "ntt_fwd_mul_dev_ptrs", "ntt_negacyclic_mul_dev_ptrs",
     "ntt_rns_inv_dot_dev_ptrs", "ntt_rns_fwd_mul_dev_ptrs", "ntt_rns_negacyclic_mul_dev_ptrs", "ntt_dev_malloc", "ntt_dev_free", "ntt_dev_mem_info",
     "ntt_h2d", "ntt_d2h", "ntt_stream_create", "ntt_stream_destroy", "ntt_stream_sync",
@@ -209,6 +212,12 @@ _sig("ntt_rns_to_plain_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP
 _sig("ntt_rns_to_double_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_double, C.c_uint64, VOIDP)
 _sig("ntt_rns_to_double_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_double, C.c_uint64, C.c_uint64, C.c_uint64,
      C.c_uint64, VOIDP)
+_sig("ntt_rns_from_plain_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_from_plain_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+     C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_from_double_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_double, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_from_double_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_double, C.c_uint64, C.c_uint64, C.c_uint64,
+     C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_transform_batch_strided", C.c_int, VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_transform_ptrs", C.c_int, VOIDP, C.POINTER(VOIDP), C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_transform_ptrs", C.c_int, C.c_int, C.POINTER(VOIDP), C.POINTER(VOIDP), C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
@@ -814,6 +823,26 @@ def rns_to_double(plans, dy, da, scale, batch, stream=None, layout=None):
         _check(_lib.ntt_rns_to_double_batch_strided(len(plans), _plan_array(plans), dy, da, scale, layout[0], layout[1], layout[2], batch,
                                                     stream))
     else: _check(_lib.ntt_rns_to_double_batch(len(plans), _plan_array(plans), dy, da, scale, batch, stream))
+
+
+def rns_from_plain(plans, dc, dm, t, batch, flags=0, stream=None, layout=None):
+    """into the RNS: dc ([limb][batch][N], canonical) = the words dm ([batch][N], in [0, t)) lifted to every limb: [m_c]_q of the centred
+    representative (BGV, plaintext operands); LIFT_SCALE: round(Q m / t) mod q (BFV; every prime coprime to t).  LIFT_TRANSFORMED: dc
+    in the NTT domain; LIFT_ACCUMULATE: dc += the lift.  2 <= t < 2^61, any limb count.  layout = (c_limb_stride, c_poly_stride,
+    m_poly_stride) in words for any other placement; OPT_LIFT_FUSED on plans[0] selects the NTT-domain route"""
+    if layout:
+        _check(_lib.ntt_rns_from_plain_batch_strided(len(plans), _plan_array(plans), dc, dm, t, layout[0], layout[1], layout[2], batch, flags,
+                                                     stream))
+    else: _check(_lib.ntt_rns_from_plain_batch(len(plans), _plan_array(plans), dc, dm, t, batch, flags, stream))
+
+
+def rns_from_double(plans, dc, dy, scale, batch, flags=0, stream=None, layout=None):
+    """into the RNS: dc = [rint(y * scale)]_q per limb for the doubles dy ([batch][N]) (CKKS, after the encoding FFT); 0 for NaN, inf and
+    |y * scale| >= 2^127.  Flags and layout = (c_limb_stride, c_poly_stride, y_poly_stride) as rns_from_plain, without LIFT_SCALE"""
+    if layout:
+        _check(_lib.ntt_rns_from_double_batch_strided(len(plans), _plan_array(plans), dc, dy, scale, layout[0], layout[1], layout[2], batch,
+                                                      flags, stream))
+    else: _check(_lib.ntt_rns_from_double_batch(len(plans), _plan_array(plans), dc, dy, scale, batch, flags, stream))
 
 
 def batch_multi(plans, dptrs, batches, inverse=False):

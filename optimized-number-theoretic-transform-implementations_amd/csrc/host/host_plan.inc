@@ -167,6 +167,8 @@ struct ntt_plan {
                                       * everywhere, -1 = where the recorded measurement says it is not slower (ksfold_pays); plans[0] */
   int              bgv_fused = -1;   /* the BGV ModDown calls: 1 = moddown_bgv_fwd_kernel where it is built, 0 = the sandwich everywhere,
                                       * -1 = where the recorded measurement says it is not slower (bgv_fused_applies); plans[0] */
+  int              lift_fused = -1;  /* the lifts with NTT_LIFT_TRANSFORMED: 1 = lift_fwd_kernel where it is built, 0 = the composition
+                                      * everywhere, -1 = the default rule (lift_fused_applies); plans[0] */
   int              block_oversub = 0; /* persistent block kernels: workgroups per resident slot (0 = the kernels' defaults) */
   int              num_cus    = 256;
   int              chunk_mib  = 256; /* bytes of one multi-pass chunk (Infinity Cache residency) */
@@ -579,6 +581,9 @@ extern "C" int ntt_plan_set_option(ntt_plan *p, int option, int64_t value)
     case NTT_OPT_BGV_FUSED:
       p->bgv_fused = value < 0 ? -1 : (value != 0);
       return NTT_OK;
+    case NTT_OPT_LIFT_FUSED:
+      p->lift_fused = value < 0 ? -1 : (value != 0);
+      return NTT_OK;
     case NTT_OPT_MAX_BATCH_HINT:
       if(value < 0) return fail(NTT_ERR_ARG, "batch hint must be >= 0");
       {
@@ -677,6 +682,7 @@ extern "C" int ntt_plan_get_option(const ntt_plan *p, int option, int64_t *value
     case NTT_OPT_PAIR_FUSED: *value = p->pair_fused; return NTT_OK;
     case NTT_OPT_MODDOWN_ADD_FUSED: *value = p->moddown_add_fused; return NTT_OK;
     case NTT_OPT_BGV_FUSED: *value = p->bgv_fused; return NTT_OK;
+    case NTT_OPT_LIFT_FUSED: *value = p->lift_fused; return NTT_OK;
     case NTT_OPT_MAX_BATCH_HINT: *value = (int64_t)p->batch_hint; return NTT_OK;
     case NTT_OPT_CTL_ALLOCATIONS: {
       std::lock_guard<std::mutex> lock(p->team_mu);

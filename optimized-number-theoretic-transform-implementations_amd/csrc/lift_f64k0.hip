@@ -1,0 +1,6 @@
+/* lift_f64k0.hip -- instantiates the fused lift kernels (lift_fwd_kernel, N = 2^6..2^14) for (ArithF64, headroom class 0). */
+#include "ntt_kernels_lift.h"
+
+namespace ntt {
+NTT_DEFINE_LAUNCH_LIFT_FWD(ArithF64, 0)
+} /* namespace ntt */

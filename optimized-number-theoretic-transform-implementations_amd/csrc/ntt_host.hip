@@ -28,6 +28,7 @@
 #include "ntt_bgv.h"
 #include "ntt_lincomb.h"
 #include "ntt_plain.h"
+#include "ntt_lift.h"
 #include "ntt_rescale.h"
 #include "ntt_tables.h"
 
@@ -149,5 +150,6 @@ static int check_device(int device)
 #include "host/host_bgv.inc"
 #include "host/host_lincomb.inc"
 #include "host/host_plain.inc"
+#include "host/host_lift.inc"
 #include "host/host_runtime.inc"
 #include "host/host_compat.inc"
