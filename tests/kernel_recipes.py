@@ -25,6 +25,18 @@ output must come back unchanged.  The pointwise kernels (pointwise_kernel, point
 case per instance through the entry point that reaches it, with 4q-1 x 4q-1 among the lazy operands and q-1 + q-1 in the
 accumulating forms.
 
+The NTT-domain product families (dot_inv_kernel, team_dot_kernel: c = inv(sum_i a_i^ (.) b_i^); fwd_mul_kernel, team_mul_kernel,
+onepass_mul_kernel: c^ = fwd(a) (.) b^ (+ c^)) are driven through ntt_inv_dot_batch / ntt_fwd_mul_batch, their strided RNS twins on
+the padded limb-major layout (MULTI) and the device-pointer-table twins (PTRS; a broadcast b^ a dense [limb][N] polynomial).  Flags
+are run-time fields, so every instance gets two cases: one pair (store) of canonical words with one b^ per polynomial, and
+kDotEvery + 1 pairs (accumulate) of lazy words with a broadcast b^.  Fixed words of the first polynomial carry the extremes:
+(q-1) x (q-1), the residue q-1 in every term (the running sum at its largest in front of a fold), 4q-1 x 4q-1 and q-1 carried as
+4q-1 among the lazy words; b^ = q-1, b^ = 0 and c^ = q-1 on top of a product q-1 in the mul forms.  The batch comes from the
+geometry these kernels are launched with (domain_batch), the grid is capped as for the product families.  Once per policy and class
+the slab form of dot_inv_kernel at 2^6 and 2^14 runs k = kDotEvery, kDotEvery + 1 and 32 pairs, canonical and lazy; team_dot_kernel
+once per policy 32 lazy pairs; once per family and policy c aliases an operand where the header allows it.  The references are
+checked against schoolbook products by tests/test_domain_reference_cpu.py.
+
 Run as a script (the launch proof of tests/test_gpu_kernel_instances.py runs it under a kernel trace, one family per child):
     python3 tests/kernel_recipes.py [substring ...]     every case whose id contains one of the substrings (default: all)
     python3 tests/kernel_recipes.py --family NAME       every case of exactly that kernel family
@@ -44,8 +56,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import kernel_inventory  # noqa: E402
 
-# instances no recipe covers yet, one normalised key per line: the remaining families (fused_kernel, the dot and mul kernels,
-# the plain host kernels).  Pinned so that a new instantiation in any family fails
+# instances no recipe covers yet, one normalised key per line: fused_kernel and the plain host kernels.  Pinned so that a new instantiation in any family fails
 # tests/test_kernel_inventory.py until a recipe claims it, and so that the list can only shrink as recipes land.
 UNCOVERED_LIST = os.path.join(ROOT, "tests", "golden", "uncovered_kernel_instances.txt")
 
@@ -330,75 +341,97 @@ def _assert_unwritten(cid, what, got, before, n, nlimbs, batch, layout):
         cid, what, bad.size, bad[0])
 
 
-def _run_slab(lib, cid, plans, qs, n, batch, entry, flags, a, b, want, a_kept, b_kept):
+# one operand of a call: data = its words per limb ([batch][N], or -- shared -- ONE polynomial of N words: a broadcast b^, handed over
+# dense as [limb][N]); kept: the header declares it const or "left as it was", so every word must come back unchanged (otherwise
+# it is scratch: only the words outside its polynomials stay)
+Op = collections.namedtuple("Op", "name data kept shared")
+
+
+def _run_slab(lib, cid, plans, qs, n, batch, ins, want, call, c_init=None, alias=None):
+    """the operands as slabs in _slab_layout; call(dc, [device buffer of every operand], layout) issues the entry point;
+    c_init: what c holds on entry (accumulating forms), alias: index of the operand whose buffer is handed over as c"""
     nl = len(plans)
     lay = _slab_layout(n, nl, batch)
-    ia, ib = _slab_image(a, n, batch, lay), _slab_image(b, n, batch, lay)
-    ic = np.full(lay[2], GUARD, dtype=np.uint64)
-    da, db, dc = (lib.DeviceBuffer(lay[2]).upload(x) for x in (ia, ib, ic))
+    imgs = [np.concatenate(list(op.data) + [np.full(n, GUARD, dtype=np.uint64)]) if op.shared else _slab_image(op.data, n, batch, lay)
+            for op in ins]
+    ic = imgs[alias] if alias is not None else (
+        np.full(lay[2], GUARD, dtype=np.uint64) if c_init is None else _slab_image(c_init, n, batch, lay))
+    bufs = [lib.DeviceBuffer(x.size).upload(x) for x in imgs]
+    dc = bufs[alias] if alias is not None else lib.DeviceBuffer(lay[2]).upload(ic)
     try:
-        if nl == 1 and entry == "mul":
-            plans[0].negacyclic_mul(dc.ptr, da.ptr, db.ptr, batch)
-        elif nl == 1:
-            plans[0].mul_transformed(dc.ptr, da.ptr, db.ptr, batch, flags)
-        elif entry == "mul":
-            lib.rns_negacyclic_mul(plans, dc.ptr, da.ptr, db.ptr, batch, layout=lay[:2])
-        else:
-            lib.rns_mul_transformed(plans, dc.ptr, da.ptr, db.ptr, batch, flags, layout=lay[:2])
-        ga, gb, gc = da.download(), db.download(), dc.download()
+        call(dc, bufs, lay)
+        got, gc = [d.download() for d in bufs], dc.download()
     finally:
-        da.free(), db.free(), dc.free()
+        for d in bufs + ([] if alias is not None else [dc]):
+            d.free()
     for l, g in enumerate(_slab_polys(gc, n, nl, batch, lay)):
         _assert_words(cid, "c", g, want[l], n, l, qs[l])
     _assert_unwritten(cid, "c", gc, ic, n, nl, batch, lay)
-    for what, kept, g, before in (("a", a_kept, ga, ia), ("b", b_kept, gb, ib)):
-        if kept:
-            assert np.array_equal(g, before), "%s: operand %s was written (the header leaves it as it was)" % (cid, what)
+    for i, (op, g, before) in enumerate(zip(ins, got, imgs)):
+        if i == alias:
+            continue
+        if op.kept or op.shared:
+            assert np.array_equal(g, before), "%s: operand %s was written (the header leaves it as it was)" % (cid, op.name)
         else:
-            _assert_unwritten(cid, what, g, before, n, nl, batch, lay)
+            _assert_unwritten(cid, op.name, g, before, n, nl, batch, lay)
 
 
-def _run_tables(lib, cid, plans, qs, n, count, a, b, want, kept):
-    """the three operands as device tables of `count` pointers into one pool: every polynomial (RNS: its limbs, n + 16 words
+def _run_tables(lib, cid, plans, qs, n, count, ins, want, call, c_init=None):
+    """the operands and c as device tables of `count` pointers into one pool: every polynomial (RNS: its limbs, n + 16 words
     apart behind the entry) at a place of its own, the operands interleaved, shuffled, no two gaps alike -- a kernel that
-    computes slab offsets instead of reading the tables produces wrong words"""
+    computes slab offsets instead of reading the tables produces wrong words.  A shared operand (a broadcast b^) is no table: its
+    [limb][N] words lie behind the records, and the call gets their device address.  call([table or address of every operand],
+    c's table, limb stride) issues the entry point."""
     nl = len(plans)
     lstride = n + 16
     rec = (nl - 1) * lstride + n
+    tabbed = [i for i, op in enumerate(ins) if not op.shared]
+    nt = len(tabbed) + 1
     rng = np.random.default_rng(0x7AB1E + n + count)
-    gaps = rng.integers(1, 40, size=3 * count) + np.arange(3 * count) % 7
+    gaps = rng.integers(1, 40, size=nt * count) + np.arange(nt * count) % 7
     starts = np.cumsum(gaps + rec) - rec
-    words = int(starts[-1] + rec + n)
-    offs = starts[rng.permutation(3 * count)].reshape(3, count)
+    end = int(starts[-1] + rec)
+    shared_at = {i: end + 24 + j * (nl * n + 24) for j, i in enumerate(i for i, op in enumerate(ins) if op.shared)}
+    words = end + len(shared_at) * (nl * n + 24) + n
+    offs = starts[rng.permutation(nt * count)].reshape(nt, count)
     img = np.full(words, GUARD, dtype=np.uint64)
-    for o, src in ((0, a), (1, b)):
+    for o, src in [(o, ins[i].data) for o, i in enumerate(tabbed)] + ([(nt - 1, c_init)] if c_init is not None else []):
         for l in range(nl):
             for p in range(count):
                 at = int(offs[o][p]) + l * lstride
                 img[at:at + n] = src[l][p * n:(p + 1) * n]
+    for i, at in shared_at.items():
+        img[at:at + nl * n] = np.concatenate(list(ins[i].data))
     pool = lib.DeviceBuffer(words).upload(img)
-    tabs = [lib.DeviceBuffer(count).upload((np.uint64(pool.ptr) + np.uint64(8) * offs[o].astype(np.uint64))) for o in range(3)]
+    tabs = [lib.DeviceBuffer(count).upload((np.uint64(pool.ptr) + np.uint64(8) * offs[o].astype(np.uint64))) for o in range(nt)]
     try:
-        if nl == 1:
-            plans[0].negacyclic_mul_dev_ptrs(tabs[2].ptr, tabs[0].ptr, tabs[1].ptr, count)
-        else:
-            lib.rns_negacyclic_mul_dev_ptrs(plans, tabs[2].ptr, tabs[0].ptr, tabs[1].ptr, count, lstride)
+        args = [pool.ptr + 8 * shared_at[i] if op.shared else tabs[tabbed.index(i)].ptr for i, op in enumerate(ins)]
+        call(args, tabs[nt - 1].ptr, lstride)
         got = pool.download()
     finally:
         pool.free()
         for t in tabs:
             t.free()
     written = np.zeros(words, dtype=bool)
+    scratch = [o for o, i in enumerate(tabbed) if not ins[i].kept]
     for l in range(nl):
-        g = np.concatenate([got[int(offs[2][p]) + l * lstride:int(offs[2][p]) + l * lstride + n] for p in range(count)])
+        g = np.concatenate([got[int(offs[nt - 1][p]) + l * lstride:int(offs[nt - 1][p]) + l * lstride + n] for p in range(count)])
         _assert_words(cid, "c", g, want[l], n, l, qs[l])
-        for o in ((2,) if kept else (0, 1, 2)):   # (above 2^14 a and b are scratch: only what lies between the polynomials stays)
+        for o in [nt - 1] + scratch:   # (scratch operands: only what lies between the polynomials stays)
             for p in range(count):
                 at = int(offs[o][p]) + l * lstride
                 written[at:at + n] = True
     bad = np.nonzero(~written & (got != img))[0]
     assert bad.size == 0, "%s: %d words outside %s were written, first at word %d of the pool" % (
-        cid, bad.size, "c's polynomials" if kept else "the polynomials", bad[0])
+        cid, bad.size, "the polynomials of c and of %s" % ", ".join(ins[tabbed[o]].name for o in scratch) if scratch else "c's polynomials", bad[0])
+
+
+def _apply(lib, plans, options):
+    for p in plans:
+        for o, v in options:
+            p.set_option(getattr(lib, o), v)
+    if len(plans) > 1:
+        lib.set_rns_launch(plans, 0)
 
 
 def _product_case(inst, policy, ksh, m, nlimbs, batch, options, entry, ptrs=False, lazy=False, suffix=""):
@@ -411,11 +444,7 @@ def _product_case(inst, policy, ksh, m, nlimbs, batch, options, entry, ptrs=Fals
         ps = make_plans(lib, oracle, policy, ksh, n, nlimbs)
         try:
             plans, qs = [p for p, _, _ in ps], [q for _, q, _ in ps]
-            for p in plans:
-                for o, v in options:
-                    p.set_option(getattr(lib, o), v)
-            if nlimbs > 1:
-                lib.set_rns_launch(plans, 0)
+            _apply(lib, plans, options)
             refs = [_product_reference(oracle, cx, n, q, batch, i, entry == "given") for i, (_, q, cx) in enumerate(ps)]
             a, b, want = ([r[k] for r in refs] for k in range(3))
             if lazy:
@@ -423,11 +452,25 @@ def _product_case(inst, policy, ksh, m, nlimbs, batch, options, entry, ptrs=Fals
             # what the header says about the operands: the one-launch forms up to 2^14 leave the coefficient operands as they
             # were; the transformed operand is const; everything else is scratch
             one_launch = m <= 14 and dict(options).get("OPT_FUSED_PRODUCT", 1) == 1
+            flags = lib.MUL_LAZY_IN if lazy else 0
             if ptrs:
-                _run_tables(lib, cid, plans, qs, n, batch, a, b, want, kept=one_launch)
+                def call(t, ctab, lstride):
+                    if nlimbs == 1:
+                        plans[0].negacyclic_mul_dev_ptrs(ctab, t[0], t[1], batch)
+                    else:
+                        lib.rns_negacyclic_mul_dev_ptrs(plans, ctab, t[0], t[1], batch, lstride)
+                _run_tables(lib, cid, plans, qs, n, batch, [Op("a", a, one_launch, False), Op("b", b, one_launch, False)], want, call)
             else:
-                _run_slab(lib, cid, plans, qs, n, batch, entry, lib.MUL_LAZY_IN if lazy else 0, a, b, want,
-                          a_kept=one_launch, b_kept=entry == "given")
+                def call(dc, d, lay):
+                    if nlimbs == 1 and entry == "mul":
+                        plans[0].negacyclic_mul(dc.ptr, d[0].ptr, d[1].ptr, batch)
+                    elif nlimbs == 1:
+                        plans[0].mul_transformed(dc.ptr, d[0].ptr, d[1].ptr, batch, flags)
+                    elif entry == "mul":
+                        lib.rns_negacyclic_mul(plans, dc.ptr, d[0].ptr, d[1].ptr, batch, layout=lay[:2])
+                    else:
+                        lib.rns_mul_transformed(plans, dc.ptr, d[0].ptr, d[1].ptr, batch, flags, layout=lay[:2])
+                _run_slab(lib, cid, plans, qs, n, batch, [Op("a", a, one_launch, False), Op("b", b, entry == "given", False)], want, call)
         finally:
             for p, _, _ in ps:
                 p.destroy()
@@ -518,6 +561,328 @@ def recipe_team_product(inst):
     if (ptrs and not four) or not 3 <= a["LEAD"] <= 5:
         return None
     return _product_forms(inst, a["KSH"], 12 + a["LEAD"], 33 if multi else 65, (("OPT_XCD_LOCAL", 1),), 0, multi, four, ptrs)
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# products of operands in the NTT domain: c = inv(sum_i a_i^ (.) b_i^) (dot_inv_kernel, team_dot_kernel) and
+# c^ = fwd(a) (.) b^ (+ c^) (fwd_mul_kernel, team_mul_kernel, onepass_mul_kernel)
+# --------------------------------------------------------------------------------------------------------------------
+K_MAX_DOT = 32   # kMaxDot (ntt_kernels_products.h)
+# words of the first polynomial that carry the extreme values (behind the canonical extremes inputs() puts into words 0..4)
+W_SQUARE, W_TOP, W_LAZY, W_CARRY, W_ZERO = 8, 9, 10, 11, 12
+
+
+def dot_every(policy):
+    """kDotEvery of the policy (ntt_arith.h): the terms between two folds of the running sum; None: ArithU64 never folds"""
+    return {"ArithF64": 3, "ArithF64W": 1, "ArithU64X<0>": 1, "ArithU64X<1>": 4, "ArithU64X<3>": 20, "ArithU64": None}[policy]
+
+
+def domain_bpw(policy, logn, inverse):
+    """blocks per workgroup of Geom<LOGN, INV, flavor_of<A>()> (ntt_kernels_block.h), the geometry dot_inv_kernel (INV) and
+    fwd_mul_kernel (!INV) are launched with: Plan<LOGN>::T = 2^(LOGN - 4) threads per block, 256 / T blocks in a 256-thread
+    workgroup below 2^12, one block above -- but two (PERSIST2) in the forward 2^13 kernel of the FP64 policies (flavor 1)"""
+    if logn == 13 and not inverse and policy in ("ArithF64", "ArithF64W"):
+        return 2
+    return max(1, 256 >> (logn - 4))
+
+
+def domain_batch(policy, logn, inverse):
+    """small_product_batch for the geometry of the dot and mul kernels (domain_bpw): four full groups of BPW polynomials and a
+    fifth that is partly dead where BPW > 1 (more than half of its sub-blocks live from BPW = 4 on, one of two at BPW = 2); with
+    two workgroups per limb (NTT_OPT_MAX_GRID) workgroup 0 takes groups 0, 2, 4 -- it wraps twice and ends on the partly dead
+    group -- and workgroup 1 groups 1, 3.  BPW = 1 (2^12 on): five polynomials, blocks 0, 2, 4 and 1, 3."""
+    bpw = domain_bpw(policy, logn, inverse)
+    return 4 * bpw + (bpw // 2 + 1 if bpw >= 4 else 1)
+
+
+def _cached(key, make):
+    """references of the NTT-domain cases, computed once and shared read-only by the cases on the same operands (the forms of
+    one instance, the MULTI / PTRS instances beside it); the cache is bounded by words, the large team cases evict one another"""
+    if key in _ref_cache:
+        _ref_cache.move_to_end(key)
+        return _ref_cache[key]
+    _ref_cache[key] = make()
+    size = lambda v: sum(x.size for part in v for x in (part if isinstance(part, list) else [part]) if x is not None)  # noqa: E731
+    while len(_ref_cache) > 1 and (len(_ref_cache) > 6 or sum(size(v) for v in _ref_cache.values()) > (1 << 28)):
+        _ref_cache.popitem(last=False)
+    return _ref_cache[key]
+
+
+def _lift(oracle, r, q, seed, top):
+    """the residues r as lazy words anywhere in [0,4q); top: {word: multiple of q added there}"""
+    w = r + np.uint64(q) * oracle.fill_uniform(r.size, 4, seed)
+    for at, mult in top.items():
+        w[at] = r[at] + np.uint64(mult * q)
+    assert int(w.max()) < 4 * q and np.array_equal(w % np.uint64(q), r)
+    return w
+
+
+def dot_reference(oracle, cx, n, q, batch, limb, k, lazy, bcast):
+    """([a_i^ words], [b_i^ words], want) of one limb: want = inv(sum_{i<k} a_i^ (.) b_i^ mod q), the products by oracle.pointwise
+    and an exact modular sum (oracle.dot), the inverse by the oracle.  Every operand is inputs(); in every term the first
+    polynomial holds (q-1) x (q-1) at W_SQUARE and (q-1) x 1 at W_TOP (the residue q-1 in every term: the running sum as large
+    as it gets in front of a fold), and the last polynomial of every a_i^ and b_i^ is q-1 throughout.  lazy: the words handed
+    over are lifted anywhere into [0,4q) (the range ntt_inv_dot_batch admits with NTT_MUL_LAZY_IN: no 2^53 bound there), at
+    W_LAZY both factors 4q-1 (the highest lazy word), at W_CARRY the residue q-1 carried as 4q-1 times 1 carried as 3q+1.
+    bcast: every b_i^ is one polynomial."""
+    def make():
+        nb = 1 if bcast else batch
+        ar = [inputs(oracle, n, q, batch, 0xA500 + 131 * limb + i) for i in range(k)]
+        br = [inputs(oracle, n, q, nb, 0xB600 + 137 * limb + i) for i in range(k)]
+        for a, b in zip(ar, br):
+            a[-n:] = np.uint64(q - 1)
+            if not bcast:
+                b[-n:] = np.uint64(q - 1)
+            for at, (x, y) in {W_SQUARE: (q - 1, q - 1), W_TOP: (q - 1, 1), W_LAZY: (q - 1, q - 1), W_CARRY: (q - 1, 1)}.items():
+                a[at], b[at] = np.uint64(x), np.uint64(y)
+        want = cx.inv(oracle.dot(ar, br, q, N=n, bcast=bcast))
+        assert int(want.max()) < q
+        if lazy:
+            aw = [_lift(oracle, a, q, 0x1A2 + i, {W_LAZY: 3, W_CARRY: 3}) for i, a in enumerate(ar)]
+            bw = [_lift(oracle, b, q, 0x2B3 + i, {W_LAZY: 3, W_CARRY: 3}) for i, b in enumerate(br)]
+            assert int(aw[0][W_LAZY]) == 4 * q - 1 and int(bw[0][W_LAZY]) == 4 * q - 1 and int(bw[0][W_CARRY]) == 3 * q + 1
+        else:
+            aw, bw = ar, br
+        _readonly(want, *aw, *bw)
+        return aw, bw, want
+    return _cached(("dot", n, q, batch, limb, k, lazy, bcast), make)
+
+
+def mul_reference(oracle, cx, n, q, batch, limb, lazy, bcast, acc):
+    """(a, b^ words, c^ on entry or None, want) of one limb: want = fwd(a) (.) b^ (+ c^) mod q by the oracle.  a: inputs(), its last
+    polynomial q-1 throughout; b^: a transformed polynomial with q-1 at W_SQUARE, 0 at W_TOP, q-1 again at W_LAZY -- lazy: carried
+    as 4q-1, the highest word NTT_MUL_LAZY_IN admits here, the other words lifted anywhere into [0,4q) -- and at W_CARRY the word
+    that makes the product q-1 there; acc: c^ canonical on entry, q-1 at W_CARRY (q-1 + q-1) and 0 at W_ZERO.  The fixed words
+    sit in the first polynomial (bcast: b^ is one polynomial, so its fixed words meet every polynomial of a)."""
+    def make():
+        a = inputs(oracle, n, q, batch, 0x2468 + 17 * limb)
+        a[-n:] = np.uint64(q - 1)
+        fa = cx.fwd(a)
+        nb = 1 if bcast else batch
+        br = cx.fwd(inputs(oracle, n, q, nb, 0xB0B + 29 * limb))
+        assert int(fa[W_CARRY]) != 0
+        for at, v in {W_SQUARE: q - 1, W_TOP: 0, W_LAZY: q - 1, W_CARRY: (q - 1) * pow(int(fa[W_CARRY]), -1, q) % q}.items():
+            br[at] = np.uint64(v)
+        want = oracle.pointwise(fa, np.tile(br, batch) if bcast else br, q)
+        assert int(want[W_CARRY]) == q - 1
+        c0 = None
+        if acc:
+            c0 = oracle.fill_uniform(batch * n, q, 0xC0C + 31 * limb)
+            c0[W_CARRY], c0[W_ZERO] = np.uint64(q - 1), np.uint64(0)
+            want = (want + c0) % np.uint64(q)
+            _readonly(c0)
+        bw = _lift(oracle, br, q, 0x3C4, {W_LAZY: 3}) if lazy else br
+        _readonly(a, bw, want)
+        return a, bw, c0, want
+    return _cached(("mul", n, q, batch, limb, lazy, bcast, acc), make)
+
+
+def _dot_case(inst, ksh, m, nlimbs, batch, options, k, lazy=False, bcast=False, ptrs=False, alias=False, suffix=""):
+    """ntt_inv_dot_batch, ntt_rns_inv_dot_batch_strided (nlimbs > 1), ntt_inv_dot_dev_ptrs / ntt_rns_inv_dot_dev_ptrs (ptrs);
+    alias: k = 1 and d_c = d_ahat[0], which the header allows.  Every a_i^ and b_i^ is const and must come back unchanged."""
+    n = 1 << m
+    cid = kernel_inventory.case_id(inst) + suffix
+
+    def run(lib, oracle):
+        ps = make_plans(lib, oracle, inst.policy, ksh, n, nlimbs)
+        try:
+            plans, qs = [p for p, _, _ in ps], [q for _, q, _ in ps]
+            _apply(lib, plans, options)
+            refs = [dot_reference(oracle, cx, n, q, batch, l, k, lazy, bcast) for l, (_, q, cx) in enumerate(ps)]
+            ins = [Op("a%d^" % i, [r[0][i] for r in refs], True, False) for i in range(k)]
+            ins += [Op("b%d^" % i, [r[1][i] for r in refs], True, bcast) for i in range(k)]
+            want = [r[2] for r in refs]
+            flags = (lib.MUL_LAZY_IN if lazy else 0) | (lib.MUL_B_BROADCAST if bcast else 0)
+            if ptrs:
+                def call(t, ctab, lstride):
+                    if nlimbs == 1:
+                        plans[0].inv_dot_dev_ptrs(ctab, t[:k], t[k:], batch, flags)
+                    else:
+                        lib.rns_inv_dot_dev_ptrs(plans, ctab, t[:k], t[k:], batch, lstride, flags)
+                _run_tables(lib, cid, plans, qs, n, batch, ins, want, call)
+            else:
+                def call(dc, d, lay):
+                    pa, pb = [x.ptr for x in d[:k]], [x.ptr for x in d[k:]]
+                    if nlimbs == 1:
+                        plans[0].inv_dot(dc.ptr, pa, pb, batch, flags)
+                    else:
+                        lib.rns_inv_dot(plans, dc.ptr, pa, pb, batch, flags, layout=lay[:2])
+                _run_slab(lib, cid, plans, qs, n, batch, ins, want, call, alias=0 if alias else None)
+        finally:
+            for p, _, _ in ps:
+                p.destroy()
+    return Case(cid, inst, run)
+
+
+def _mul_case(inst, ksh, m, nlimbs, batch, options, lazy=False, bcast=False, acc=False, ptrs=False, a_kept=True, alias=None, suffix=""):
+    """ntt_fwd_mul_batch, ntt_rns_fwd_mul_batch_strided (nlimbs > 1), ntt_fwd_mul_dev_ptrs / ntt_rns_fwd_mul_dev_ptrs (ptrs); alias:
+    d_c = d_a (0) or d_bhat (1), store form.  b^ is const; a_kept: the header leaves a as it was (up to 2^14, and 2^15 in one pass)."""
+    n = 1 << m
+    cid = kernel_inventory.case_id(inst) + suffix
+
+    def run(lib, oracle):
+        ps = make_plans(lib, oracle, inst.policy, ksh, n, nlimbs)
+        try:
+            plans, qs = [p for p, _, _ in ps], [q for _, q, _ in ps]
+            _apply(lib, plans, options)
+            refs = [mul_reference(oracle, cx, n, q, batch, l, lazy, bcast, acc) for l, (_, q, cx) in enumerate(ps)]
+            ins = [Op("a", [r[0] for r in refs], a_kept, False), Op("b^", [r[1] for r in refs], True, bcast)]
+            c0, want = [r[2] for r in refs] if acc else None, [r[3] for r in refs]
+            flags = (lib.MUL_LAZY_IN if lazy else 0) | (lib.MUL_B_BROADCAST if bcast else 0) | (lib.MUL_ACCUMULATE if acc else 0)
+            if ptrs:
+                def call(t, ctab, lstride):
+                    if nlimbs == 1:
+                        plans[0].fwd_mul_dev_ptrs(ctab, t[0], t[1], batch, flags)
+                    else:
+                        lib.rns_fwd_mul_dev_ptrs(plans, ctab, t[0], t[1], batch, lstride, flags)
+                _run_tables(lib, cid, plans, qs, n, batch, ins, want, call, c_init=c0)
+            else:
+                def call(dc, d, lay):
+                    if nlimbs == 1:
+                        plans[0].fwd_mul(dc.ptr, d[0].ptr, d[1].ptr, batch, flags)
+                    else:
+                        lib.rns_fwd_mul(plans, dc.ptr, d[0].ptr, d[1].ptr, batch, flags, layout=lay[:2])
+                _run_slab(lib, cid, plans, qs, n, batch, ins, want, call, c_init=c0, alias=alias)
+        finally:
+            for p, _, _ in ps:
+                p.destroy()
+    return Case(cid, inst, run)
+
+
+def _dot_forms(inst, ksh, m, nl, batch, opts, ptrs, suffix=""):
+    """the two cases of every dot instance: one pair of canonical words, one b^ per polynomial; kDotEvery + 1 pairs (the first
+    term behind a fold; 3 for ArithU64, which never folds) of lazy words with broadcast b^"""
+    every = dot_every(inst.policy)
+    return [_dot_case(inst, ksh, m, nl, batch, opts, 1, ptrs=ptrs, suffix=suffix),
+            _dot_case(inst, ksh, m, nl, batch, opts, every + 1 if every else 3, lazy=True, bcast=True, ptrs=ptrs, suffix=suffix + "-lazy-bcast")]
+
+
+def _mul_forms(inst, ksh, m, nl, batch, opts, ptrs, a_kept, suffix=""):
+    """the two cases of every mul instance: store, canonical words, one b^ per polynomial; accumulate onto c^, lazy words,
+    broadcast b^"""
+    return [_mul_case(inst, ksh, m, nl, batch, opts, ptrs=ptrs, a_kept=a_kept, suffix=suffix),
+            _mul_case(inst, ksh, m, nl, batch, opts, lazy=True, bcast=True, acc=True, ptrs=ptrs, a_kept=a_kept, suffix=suffix + "-acc-lazy-bcast")]
+
+
+def _first_class(inst):
+    """one instance per policy: of the scheduled FP64 policy class 0 (the other policies have one class each)"""
+    return inst.policy != "ArithF64" or inst.args["KSH"] == 0
+
+
+def recipe_dot_inv(inst):
+    """dot_inv_kernel<A, LOGN, KSH, LASTINV, MULTI, PTRS> (ntt_kernels_launch.h, launch_dot_impl / launch_dot_blocks;
+    host_ntt_domain.inc, inv_dot, rns_inv_dot, inv_dot_ptrs_limb / inv_dot_ptrs_run).
+    LASTINV: N = 2^LOGN, 6..14 (launch_dot_impl: with_int<6, 14>), ntt_inv_dot_batch; MULTI: ntt_rns_inv_dot_batch_strided with
+    NTT_OPT_RNS_LAUNCH 0 (rns_one_launch_pays); PTRS: ntt_inv_dot_dev_ptrs (ptrs_fused), with MULTI ntt_rns_inv_dot_dev_ptrs
+    (ptrs_run_pays).  Batch: domain_batch for Geom<LOGN, true, flavor>, two workgroups per limb.
+    !LASTINV (launch_dot_impl: logn > kFusedMax, block_log 12 or 14; no PTRS form): the blocks of N = 2^15 with
+    NTT_OPT_BLOCK_LOG = LOGN, the XCD-local launch off, 3 polynomials; block_grid rounds the cap of one workgroup up to the 2^s0
+    blocks of a polynomial, so every workgroup takes three blocks at its position.
+    Once per policy and class, slab form, LOGN 6 and 14: k = kDotEvery, kDotEvery + 1 and 32 pairs, canonical and lazy words
+    (ArithU64 never folds: 32).  Once per policy (LOGN 12): k = 1 with d_c = d_ahat[0]."""
+    a = inst.args
+    ln, ksh, multi, ptrs = a["LOGN"], a["KSH"], a["MULTI"], a["PTRS"]
+    nl = _nlimbs(multi)
+    if not a["LASTINV"]:
+        if ptrs or ln not in (12, 14):
+            return None
+        opts = _grid_option((("OPT_BLOCK_LOG", ln), ("OPT_XCD_LOCAL", 0)), 1, nl)
+        return _dot_forms(inst, ksh, 15, nl, 3, opts, False)
+    if not 6 <= ln <= 14:
+        return None
+    opts, batch = _grid_option((), 2, nl), domain_batch(inst.policy, ln, True)
+    out = _dot_forms(inst, ksh, ln, nl, batch, opts, ptrs)
+    if not multi and not ptrs:
+        if ln in (6, 14):
+            every = dot_every(inst.policy)
+            for k in sorted({every, every + 1, K_MAX_DOT} if every else {K_MAX_DOT}):
+                out += [_dot_case(inst, ksh, ln, 1, batch, opts, k, lazy=lazy, suffix="-k%d%s" % (k, "-lazy" if lazy else ""))
+                        for lazy in (False, True)]
+        if ln == 12 and _first_class(inst):
+            out.append(_dot_case(inst, ksh, ln, 1, batch, opts, 1, alias=True, suffix="-alias-a"))
+    return out
+
+
+def recipe_fwd_mul(inst):
+    """fwd_mul_kernel<A, LOGN, KSH, MULTI, PTRS> (ntt_kernels_launch.h, launch_fwd_mul_impl / launch_fwd_mul_blocks;
+    host_ntt_domain.inc, fwd_mul, rns_fwd_mul, fwd_mul_ptrs_limb).  N = 2^LOGN, 6..14 (with_int<6, 14>): ntt_fwd_mul_batch; MULTI:
+    ntt_rns_fwd_mul_batch_strided with NTT_OPT_RNS_LAUNCH 0; PTRS: ntt_fwd_mul_dev_ptrs (ptrs_fused), with MULTI
+    ntt_rns_fwd_mul_dev_ptrs.  Batch: domain_batch for Geom<LOGN, false, flavor> (two blocks per workgroup at 2^13 with the FP64
+    policies), two workgroups per limb.  a is left as it was.
+    The instances of LOGN 12 and 14 without PTRS also as the block pass of N = 2^15 (launch_fwd_mul_impl: logn > kFusedMax; s0 != 0):
+    NTT_OPT_BLOCK_LOG = LOGN, the XCD-local and the one-pass launch off, 3 polynomials, every workgroup three blocks at its
+    position; a is scratch there.  Once per policy (LOGN 12): the store form with d_c = d_a and with d_c = d_bhat."""
+    a = inst.args
+    ln, ksh, multi, ptrs = a["LOGN"], a["KSH"], a["MULTI"], a["PTRS"]
+    if not 6 <= ln <= 14:
+        return None
+    nl = _nlimbs(multi)
+    opts, batch = _grid_option((), 2, nl), domain_batch(inst.policy, ln, False)
+    out = _mul_forms(inst, ksh, ln, nl, batch, opts, ptrs, True)
+    if ln in (12, 14) and not ptrs:
+        blk = _grid_option((("OPT_BLOCK_LOG", ln), ("OPT_XCD_LOCAL", 0), ("OPT_ONE_PASS", 0)), 1, nl)
+        out += _mul_forms(inst, ksh, 15, nl, 3, blk, False, False, suffix="-N15")
+    if ln == 12 and not multi and not ptrs and _first_class(inst):
+        out += [_mul_case(inst, ksh, ln, 1, batch, opts, alias=0, suffix="-alias-a"),
+                _mul_case(inst, ksh, ln, 1, batch, opts, alias=1, suffix="-alias-b")]
+    return out
+
+
+def _team_shape(a):
+    """N = 2^(12 + LEAD) and 65 polynomials (two limbs: 33 each): one past the 64 polynomials x limbs inv_dot / fwd_mul
+    (host_ntt_domain.inc: polys >= 64) and ptrs_team want; NTT_OPT_XCD_LOCAL 1 forces the one-launch form, NTT_OPT_ONE_PASS 0
+    keeps 2^15 with the FP64 policies from the one-pass kernel (fwd_mul asks one_pass_pays first)"""
+    nl = _nlimbs(a["MULTI"])
+    return 12 + a["LEAD"], nl, 33 if nl > 1 else 65, (("OPT_XCD_LOCAL", 1), ("OPT_ONE_PASS", 0))
+
+
+def recipe_team_dot(inst):
+    """team_dot_kernel<A, LEAD, KSH, MULTI, PTRS> (ntt_kernels_launch.h, launch_dot_impl: da.team_ctl -> launch_team_dot;
+    host_ntt_domain.inc, inv_dot: team, inv_dot_ptrs_limb: ptrs_team): _team_shape, LEAD 3..5 (with_int<3, 5>).  The launch is the
+    team kernels' own grid on eight queues (team_prologue).  Once per policy (LEAD 3, slab): 32 pairs of lazy words, and k = 1
+    with d_c = d_ahat[0]."""
+    a = inst.args
+    if not 3 <= a["LEAD"] <= 5:
+        return None
+    m, nl, batch, opts = _team_shape(a)
+    out = _dot_forms(inst, a["KSH"], m, nl, batch, opts, a["PTRS"])
+    if a["LEAD"] == 3 and nl == 1 and not a["PTRS"] and _first_class(inst):
+        out += [_dot_case(inst, a["KSH"], m, 1, batch, opts, K_MAX_DOT, lazy=True, suffix="-k32-lazy"),
+                _dot_case(inst, a["KSH"], m, 1, batch, opts, 1, alias=True, suffix="-alias-a")]
+    return out
+
+
+def recipe_team_mul(inst):
+    """team_mul_kernel<A, LEAD, KSH, MULTI, PTRS> (ntt_kernels_launch.h, launch_fwd_mul_impl: ma.team_ctl -> launch_team_mul;
+    host_ntt_domain.inc, fwd_mul: team, fwd_mul_ptrs_limb: ptrs_team): _team_shape, LEAD 3..5; a's column stages run in place, so
+    a is scratch.  Once per policy (LEAD 3, slab): the store form with d_c = d_a and with d_c = d_bhat."""
+    a = inst.args
+    if not 3 <= a["LEAD"] <= 5:
+        return None
+    m, nl, batch, opts = _team_shape(a)
+    out = _mul_forms(inst, a["KSH"], m, nl, batch, opts, a["PTRS"], False)
+    if a["LEAD"] == 3 and nl == 1 and not a["PTRS"] and _first_class(inst):
+        out += [_mul_case(inst, a["KSH"], m, 1, batch, opts, a_kept=False, alias=0, suffix="-alias-a"),
+                _mul_case(inst, a["KSH"], m, 1, batch, opts, a_kept=False, alias=1, suffix="-alias-b")]
+    return out
+
+
+def recipe_onepass_mul(inst):
+    """onepass_mul_kernel<A, KSH, MULTI, PTRS> (ntt_kernels_launch.h, launch_fwd_mul_impl: ma.one_pass -> launch_onepass_mul;
+    host_ntt_domain.inc, fwd_mul: one_pass_pays, fwd_mul_ptrs_limb: ptrs_one_pass_mul): N = 2^15, NTT_OPT_ONE_PASS 1, the FP64
+    policies; 5 polynomials on two workgroups per limb (onepass_grid: workgroup 0 takes polynomials 0, 2, 4, workgroup 1 takes
+    1, 3); a is left as it was.  MULTI with PTRS is not built (launch_onepass_mul; fwd_mul_ptrs_limb hands a run over limb by
+    limb).  Once per policy (slab): the store form with d_c = d_a and with d_c = d_bhat."""
+    a = inst.args
+    if a["MULTI"] and a["PTRS"]:
+        return None
+    nl = _nlimbs(a["MULTI"])
+    opts = _grid_option((("OPT_ONE_PASS", 1),), 2, nl)
+    out = _mul_forms(inst, a["KSH"], 15, nl, 5, opts, a["PTRS"], True)
+    if nl == 1 and not a["PTRS"] and _first_class(inst):
+        out += [_mul_case(inst, a["KSH"], 15, 1, 5, opts, alias=0, suffix="-alias-a"),
+                _mul_case(inst, a["KSH"], 15, 1, 5, opts, alias=1, suffix="-alias-b")]
+    return out
 
 
 # --------------------------------------------------------------------------------------------------------------------
@@ -671,6 +1036,11 @@ RECIPES = {
     "fused_product_kernel": recipe_fused_product,
     "fused_product_small_kernel": recipe_fused_product_small,
     "team_product_kernel": recipe_team_product,
+    "dot_inv_kernel": recipe_dot_inv,
+    "fwd_mul_kernel": recipe_fwd_mul,
+    "team_dot_kernel": recipe_team_dot,
+    "team_mul_kernel": recipe_team_mul,
+    "onepass_mul_kernel": recipe_onepass_mul,
     "pointwise_kernel": recipe_pointwise,
     "pointwise_acc_kernel": recipe_pointwise_acc,
     "pointwise_ptrs_kernel": recipe_pointwise_ptrs,

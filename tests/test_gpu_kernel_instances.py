@@ -1,7 +1,8 @@
 """GPU: every kernel instance the recipe table covers (tests/kernel_recipes.py) -- the transform families (onepass, twophase, team,
-column), the coefficient-domain product families (fused_product, fused_product_small, team_product) and the pointwise kernels --
-launched and checked word for word against the oracle; a kernel trace, one traced child per family, proves that the recipes
-launch every instance they claim; route precedence of explicit plan options over the automatic one-pass choice."""
+column), the coefficient-domain product families (fused_product, fused_product_small, team_product), the NTT-domain product
+families (dot_inv, fwd_mul, team_dot, team_mul, onepass_mul) and the pointwise kernels -- launched and checked word for word
+against the oracle; a kernel trace, one traced child per family, proves that the recipes launch every instance they claim; route
+precedence of explicit plan options over the automatic one-pass choice."""
 import csv
 import glob
 import os
@@ -68,22 +69,55 @@ FAMILY_LIMITS = {
     "fused_product_kernel": 120,         # 4.3 s
     "fused_product_small_kernel": 120,   # 3.1 s
     "team_product_kernel": 120,          # 24.8 s
+    "dot_inv_kernel": 120,               # 17.9 s
+    "fwd_mul_kernel": 120,               # 13.5 s
+    "team_dot_kernel": 180,              # 58.2 s
+    "team_mul_kernel": 120,              # 29.4 s
+    "onepass_mul_kernel": 120,           # 2.1 s
     "pointwise_kernel": 120,             # 1.0 s
     "pointwise_acc_kernel": 120,         # 0.8 s
     "pointwise_ptrs_kernel": 120,        # 0.8 s
 }
 
 
+_TRACES = {}   # family -> the kernels its traced child launched (one child per family and session)
+_BROKEN = []   # the family whose traced child did not end cleanly: no further child is started on the GPU after it
+
+
+def _family_trace(family):
+    if family not in _TRACES:
+        if _BROKEN:
+            pytest.fail("not started: the traced child of %s did not end cleanly" % _BROKEN[0])
+        try:
+            _TRACES[family] = _traced(["--family", family], FAMILY_LIMITS[family])
+        except BaseException:
+            _BROKEN.append(family)
+            raise
+    return _TRACES[family]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("family", list(kernel_recipes.RECIPES))
+def test_family_launches_the_instances_it_claims(family):
+    """the traced child of one family launches every shipped instance of that family that is neither pinned as not covered nor
+    allowlisted (the children run one per test, so that fifteen of them do not sit in one test without a sign of life)"""
+    inv = kernel_inventory.instances()
+    claimed = {k for k, i in inv.items() if i.family == family} - kernel_recipes.uncovered() - set(kernel_recipes.ALLOWLIST)
+    missing = sorted(claimed - _family_trace(family))
+    assert not missing, "instances the recipe names but never launches: %s" % missing
+
+
 @pytest.mark.gpu
 def test_every_covered_instance_is_launched():
     """the instances the recipes claim (every shipped instance outside tests/golden/uncovered_kernel_instances.txt) - launched -
-    allowlist = {}, and no allowlisted instance is launched.  One traced child per family, one after the other (a failing child
-    fails the test before the next one starts); the union of their traces is what is asserted."""
+    allowlist = {}, and no allowlisted instance is launched.  One traced child per family, one after the other (shared with the
+    per-family test above; after a child that did not end cleanly no further one is started); the union of their traces is what
+    is asserted."""
     inv = kernel_inventory.instances()
     assert set(FAMILY_LIMITS) == set(kernel_recipes.RECIPES)
     launched = set()
     for family in kernel_recipes.RECIPES:
-        launched |= _traced(["--family", family], FAMILY_LIMITS[family])
+        launched |= _family_trace(family)
     # the trace's names normalise to the inventory's: the headline kernel (the block pass behind the recipes' 1-stage column
     # passes) by name
     assert "fused_kernel<ArithF64,14,false,0,false,false,false>" in inv
