@@ -90,15 +90,7 @@ static int bgv_fwd_launch(ntt_plan *const *plans, int first, int n, int nq, int 
   ModDownBgvArgs                   ba{};
   KsFoldArgs &                     ka = ba.k;
   ModDownFwdArgs &                 ma = ka.m;
-  ma.c           = d_a + (uint64_t)first * alay.limb;
-  ma.t           = d_a + (uint64_t)nq * alay.limb;
-  ma.limbs       = recs.data();
-  ma.nlimbs      = n;
-  ma.np          = np;
-  ma.limb_stride = alay.limb;
-  ma.poly_stride = alay.poly;
-  ma.batch       = batch;
-  ma.logn        = (uint32_t)plans[first]->m;
+  const int                        kc = moddown_fwd_args(ma, recs, plans, first, n, nq, np, d_a, batch, stream, alay);
   bgv_sources(pr, np, t, ma.pl);
   for(int l = 0; l < n; l++) {
     const uint64_t q = plans[first + l]->q;
@@ -107,20 +99,11 @@ static int bgv_fwd_launch(ntt_plan *const *plans, int first, int n, int nq, int 
     ma.ql[l].h = h_mulmod(ma.ql[l].h, t % q, q);
     ba.ts[l]   = bgv_scale_of(t, q);
   }
-  ma.max_grid        = plans[first]->max_grid;
-  ma.num_cus         = plans[first]->num_cus;
-  ma.stream          = (hipStream_t)stream;
   ka.out             = d_c + (uint64_t)first * clay.limb;
   ka.out_limb_stride = clay.limb;
   ka.out_poly_stride = clay.poly;
   ka.accumulate      = accumulate;
-  /* the run's coarsest headroom class, as ksfold_launch */
-  int kc = plans[first]->kcls;
-  for(int l = first + 1; l < first + n; l++) kc = plans[l]->kcls < kc ? plans[l]->kcls : kc;
-  const hipError_t e = kc == kWideClass ? launch_moddown_bgv_fwd<ArithF64W, 0>(ba)
-                       : kc == 18       ? launch_moddown_bgv_fwd<ArithF64, 18>(ba)
-                       : kc == 1        ? launch_moddown_bgv_fwd<ArithF64, 1>(ba)
-                                        : launch_moddown_bgv_fwd<ArithF64, 0>(ba);
+  const hipError_t e = with_f64_class(kc, [&](auto k) { return launch_moddown_bgv_fwd<typename decltype(k)::A, decltype(k)::KSH>(ba); });
   if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("moddown_bgv_fwd_kernel: ") + hipGetErrorString(e));
   return NTT_OK;
 }
@@ -146,52 +129,17 @@ static int rns_mod_down_bgv(int nq, int np, ntt_plan *const *plans, uint64_t *d_
   for(int j = nq; j < nlimbs; j++) {
     if(t % plans[j]->q == 0) return fail(NTT_ERR_ARG, "a P prime divides the plaintext modulus");
   }
-  const bool                             ntt_dom    = (flags & NTT_MODDOWN_TRANSFORMED) != 0;
-  const bool                             accumulate = (flags & NTT_MODDOWN_ACCUMULATE) != 0;
-  const std::vector<std::pair<int, int>> runs       = rns_runs(nq, plans);
-  std::vector<char>                      fused(runs.size(), 0);
-  if(ntt_dom) {
-    /* every table the call will need, before anything is written */
-    for(int j = nq; j < nlimbs; j++) {
-      if(!plans[j]->has_inv) return fail(NTT_ERR_ARG, "a P limb's plan lacks the inverse table");
-    }
-    for(size_t r = 0; r < runs.size(); r++) {
-      fused[r] = bgv_fused_applies(plans[0], plans[runs[r].first], np, add_form) ? 1 : 0;
-      for(int l = runs[r].first; l < runs[r].first + runs[r].second; l++) {
-        if(!plans[l]->has_fwd) return fail(NTT_ERR_ARG, "a Q limb's plan lacks the forward table");
-        if(!fused[r] && !plans[l]->has_inv) return fail(NTT_ERR_ARG, "a Q limb's plan lacks the inverse table (sandwich route)");
-      }
-    }
-  }
-  if(batch == 0) return NTT_OK;
-  const uint64_t N = plans[0]->N;
-  if(add_form && galois_overlap(galois_span(d_c, N, nq, batch, clay.limb, clay.poly), galois_span(d_a, N, nlimbs, batch, alay.limb, alay.poly)))
-    return fail(NTT_ERR_ARG, "mod_down_bgv_add: d_c overlaps d_a");
-  USE_DEVICE(plans[0]->device);
-  uint64_t pr[kBconvLimbs];
-  for(int j = 0; j < np; j++) pr[j] = plans[nq + j]->q;
-  const Layout one{alay.limb, alay.poly};
-  if(!ntt_dom) {
-    for(int first = 0; !rc && first < nq; first += kBconvLimbs) {
-      rc = bgv_coef_launch(plans, first, nq - first < kBconvLimbs ? nq - first : kBconvLimbs, nq, np, d_a, t, batch, stream, alay, pr);
-    }
-    if(!rc && add_form) rc = ct_fold_launches(plans, 0, nq, d_c, d_a, batch, accumulate, stream, clay, alay);
-    return rc;
-  }
-  rc = rns_transform(np, plans + nq, d_a + (uint64_t)nq * alay.limb, batch, true, stream, one);
-  for(size_t r = 0; !rc && r < runs.size(); r++) {
-    const int first = runs[r].first, n = runs[r].second;
-    if(fused[r]) {
-      rc = bgv_fwd_launch(plans, first, n, nq, np, add_form ? d_c : d_a, d_a, t, batch, accumulate, stream, add_form ? clay : alay, alay, pr);
-      continue;
-    }
-    uint64_t *c = d_a + (uint64_t)first * alay.limb;
-    rc          = rns_transform(n, plans + first, c, batch, true, stream, one);
-    if(!rc) rc = bgv_coef_launch(plans, first, n, nq, np, d_a, t, batch, stream, alay, pr);
-    if(!rc) rc = rns_transform(n, plans + first, c, batch, false, stream, one);
-    if(!rc && add_form) rc = ct_fold_launches(plans, first, n, d_c, d_a, batch, accumulate, stream, clay, alay);
-  }
-  return rc;
+  const bool accumulate = (flags & NTT_MODDOWN_ACCUMULATE) != 0;
+  const bool overlap    = add_form && galois_overlap(galois_span(d_c, plans[0]->N, nq, batch, clay.limb, clay.poly),
+                                                     galois_span(d_a, plans[0]->N, nlimbs, batch, alay.limb, alay.poly));
+  return moddown_route(
+    nq, np, plans, d_a, batch, (flags & NTT_MODDOWN_TRANSFORMED) != 0, stream, alay, overlap ? "mod_down_bgv_add: d_c overlaps d_a" : nullptr,
+    [&](const ntt_plan *p) { return bgv_fused_applies(plans[0], p, np, add_form) ? kModDownFusedInto : kModDownSandwich; },
+    [&](int first, int n, const uint64_t *pr) { return bgv_coef_launch(plans, first, n, nq, np, d_a, t, batch, stream, alay, pr); },
+    [&](ModDownRun, int first, int n, const uint64_t *pr) { /* (the in-place form: into d_a's own Q limbs) */
+      return bgv_fwd_launch(plans, first, n, nq, np, add_form ? d_c : d_a, d_a, t, batch, accumulate, stream, add_form ? clay : alay, alay, pr);
+    },
+    [&](int first, int n) { return add_form ? ct_fold_launches(plans, first, n, d_c, d_a, batch, accumulate, stream, clay, alay) : NTT_OK; });
 }
 
 extern "C" int ntt_rns_mod_down_bgv_batch(int nq, int np, ntt_plan *const *plans, uint64_t *d_a, uint64_t t, uint64_t batch, unsigned flags,

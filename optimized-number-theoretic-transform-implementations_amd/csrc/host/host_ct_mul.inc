@@ -109,34 +109,17 @@ static int ksfold_launch(ntt_plan *const *plans, int first, int n, int nq, int n
   const std::vector<unsigned char> recs = rns_records(plans, first, n);
   KsFoldArgs                       ka{};
   ModDownFwdArgs &                 ma = ka.m;
-  ma.c           = d_a + (uint64_t)first * alay.limb;
-  ma.t           = d_a + (uint64_t)nq * alay.limb;
-  ma.limbs       = recs.data();
-  ma.nlimbs      = n;
-  ma.np          = np;
-  ma.limb_stride = alay.limb;
-  ma.poly_stride = alay.poly;
-  ma.batch       = batch;
-  ma.logn        = (uint32_t)plans[first]->m;
+  const int                        kc = moddown_fwd_args(ma, recs, plans, first, n, nq, np, d_a, batch, stream, alay);
   bconv_sources(pr, np, !floor_div, ma.pl);
   for(int l = 0; l < n; l++) {
     uint64_t g[kBconvLimbs]; /* (formed again by the kernel's workgroups: no room for the table in its arguments) */
     ma.ql[l] = moddown_dst(plans[first + l]->q, pr, np, floor_div, g);
   }
-  ma.max_grid        = plans[first]->max_grid;
-  ma.num_cus         = plans[first]->num_cus;
-  ma.stream          = (hipStream_t)stream;
   ka.out             = d_c + (uint64_t)first * clay.limb;
   ka.out_limb_stride = clay.limb;
   ka.out_poly_stride = clay.poly;
   ka.accumulate      = accumulate;
-  /* the run's coarsest headroom class (rns_for_runs); a run of 52-bit primes is all of the wide policy (rns_compatible) */
-  int kc = plans[first]->kcls;
-  for(int l = first + 1; l < first + n; l++) kc = plans[l]->kcls < kc ? plans[l]->kcls : kc;
-  const hipError_t e = kc == kWideClass ? launch_ksfold_fwd<ArithF64W, 0>(ka)
-                       : kc == 18       ? launch_ksfold_fwd<ArithF64, 18>(ka)
-                       : kc == 1        ? launch_ksfold_fwd<ArithF64, 1>(ka)
-                                        : launch_ksfold_fwd<ArithF64, 0>(ka);
+  const hipError_t e = with_f64_class(kc, [&](auto k) { return launch_ksfold_fwd<typename decltype(k)::A, decltype(k)::KSH>(ka); });
   if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("ksfold_fwd_kernel: ") + hipGetErrorString(e));
   return NTT_OK;
 }
@@ -180,59 +163,21 @@ static int rns_mod_down_add(int nq, int np, ntt_plan *const *plans, uint64_t *d_
   if(!rc) rc = layout_check(plans[0]->N, nq, batch, clay);
   if(!rc) rc = distinct_primes(nlimbs, plans);
   if(rc) return rc;
-  const bool                             ntt_dom    = (flags & NTT_MODDOWN_TRANSFORMED) != 0;
-  const bool                             floor_div  = (flags & NTT_MODDOWN_FLOOR) != 0;
-  const bool                             accumulate = (flags & NTT_MODDOWN_ACCUMULATE) != 0;
-  const std::vector<std::pair<int, int>> runs       = rns_runs(nq, plans);
-  std::vector<char>                      fold(runs.size(), 0);
-  if(ntt_dom) {
-    /* every table the call will need, before anything is written */
-    for(int j = nq; j < nlimbs; j++) {
-      if(!plans[j]->has_inv) return fail(NTT_ERR_ARG, "a P limb's plan lacks the inverse table");
-    }
-    for(size_t r = 0; r < runs.size(); r++) {
-      const ntt_plan *pf = plans[runs[r].first];
-      fold[r]            = ksfold_applies(plans[0], pf, np) ? 1 : 0;
-      const bool fused   = fold[r] || rescale_fused_applies(plans[0], pf);
-      for(int l = runs[r].first; l < runs[r].first + runs[r].second; l++) {
-        if(!plans[l]->has_fwd) return fail(NTT_ERR_ARG, "a Q limb's plan lacks the forward table");
-        if(!fused && !plans[l]->has_inv) return fail(NTT_ERR_ARG, "a Q limb's plan lacks the inverse table (sandwich route)");
-      }
-    }
-  }
-  if(batch == 0) return NTT_OK;
-  const uint64_t N = plans[0]->N;
-  if(galois_overlap(galois_span(d_c, N, nq, batch, clay.limb, clay.poly), galois_span(d_a, N, nlimbs, batch, alay.limb, alay.poly)))
-    return fail(NTT_ERR_ARG, "mod_down_add: d_c overlaps d_a");
-  USE_DEVICE(plans[0]->device);
-  uint64_t pr[kBconvLimbs];
-  for(int j = 0; j < np; j++) pr[j] = plans[nq + j]->q;
-  const Layout one{alay.limb, alay.poly};
-  if(!ntt_dom) {
-    for(int first = 0; !rc && first < nq; first += kBconvLimbs) {
-      rc = moddown_coef_launch(plans, first, nq - first < kBconvLimbs ? nq - first : kBconvLimbs, nq, np, d_a, batch, floor_div, stream, alay, pr);
-    }
-    if(!rc) rc = ct_fold_launches(plans, 0, nq, d_c, d_a, batch, accumulate, stream, clay, alay);
-    return rc;
-  }
-  rc = rns_transform(np, plans + nq, d_a + (uint64_t)nq * alay.limb, batch, true, stream, one);
-  for(size_t r = 0; !rc && r < runs.size(); r++) {
-    const int first = runs[r].first, n = runs[r].second;
-    if(fold[r]) {
-      rc = ksfold_launch(plans, first, n, nq, np, d_c, d_a, batch, floor_div, accumulate, stream, clay, alay, pr);
-      continue;
-    }
-    if(rescale_fused_applies(plans[0], plans[first])) {
-      rc = moddown_fwd_launch(plans, first, n, nq, np, d_a, batch, floor_div, stream, alay, pr);
-    } else {
-      uint64_t *c = d_a + (uint64_t)first * alay.limb;
-      rc          = rns_transform(n, plans + first, c, batch, true, stream, one);
-      if(!rc) rc = moddown_coef_launch(plans, first, n, nq, np, d_a, batch, floor_div, stream, alay, pr);
-      if(!rc) rc = rns_transform(n, plans + first, c, batch, false, stream, one);
-    }
-    if(!rc) rc = ct_fold_launches(plans, first, n, d_c, d_a, batch, accumulate, stream, clay, alay);
-  }
-  return rc;
+  const bool floor_div  = (flags & NTT_MODDOWN_FLOOR) != 0;
+  const bool accumulate = (flags & NTT_MODDOWN_ACCUMULATE) != 0;
+  const bool overlap    = galois_overlap(galois_span(d_c, plans[0]->N, nq, batch, clay.limb, clay.poly),
+                                         galois_span(d_a, plans[0]->N, nlimbs, batch, alay.limb, alay.poly));
+  return moddown_route(
+    nq, np, plans, d_a, batch, (flags & NTT_MODDOWN_TRANSFORMED) != 0, stream, alay, overlap ? "mod_down_add: d_c overlaps d_a" : nullptr,
+    [&](const ntt_plan *p) {
+      return ksfold_applies(plans[0], p, np) ? kModDownFusedInto : rescale_fused_applies(plans[0], p) ? kModDownFusedHere : kModDownSandwich;
+    },
+    [&](int first, int n, const uint64_t *pr) { return moddown_coef_launch(plans, first, n, nq, np, d_a, batch, floor_div, stream, alay, pr); },
+    [&](ModDownRun k, int first, int n, const uint64_t *pr) {
+      return k == kModDownFusedInto ? ksfold_launch(plans, first, n, nq, np, d_c, d_a, batch, floor_div, accumulate, stream, clay, alay, pr)
+                                    : moddown_fwd_launch(plans, first, n, nq, np, d_a, batch, floor_div, stream, alay, pr);
+    },
+    [&](int first, int n) { return ct_fold_launches(plans, first, n, d_c, d_a, batch, accumulate, stream, clay, alay); });
 }
 
 extern "C" int ntt_rns_mod_down_add_batch(int nq, int np, ntt_plan *const *plans, uint64_t *d_c, uint64_t *d_a, uint64_t batch, unsigned flags,

@@ -129,15 +129,7 @@ static int moddown_exact_fwd_launch(ntt_plan *const *plans, int first, int n, in
   const std::vector<unsigned char> recs = rns_records(plans, first, n);
   ModDownExactFwdArgs              xa{};
   ModDownFwdArgs &                 ma = xa.ma;
-  ma.c           = d_a + (uint64_t)first * lay.limb;
-  ma.t           = d_a + (uint64_t)nq * lay.limb;
-  ma.limbs       = recs.data();
-  ma.nlimbs      = n;
-  ma.np          = np;
-  ma.limb_stride = lay.limb;
-  ma.poly_stride = lay.poly;
-  ma.batch       = batch;
-  ma.logn        = (uint32_t)plans[first]->m;
+  const int                        kc = moddown_fwd_args(ma, recs, plans, first, n, nq, np, d_a, batch, stream, lay);
   exact_sources(pr, np, mult, ma.pl, xa.rho);
   for(int l = 0; l < n; l++) {
     const uint64_t q = plans[first + l]->q;
@@ -145,16 +137,7 @@ static int moddown_exact_fwd_launch(ntt_plan *const *plans, int first, int n, in
     ma.ql[l] = moddown_exact_dst(q, pr, np, g);
     xa.mq[l] = mult % q;
   }
-  ma.max_grid = plans[first]->max_grid;
-  ma.num_cus  = plans[first]->num_cus;
-  ma.stream   = (hipStream_t)stream;
-  /* the run's coarsest headroom class, as moddown_fwd_launch */
-  int kc = plans[first]->kcls;
-  for(int l = first + 1; l < first + n; l++) kc = plans[l]->kcls < kc ? plans[l]->kcls : kc;
-  const hipError_t e = kc == kWideClass ? launch_moddown_exact_fwd<ArithF64W, 0>(xa)
-                       : kc == 18       ? launch_moddown_exact_fwd<ArithF64, 18>(xa)
-                       : kc == 1        ? launch_moddown_exact_fwd<ArithF64, 1>(xa)
-                                        : launch_moddown_exact_fwd<ArithF64, 0>(xa);
+  const hipError_t e = with_f64_class(kc, [&](auto k) { return launch_moddown_exact_fwd<typename decltype(k)::A, decltype(k)::KSH>(xa); });
   if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("moddown_exact_fwd_kernel: ") + hipGetErrorString(e));
   return NTT_OK;
 }
@@ -202,46 +185,12 @@ static int rns_mod_down_exact(int nq, int np, ntt_plan *const *plans, uint64_t *
   rc = layout_check(plans[0]->N, nlimbs, batch, lay);
   if(!rc) rc = distinct_primes(nlimbs, plans);
   if(rc) return rc;
-  const bool                             ntt_dom = (flags & NTT_MODDOWN_TRANSFORMED) != 0;
-  const std::vector<std::pair<int, int>> runs    = rns_runs(nq, plans);
-  if(ntt_dom) {
-    /* every table the call will need, before anything is written */
-    for(int j = nq; j < nlimbs; j++) {
-      if(!plans[j]->has_inv) return fail(NTT_ERR_ARG, "a P limb's plan lacks the inverse table");
-    }
-    for(const std::pair<int, int> &run : runs) {
-      const bool fused = exact_fused_applies(plans[0], plans[run.first], np);
-      for(int l = run.first; l < run.first + run.second; l++) {
-        if(!plans[l]->has_fwd) return fail(NTT_ERR_ARG, "a Q limb's plan lacks the forward table");
-        if(!fused && !plans[l]->has_inv) return fail(NTT_ERR_ARG, "a Q limb's plan lacks the inverse table (sandwich route)");
-      }
-    }
-  }
-  if(batch == 0) return NTT_OK;
-  USE_DEVICE(plans[0]->device);
-  uint64_t pr[kBconvLimbs];
-  for(int j = 0; j < np; j++) pr[j] = plans[nq + j]->q;
-  const Layout one{lay.limb, lay.poly};
-  if(!ntt_dom) {
-    for(int first = 0; !rc && first < nq; first += kBconvLimbs) {
-      rc = moddown_exact_launch(plans, first, nq - first < kBconvLimbs ? nq - first : kBconvLimbs, nq, np, d_a, mult, batch, stream, lay, pr);
-    }
-    return rc;
-  }
-  rc = rns_transform(np, plans + nq, d_a + (uint64_t)nq * lay.limb, batch, true, stream, one);
-  for(const std::pair<int, int> &run : runs) {
-    if(rc) break;
-    const int first = run.first, n = run.second;
-    if(exact_fused_applies(plans[0], plans[first], np)) {
-      rc = moddown_exact_fwd_launch(plans, first, n, nq, np, d_a, mult, batch, stream, lay, pr);
-      continue;
-    }
-    uint64_t *c = d_a + (uint64_t)first * lay.limb;
-    rc          = rns_transform(n, plans + first, c, batch, true, stream, one);
-    if(!rc) rc = moddown_exact_launch(plans, first, n, nq, np, d_a, mult, batch, stream, lay, pr);
-    if(!rc) rc = rns_transform(n, plans + first, c, batch, false, stream, one);
-  }
-  return rc;
+  return moddown_route(
+    nq, np, plans, d_a, batch, (flags & NTT_MODDOWN_TRANSFORMED) != 0, stream, lay, nullptr,
+    [&](const ntt_plan *p) { return exact_fused_applies(plans[0], p, np) ? kModDownFusedHere : kModDownSandwich; },
+    [&](int first, int n, const uint64_t *pr) { return moddown_exact_launch(plans, first, n, nq, np, d_a, mult, batch, stream, lay, pr); },
+    [&](ModDownRun, int first, int n, const uint64_t *pr) { return moddown_exact_fwd_launch(plans, first, n, nq, np, d_a, mult, batch, stream, lay, pr); },
+    moddown_no_fold);
 }
 
 extern "C" int ntt_rns_mod_down_exact_batch(int nq, int np, ntt_plan *const *plans, uint64_t *d_a, uint64_t mult, uint64_t batch,

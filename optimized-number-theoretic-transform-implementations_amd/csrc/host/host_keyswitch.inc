@@ -12,6 +12,8 @@
  *                            N = 2^6..2^14 -- moddown_fwd_kernel, ONE launch per run: 8N(2nq + 3np) bytes in all; anything else --
  *                            the sandwich: the inverse over the run, moddown_coef_kernel, the forward over the run.  The route
  *                            switch is NTT_OPT_RESCALE_FUSED on plans[0] (rescale_fused_applies).
+ *             The route itself is moddown_route, shared with ntt_rns_mod_down_add_batch (host_ct_mul.inc), the exact ModDown
+ *             (host_exact.inc) and the BGV ModDown (host_bgv.inc); moddown_fwd_args fills what their fused launches have in common.
  * The per-call constants take O(n^2) modular products for n source primes plus O(n) per destination prime (prefix and suffix
  * products; one inverse per source prime and per destination prime, none per pair).  Nothing is allocated, the host is not
  * synchronised and no memset is issued: the calls can be captured into a graph. */
@@ -212,11 +214,13 @@ static int moddown_coef_launch(ntt_plan *const *plans, int first, int n, int nq,
   return NTT_OK;
 }
 
-static int moddown_fwd_launch(ntt_plan *const *plans, int first, int n, int nq, int np, uint64_t *d_a, uint64_t batch, bool floor_div,
-                              void *stream, const Layout &lay, const uint64_t *pr)
+/* The fields of a fused ModDown launch (moddown_fwd_body's four kernels) that every variant fills alike: the run [first, first + n) of
+ * d_a's Q limbs, its P limbs behind the nq Q limbs, the run's limb records (recs: the caller's, alive until the launch returns), sizes
+ * and launch limits of the run's first plan.  The sources, ql[] and the variant's own constants are the caller's.  Returns the run's
+ * headroom class. */
+static int moddown_fwd_args(ModDownFwdArgs &ma, const std::vector<unsigned char> &recs, ntt_plan *const *plans, int first, int n, int nq, int np,
+                            uint64_t *d_a, uint64_t batch, void *stream, const Layout &lay)
 {
-  const std::vector<unsigned char> recs = rns_records(plans, first, n);
-  ModDownFwdArgs                   ma{};
   ma.c           = d_a + (uint64_t)first * lay.limb;
   ma.t           = d_a + (uint64_t)nq * lay.limb;
   ma.limbs       = recs.data();
@@ -226,23 +230,90 @@ static int moddown_fwd_launch(ntt_plan *const *plans, int first, int n, int nq, 
   ma.poly_stride = lay.poly;
   ma.batch       = batch;
   ma.logn        = (uint32_t)plans[first]->m;
+  ma.max_grid    = plans[first]->max_grid;
+  ma.num_cus     = plans[first]->num_cus;
+  ma.stream      = (hipStream_t)stream;
+  return run_class(plans, first, n);
+}
+
+static int moddown_fwd_launch(ntt_plan *const *plans, int first, int n, int nq, int np, uint64_t *d_a, uint64_t batch, bool floor_div,
+                              void *stream, const Layout &lay, const uint64_t *pr)
+{
+  const std::vector<unsigned char> recs = rns_records(plans, first, n);
+  ModDownFwdArgs                   ma{};
+  const int                        kc = moddown_fwd_args(ma, recs, plans, first, n, nq, np, d_a, batch, stream, lay);
   bconv_sources(pr, np, !floor_div, ma.pl);
   for(int l = 0; l < n; l++) {
     uint64_t g[kBconvLimbs]; /* (formed again by the kernel's workgroups: no room for the table in its arguments) */
     ma.ql[l] = moddown_dst(plans[first + l]->q, pr, np, floor_div, g);
   }
-  ma.max_grid = plans[first]->max_grid;
-  ma.num_cus  = plans[first]->num_cus;
-  ma.stream   = (hipStream_t)stream;
-  /* the run's coarsest headroom class (rns_for_runs); a run of 52-bit primes is all of the wide policy (rns_compatible) */
-  int kc = plans[first]->kcls;
-  for(int l = first + 1; l < first + n; l++) kc = plans[l]->kcls < kc ? plans[l]->kcls : kc;
-  const hipError_t e = kc == kWideClass ? launch_moddown_fwd<ArithF64W, 0>(ma)
-                       : kc == 18       ? launch_moddown_fwd<ArithF64, 18>(ma)
-                       : kc == 1        ? launch_moddown_fwd<ArithF64, 1>(ma)
-                                        : launch_moddown_fwd<ArithF64, 0>(ma);
+  const hipError_t e = with_f64_class(kc, [&](auto k) { return launch_moddown_fwd<typename decltype(k)::A, decltype(k)::KSH>(ma); });
   if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("moddown_fwd_kernel: ") + hipGetErrorString(e));
   return NTT_OK;
+}
+
+/* The route of every ModDown call (ntt_rns_mod_down_batch, _add_, _bgv_, _bgv_add_, _exact_) behind its own argument checks.  What
+ * differs comes in as
+ *   kind(p)              how the run whose first plan is p is served (ModDownRun);
+ *   coef(first, n, pr)   the coefficient kernel over Q limbs [first, first + n) of d_a, in place;
+ *   fused(k, first, n, pr)   the fused kernel of kind k over the run;
+ *   fold(first, n)       d_c's limbs (+)= d_a's where the result was left in d_a (moddown_no_fold: the in-place calls);
+ *   overlap              the error text if d_c overlaps d_a, else null -- formed by the caller, reported here in its place.
+ * pr: the P primes. */
+enum ModDownRun {
+  kModDownSandwich,  /* the inverse over the run, coef, the forward over the run; then fold */
+  kModDownFusedHere, /* fused, the result in d_a's Q limbs; then fold                     */
+  kModDownFusedInto  /* fused, the result where the call wants it: no fold                */
+};
+static int moddown_no_fold(int, int) { return NTT_OK; }
+
+template <class Kind, class Coef, class Fused, class Fold>
+static int moddown_route(int nq, int np, ntt_plan *const *plans, uint64_t *d_a, uint64_t batch, bool ntt_dom, void *stream, const Layout &alay,
+                         const char *overlap, Kind kind, Coef coef, Fused fused, Fold fold)
+{
+  const int                              nlimbs = nq + np;
+  const std::vector<std::pair<int, int>> runs   = rns_runs(nq, plans);
+  std::vector<ModDownRun>                kinds(runs.size(), kModDownSandwich);
+  if(ntt_dom) {
+    /* every table the call will need, before anything is written */
+    for(int j = nq; j < nlimbs; j++) {
+      if(!plans[j]->has_inv) return fail(NTT_ERR_ARG, "a P limb's plan lacks the inverse table");
+    }
+    for(size_t r = 0; r < runs.size(); r++) {
+      kinds[r] = kind(plans[runs[r].first]);
+      for(int l = runs[r].first; l < runs[r].first + runs[r].second; l++) {
+        if(!plans[l]->has_fwd) return fail(NTT_ERR_ARG, "a Q limb's plan lacks the forward table");
+        if(kinds[r] == kModDownSandwich && !plans[l]->has_inv) return fail(NTT_ERR_ARG, "a Q limb's plan lacks the inverse table (sandwich route)");
+      }
+    }
+  }
+  if(batch == 0) return NTT_OK;
+  if(overlap) return fail(NTT_ERR_ARG, overlap);
+  USE_DEVICE(plans[0]->device);
+  uint64_t pr[kBconvLimbs];
+  for(int j = 0; j < np; j++) pr[j] = plans[nq + j]->q;
+  const Layout one{alay.limb, alay.poly};
+  int          rc = NTT_OK;
+  if(!ntt_dom) {
+    for(int first = 0; !rc && first < nq; first += kBconvLimbs) rc = coef(first, nq - first < kBconvLimbs ? nq - first : kBconvLimbs, pr);
+    if(!rc) rc = fold(0, nq);
+    return rc;
+  }
+  rc = rns_transform(np, plans + nq, d_a + (uint64_t)nq * alay.limb, batch, true, stream, one);
+  for(size_t r = 0; !rc && r < runs.size(); r++) {
+    const int first = runs[r].first, n = runs[r].second;
+    if(kinds[r] != kModDownSandwich) {
+      rc = fused(kinds[r], first, n, pr);
+      if(kinds[r] == kModDownFusedInto) continue;
+    } else {
+      uint64_t *c = d_a + (uint64_t)first * alay.limb;
+      rc          = rns_transform(n, plans + first, c, batch, true, stream, one);
+      if(!rc) rc = coef(first, n, pr);
+      if(!rc) rc = rns_transform(n, plans + first, c, batch, false, stream, one);
+    }
+    if(!rc) rc = fold(first, n);
+  }
+  return rc;
 }
 
 static int rns_mod_down(int nq, int np, ntt_plan *const *plans, uint64_t *d_a, uint64_t batch, unsigned flags, void *stream,
@@ -257,47 +328,13 @@ static int rns_mod_down(int nq, int np, ntt_plan *const *plans, uint64_t *d_a, u
   rc = layout_check(plans[0]->N, nlimbs, batch, lay);
   if(!rc) rc = distinct_primes(nlimbs, plans);
   if(rc) return rc;
-  const bool                             ntt_dom   = (flags & NTT_MODDOWN_TRANSFORMED) != 0;
-  const bool                             floor_div = (flags & NTT_MODDOWN_FLOOR) != 0;
-  const std::vector<std::pair<int, int>> runs      = rns_runs(nq, plans);
-  if(ntt_dom) {
-    /* every table the call will need, before anything is written */
-    for(int j = nq; j < nlimbs; j++) {
-      if(!plans[j]->has_inv) return fail(NTT_ERR_ARG, "a P limb's plan lacks the inverse table");
-    }
-    for(const std::pair<int, int> &run : runs) {
-      const bool fused = rescale_fused_applies(plans[0], plans[run.first]);
-      for(int l = run.first; l < run.first + run.second; l++) {
-        if(!plans[l]->has_fwd) return fail(NTT_ERR_ARG, "a Q limb's plan lacks the forward table");
-        if(!fused && !plans[l]->has_inv) return fail(NTT_ERR_ARG, "a Q limb's plan lacks the inverse table (sandwich route)");
-      }
-    }
-  }
-  if(batch == 0) return NTT_OK;
-  USE_DEVICE(plans[0]->device);
-  uint64_t pr[kBconvLimbs];
-  for(int j = 0; j < np; j++) pr[j] = plans[nq + j]->q;
-  const Layout one{lay.limb, lay.poly};
-  if(!ntt_dom) {
-    for(int first = 0; !rc && first < nq; first += kBconvLimbs) {
-      rc = moddown_coef_launch(plans, first, nq - first < kBconvLimbs ? nq - first : kBconvLimbs, nq, np, d_a, batch, floor_div, stream, lay, pr);
-    }
-    return rc;
-  }
-  rc = rns_transform(np, plans + nq, d_a + (uint64_t)nq * lay.limb, batch, true, stream, one);
-  for(const std::pair<int, int> &run : runs) {
-    if(rc) break;
-    const int first = run.first, n = run.second;
-    if(rescale_fused_applies(plans[0], plans[first])) {
-      rc = moddown_fwd_launch(plans, first, n, nq, np, d_a, batch, floor_div, stream, lay, pr);
-      continue;
-    }
-    uint64_t *c = d_a + (uint64_t)first * lay.limb;
-    rc          = rns_transform(n, plans + first, c, batch, true, stream, one);
-    if(!rc) rc = moddown_coef_launch(plans, first, n, nq, np, d_a, batch, floor_div, stream, lay, pr);
-    if(!rc) rc = rns_transform(n, plans + first, c, batch, false, stream, one);
-  }
-  return rc;
+  const bool floor_div = (flags & NTT_MODDOWN_FLOOR) != 0;
+  return moddown_route(
+    nq, np, plans, d_a, batch, (flags & NTT_MODDOWN_TRANSFORMED) != 0, stream, lay, nullptr,
+    [&](const ntt_plan *p) { return rescale_fused_applies(plans[0], p) ? kModDownFusedHere : kModDownSandwich; },
+    [&](int first, int n, const uint64_t *pr) { return moddown_coef_launch(plans, first, n, nq, np, d_a, batch, floor_div, stream, lay, pr); },
+    [&](ModDownRun, int first, int n, const uint64_t *pr) { return moddown_fwd_launch(plans, first, n, nq, np, d_a, batch, floor_div, stream, lay, pr); },
+    moddown_no_fold);
 }
 
 extern "C" int ntt_rns_mod_down_batch(int nq, int np, ntt_plan *const *plans, uint64_t *d_a, uint64_t batch, unsigned flags, void *stream)

@@ -90,13 +90,7 @@ static int lift_fwd_launch(ntt_plan *const *plans, int first, int n, uint64_t *d
   la.max_grid = plans[first]->max_grid;
   la.num_cus  = plans[first]->num_cus;
   la.stream   = (hipStream_t)stream;
-  /* the run's coarsest headroom class (rns_for_runs); a run of 52-bit primes is all of the wide policy (rns_compatible) */
-  int kc = plans[first]->kcls;
-  for(int l = first + 1; l < first + n; l++) kc = plans[l]->kcls < kc ? plans[l]->kcls : kc;
-  const hipError_t e = kc == kWideClass ? launch_lift_fwd<ArithF64W, 0>(la)
-                       : kc == 18       ? launch_lift_fwd<ArithF64, 18>(la)
-                       : kc == 1        ? launch_lift_fwd<ArithF64, 1>(la)
-                                        : launch_lift_fwd<ArithF64, 0>(la);
+  const hipError_t e = with_f64_class(run_class(plans, first, n), [&](auto k) { return launch_lift_fwd<typename decltype(k)::A, decltype(k)::KSH>(la); });
   if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("lift_fwd_kernel: ") + hipGetErrorString(e));
   return NTT_OK;
 }

@@ -77,15 +77,8 @@ static int modup_mul_launch(ntt_plan *const *plans, int rf, int rn, int first, i
   ma.max_grid = plans[rf]->max_grid;
   ma.num_cus  = plans[rf]->num_cus;
   ma.stream   = (hipStream_t)stream;
-  /* the run's coarsest headroom class (rns_for_runs); a run of 52-bit primes is all of the wide policy (rns_compatible) */
-  int kc = plans[rf]->kcls;
-  for(int l = rf + 1; l < rf + rn; l++) kc = plans[l]->kcls < kc ? plans[l]->kcls : kc;
   const hipError_t e = with_int<1, 2>(ncomp, hipErrorInvalidValue, [&](auto nc) {
-    constexpr int NC = decltype(nc)::value;
-    return kc == kWideClass ? launch_modup_mul<ArithF64W, 0, NC>(ma)
-           : kc == 18       ? launch_modup_mul<ArithF64, 18, NC>(ma)
-           : kc == 1        ? launch_modup_mul<ArithF64, 1, NC>(ma)
-                            : launch_modup_mul<ArithF64, 0, NC>(ma);
+    return with_f64_class(run_class(plans, rf, rn), [&](auto k) { return launch_modup_mul<typename decltype(k)::A, decltype(k)::KSH, decltype(nc)::value>(ma); });
   });
   if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string(ncomp == 2 ? "modup_mul2_kernel: " : "modup_mul_kernel: ") + hipGetErrorString(e));
   return NTT_OK;

@@ -1171,11 +1171,7 @@ static int negacyclic_mul_ptrs_limb(const ntt_plan *p, const uint64_t *const *d_
     pa.num_cus      = p->num_cus;
     pa.oversub      = p->block_oversub;
     pa.stream       = (hipStream_t)stream;
-    const int  kc = eff_kcls(p);
-    hipError_t e  = kc == kWideClass ? launch_product<ArithF64W, 0>(pa)
-                    : kc == 18       ? launch_product<ArithF64, 18>(pa)
-                    : kc == 1        ? launch_product<ArithF64, 1>(pa)
-                                     : launch_product<ArithF64, 0>(pa);
+    const hipError_t e = with_f64_class(eff_kcls(p), [&](auto k) { return launch_product<typename decltype(k)::A, decltype(k)::KSH>(pa); });
     if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return NTT_OK;
   }
@@ -1207,11 +1203,7 @@ static int negacyclic_mul_ptrs_limb(const ntt_plan *p, const uint64_t *const *d_
       pa.ptrs         = 1;
       pa.ptr_limb_off = limb_off;
       pa.stream       = (hipStream_t)stream;
-      const int  kc = eff_kcls(p);
-      hipError_t e  = kc == kWideClass ? launch_team_product<ArithF64W, 0>(pa)
-                      : kc == 18       ? launch_team_product<ArithF64, 18>(pa)
-                      : kc == 1        ? launch_team_product<ArithF64, 1>(pa)
-                                       : launch_team_product<ArithF64, 0>(pa);
+      const hipError_t e = with_f64_class(eff_kcls(p), [&](auto k) { return launch_team_product<typename decltype(k)::A, decltype(k)::KSH>(pa); });
       if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
       return NTT_OK;
     }

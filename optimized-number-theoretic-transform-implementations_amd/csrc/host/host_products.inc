@@ -233,11 +233,7 @@ static int fused_product(const ntt_plan *p, uint64_t *d_c, uint64_t *d_a, uint64
       pa.team_lag    = p->team_lag ? p->team_lag : (p->m == kTeamBlock + 3 ? 20 : (p->m == kTeamBlock + 4 ? 14 : (four ? 8 : 12)));
       pa.team_wpc    = p->team_wpc;
       pa.stream      = (hipStream_t)stream;
-      const int  kc = eff_kcls(p);
-      hipError_t e = kc == kWideClass ? launch_team_product<ArithF64W, 0>(pa)
-                     : kc == 18       ? launch_team_product<ArithF64, 18>(pa)
-                     : kc == 1        ? launch_team_product<ArithF64, 1>(pa)
-                                           : launch_team_product<ArithF64, 0>(pa);
+      const hipError_t e = with_f64_class(eff_kcls(p), [&](auto k) { return launch_team_product<typename decltype(k)::A, decltype(k)::KSH>(pa); });
       if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
       return NTT_OK;
     }
@@ -278,11 +274,7 @@ static int fused_product(const ntt_plan *p, uint64_t *d_c, uint64_t *d_a, uint64
     pa.num_cus  = p->num_cus;
     pa.oversub  = p->block_oversub;
     pa.stream   = (hipStream_t)stream;
-    const int  kc = eff_kcls(p);
-    hipError_t e = kc == kWideClass ? launch_product<ArithF64W, 0>(pa)
-                   : kc == 18       ? launch_product<ArithF64, 18>(pa)
-                   : kc == 1        ? launch_product<ArithF64, 1>(pa)
-                                         : launch_product<ArithF64, 0>(pa);
+    const hipError_t e = with_f64_class(eff_kcls(p), [&](auto k) { return launch_product<typename decltype(k)::A, decltype(k)::KSH>(pa); });
     if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     for(int k = L.n - 2; k >= 0; k--) { /* inverse column passes of c, the last one ends the transform (N^-1) */
       rc = launch_one_pass(p, L.p[k], d_c + off, nb, true, false, false, k == 0, stream, ls);
@@ -462,6 +454,15 @@ static std::vector<unsigned char> rns_records(ntt_plan *const *plans, int first,
   std::vector<unsigned char> all;
   for(int l = first; l < first + n; l++) all.insert(all.end(), plans[l]->limbrec.begin(), plans[l]->limbrec.end());
   return all;
+}
+
+/* the coarsest headroom class of the run [first, first + n) (rns_for_runs); a run of 52-bit primes is all of the wide policy
+ * (rns_compatible) */
+static int run_class(ntt_plan *const *plans, int first, int n)
+{
+  int kc = plans[first]->kcls;
+  for(int l = first + 1; l < first + n; l++) kc = plans[l]->kcls < kc ? plans[l]->kcls : kc;
+  return kc;
 }
 
 /* the plan's own record as a one-limb set whose polynomials are lay.poly words apart */

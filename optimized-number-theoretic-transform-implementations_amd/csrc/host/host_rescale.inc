@@ -68,13 +68,7 @@ static int rescale_fwd_launch(ntt_plan *const *plans, int first, int n, uint64_t
   ra.max_grid = plans[first]->max_grid;
   ra.num_cus  = plans[first]->num_cus;
   ra.stream   = (hipStream_t)stream;
-  /* the run's coarsest headroom class (rns_for_runs); a run of 52-bit primes is all of the wide policy (rns_compatible) */
-  int kc = plans[first]->kcls;
-  for(int l = first + 1; l < first + n; l++) kc = plans[l]->kcls < kc ? plans[l]->kcls : kc;
-  const hipError_t e = kc == kWideClass ? launch_rescale_fwd<ArithF64W, 0>(ra)
-                       : kc == 18       ? launch_rescale_fwd<ArithF64, 18>(ra)
-                       : kc == 1        ? launch_rescale_fwd<ArithF64, 1>(ra)
-                                        : launch_rescale_fwd<ArithF64, 0>(ra);
+  const hipError_t e = with_f64_class(run_class(plans, first, n), [&](auto k) { return launch_rescale_fwd<typename decltype(k)::A, decltype(k)::KSH>(ra); });
   if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("rescale_fwd_kernel: ") + hipGetErrorString(e));
   return NTT_OK;
 }

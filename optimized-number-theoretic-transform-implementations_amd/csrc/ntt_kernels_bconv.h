@@ -1,7 +1,7 @@
 /*
  * ntt_kernels_bconv.h -- what the block kernels that reduce raw words in front of the forward block stages have in common
- * (modup_mul_kernel / modup_mul2_kernel, moddown_fwd_kernel, rescale_fwd_kernel): the [b^_i]_q table, the half-tile 128-bit
- * base conversion and the forward stage chain.  Included by ntt_kernels_modup_mul.h, ntt_kernels_keyswitch.h and
+ * (modup_mul_kernel / modup_mul2_kernel, the four kernels of moddown_fwd_body, rescale_fwd_kernel): the [b^_i]_q table, the half-tile 128-bit
+ * base conversion and the forward stage chain.  Included by ntt_kernels_modup_mul.h, ntt_kernels_moddown.h and
  * ntt_kernels_rescale.h, after the block kernels' pieces.
  *
  * Every piece is inlined into its caller and adds NO workgroup barrier (the stage chain has the exchanges' own, nothing else): where

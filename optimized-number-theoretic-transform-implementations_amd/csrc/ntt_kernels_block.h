@@ -191,6 +191,19 @@ template <int LO, int HI, class F> inline hipError_t with_int(int v, hipError_t 
   else return otherwise;
 }
 
+/* The grid and the launch of the kernels that run the forward block kernel's plain loop over whole polynomials, one limb per grid row
+ * (rescale, ModDown, ModUp products, lift): no oversubscription of the persistent sizes, four table-filling workgroups per slot below
+ * them; eights: the x extent a multiple of 8 (block_grid).  kr is the kernel's argument record, complete but for k.wgs_per_limb. */
+template <class G, class K, void (&Kernel)(const K)>
+inline hipError_t launch_plain_loop(K &kr, uint64_t nl, uint64_t batch, int num_cus, int max_grid, bool eights, hipStream_t stream)
+{
+  const uint64_t wgs = block_grid<G>(batch, 0, nl, num_cus, max_grid, G::PERSISTENT ? 1 : 4, eights);
+  if(batch == 0) return hipSuccess;
+  kr.k.wgs_per_limb = (uint32_t)wgs;
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)wgs, (unsigned)nl), dim3(G::WG), 0, stream, kr);
+  return hipGetLastError();
+}
+
 /* the launch's Params for this workgroup's limb; bid = its block id inside the limb's share of the grid */
 /* MULTI is a compile-time property of the kernel: with it off the limb is 0, every record field sits at a fixed offset of
  * the kernel-argument segment (the compiler re-loads such values at will instead of keeping them in registers) and the

@@ -3,25 +3,13 @@
  * the P limbs) for a run of Q limbs in ONE launch.  Included by the keyswitch_f64*.hip units only (the host layer sees the
  * launchers of ntt_keyswitch.h).
  *
- * rescale_fwd_kernel's structure (ntt_kernels_rescale.h) with one change, the prologue.  Per block of Q limb l (FP64 policies,
- * N = 2^6..2^14, one block = one polynomial):
- *   prologue  the np P limbs' blocks (already inverse-transformed) as raw words -- up to 2^61, not exact in a double -- are reduced
- *             in integer arithmetic to u_l = FastBConv_{P->q_l}([t + h]_P) - [h]_{q_l} (ntt_keyswitch.h), then converted;
- *   stages    the forward block stages, unchanged;
- *   epilogue  a quarter-tile at a time: c^ read in the last group's layout, (c^ - x) * P^-1 with the limb's FP64 constants.
- * 8N np bytes of t and 16N of c^ per limb-polynomial.  [p^_j]_{q_l} = prod_{k != j} p_k mod q_l is formed once per workgroup
- * (its limb is the grid's y index) into LDS: no table of np x nq words has room beside the run's limb records in the kernel
- * arguments.  With np = 1 the prologue is the rescale's (moddown_digit1).
+ * The in-place variant of moddown_fwd_body (ntt_kernels_moddown.h).  Per block of Q limb l:
+ *   prologue  u_l = FastBConv_{P->q_l}([t + h]_P) - [h]_{q_l} (ntt_keyswitch.h); with np = 1 the rescale's (moddown_digit1);
+ *   epilogue  (c^ - x) * P^-1, stored over c^.
+ * 8N np bytes of t and 16N of c^ per limb-polynomial.
  */
 #pragma once
-#include <hip/hip_runtime.h>
-
-/* the block kernels' pieces (Geom, KArgs, limb_params, the stage groups and exchanges) -- not all of ntt_kernels.h, whose launch
- * section defines a kernel of its own (team_ctl_clear_kernel) in every unit that includes it */
-#include "ntt_core.h"
-#include "ntt_passplan.h"
-#include "ntt_kernels_block.h"
-#include "ntt_kernels_bconv.h"
+#include "ntt_kernels_moddown.h"
 
 namespace ntt {
 
@@ -37,87 +25,12 @@ template <class A, int LOGN, int KSH>
 __global__ void __launch_bounds__((Geom<LOGN, false, flavor_of<A>()>::WG), (Geom<LOGN, false, flavor_of<A>()>::WPS))
   moddown_fwd_kernel(const KModDown<A> kr)
 {
-  static_assert(A::kCompact, "built for the FP64 policies");
-  uint32_t        bid, gdim, limb;
-  const Params<A> p = limb_params<A, false, true>(kr.k, bid, gdim, limb);
-  using P = Plan<LOGN>;
-  using G = Geom<LOGN, false, flavor_of<A>()>;
-  constexpr uint32_t MASK   = fused_mask<A, LOGN, false, KSH>();
-  constexpr int      LDS_TW = G::LDS_TW;
-  __shared__ typename A::val lds_all[G::BPW * P::LDS_ELEMS + LDS_TW];
-  __shared__ uint64_t        ghat[kBconvLimbs]; /* [p^_j]_{q_l} */
-  const uint32_t       tid = threadIdx.x;
-  const uint32_t       sub = tid >> P::LT;
-  const uint32_t       t   = tid & (P::T - 1);
-  typename A::val *    lds = lds_all + sub * P::LDS_ELEMS;
-  const BconvDst       ql  = kr.ql[limb];
-  const int            np  = kr.np;
-  const lds_ctw_ptr<A> gtw = (lds_ctw_ptr<A>)reinterpret_cast<typename A::ctw *>(lds_all + G::BPW * P::LDS_ELEMS);
-  if constexpr(LDS_TW > 0) fill_lds_tables<A, LOGN, false>(reinterpret_cast<typename A::ctw *>(lds_all + G::BPW * P::LDS_ELEMS), p, 0u, tid);
-  if(np > 1) bconv_ghat(ghat, kr.pl, np, ql, tid);
-  if constexpr(LDS_TW > 0) __syncthreads();
-  else if(np > 1) __syncthreads();
-  /* P^-1 mod q_l as a balanced double, |.| <= q/2 (the multiplier of every product of this workgroup) */
-  const double sb = A::reduce(A::u64_to_f64_lt52(ql.s), p.c);
-  for(uint64_t b0 = (uint64_t)bid * G::BPW; b0 < p.nblocks; b0 += (uint64_t)gdim * G::BPW) {
-    uint64_t   b    = b0 + sub;
-    const bool live = b < p.nblocks;
-    if(!live) b = p.nblocks - 1;
-    const uint64_t  off  = blk_off<LOGN>(p, b); /* (whole polynomials: s0 = 0) */
-    const uint64_t *tblk = kr.t + off;
-    uint64_t *      cblk = p.a + off;
-    uint32_t        tg   = t; /* (an opaque copy per block, as fwd_mul_kernel's plain loop) */
-    asm volatile("" : "+v"(tg));
-    typename A::val x[kE];
-    {
-      uint64_t raw[kE];
-      if(np == 1) {
-        const BconvSrc s0 = kr.pl[0];
-        static_for<0, kE>([&](auto ee) {
-          constexpr int   E   = decltype(ee)::value;
-          const uint64_t *row = tblk + ((uint32_t)E << P::LT);
-          raw[E]              = moddown_digit1(stream_load(coef_at(row, tg)), s0, ql);
-        });
-      } else {
-        bconv_tile<P::LT>(raw, tblk, kr.k.limb_stride, kr.pl, ghat, np, tg, [&](uint64_t hi, uint64_t lo) { return moddown_digit(hi, lo, ql); });
-      }
-      convert_inputs<A, false>(x, raw, false, p.c);
-    }
-    fwd_block_stages<A, LOGN, MASK>(x, tg, p, lds, gtw);
-    static_for<0, 4>([&](auto qq) {
-      constexpr int Q = decltype(qq)::value;
-      uint64_t      rc[kE], u[kE];
-      sched_fence();
-      load_last_raw<LOGN, 4 * Q, 4 * Q + 4>(rc, tg, cblk);
-      static_for<4 * Q, 4 * Q + 4>([&](auto ee) {
-        constexpr int E = decltype(ee)::value;
-        const double  d = A::reduce(A::u64_to_f64_lt52(rc[E]) - A::reduce(x[E], p.c), p.c); /* |c^ - x| < 1.5 q before */
-        u[E]            = A::mul_store(A::mulmod_c(sb, d, p.c), p.c);
-      });
-      if(live) store_last_raw<LOGN, 4 * Q, 4 * Q + 4>(u, tg, cblk);
-      sched_fence();
-    });
-  }
+  moddown_fwd_body<A, LOGN, KSH, kModDownInPlace>(kr);
 }
 
 template <class A, int LOGN, int KSH> hipError_t launch_moddown_fwd_n(const ModDownFwdArgs &ma)
 {
-  using G = Geom<LOGN, false, flavor_of<A>()>;
-  if(ma.nlimbs < 1 || ma.nlimbs > kBconvLimbs || ma.nlimbs > kMaxLimbs || ma.np < 1 || ma.np > kBconvLimbs) return hipErrorInvalidValue;
-  KModDown<A>    kr{};
-  const uint64_t nl = (uint64_t)ma.nlimbs;
-  fill_kargs(kr.k, ma.c, ma.limbs, nl, ma.limb_stride, ma.poly_stride, ma.logn, 0, ma.batch);
-  for(int l = 0; l < ma.nlimbs; l++) kr.ql[l] = ma.ql[l];
-  for(int j = 0; j < ma.np; j++) kr.pl[j] = ma.pl[j];
-  kr.t  = ma.t;
-  kr.np = ma.np;
-  /* the plain loop of the forward block kernel: no oversubscription of the persistent sizes, four table-filling workgroups per
-   * slot below them; the x extent a multiple of 8 (the header's note on the XCDs) */
-  const uint64_t wgs = block_grid<G>(ma.batch, 0, nl, ma.num_cus, ma.max_grid, G::PERSISTENT ? 1 : 4, true);
-  if(ma.batch == 0) return hipSuccess;
-  kr.k.wgs_per_limb = (uint32_t)wgs;
-  hipLaunchKernelGGL((moddown_fwd_kernel<A, LOGN, KSH>), dim3((unsigned)wgs, (unsigned)nl), dim3(G::WG), 0, ma.stream, kr);
-  return hipGetLastError();
+  return launch_moddown_variant_n<A, LOGN, KModDown<A>, moddown_fwd_kernel<A, LOGN, KSH>>(ma, [](KModDown<A> &) {});
 }
 
 #define NTT_DEFINE_LAUNCH_MODDOWN_FWD(A, KSH)                                                                                                   \

@@ -121,11 +121,7 @@ template <class A, int LOGN, int KSH> hipError_t launch_lift_fwd_n(const LiftFwd
   kl.call[0]       = la.call;
   kl.accumulate    = la.call.accumulate;
   /* rescale_fwd_kernel's grid: the plain loop of the forward block kernel, the x extent a multiple of 8 */
-  const uint64_t wgs = block_grid<G>(la.batch, 0, nl, la.num_cus, la.max_grid, G::PERSISTENT ? 1 : 4, true);
-  if(la.batch == 0) return hipSuccess;
-  kl.k.wgs_per_limb = (uint32_t)wgs;
-  hipLaunchKernelGGL((lift_fwd_kernel<A, LOGN, KSH>), dim3((unsigned)wgs, (unsigned)nl), dim3(G::WG), 0, la.stream, kl);
-  return hipGetLastError();
+  return launch_plain_loop<G, KLift<A>, lift_fwd_kernel<A, LOGN, KSH>>(kl, nl, la.batch, la.num_cus, la.max_grid, true, la.stream);
 }
 
 #define NTT_DEFINE_LAUNCH_LIFT_FWD(A, KSH)                                                                                                \

@@ -28,7 +28,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-/* the block kernels' pieces (see ntt_kernels_keyswitch.h on why not all of ntt_kernels.h) */
+/* the block kernels' pieces (see ntt_kernels_moddown.h on why not all of ntt_kernels.h) */
 #include "ntt_core.h"
 #include "ntt_passplan.h"
 #include "ntt_kernels_block.h"
@@ -171,12 +171,9 @@ template <class A, int LOGN, int KSH, int NC> hipError_t launch_modup_mul_n(cons
   kr.count         = ma.count;
   /* moddown_fwd_kernel's grid: the plain loop of the forward block kernel, the x extent a multiple of 8 so that the limb-blocks
    * reading one block of the digit share blockIdx % 8 (speed only).  NTT_OPT_MAX_GRID is taken as it stands (per limb at least 1). */
-  const uint64_t wgs = block_grid<G>(ma.batch, 0, nl, ma.num_cus, ma.max_grid, G::PERSISTENT ? 1 : 4, ma.max_grid <= 0);
-  if(ma.batch == 0) return hipSuccess;
-  kr.k.wgs_per_limb = (uint32_t)wgs;
-  if constexpr(NC == 1) hipLaunchKernelGGL((modup_mul_kernel<A, LOGN, KSH>), dim3((unsigned)wgs, (unsigned)nl), dim3(G::WG), 0, ma.stream, kr);
-  else hipLaunchKernelGGL((modup_mul2_kernel<A, LOGN, KSH>), dim3((unsigned)wgs, (unsigned)nl), dim3(G::WG), 0, ma.stream, kr);
-  return hipGetLastError();
+  const bool eights = ma.max_grid <= 0;
+  if constexpr(NC == 1) return launch_plain_loop<G, KModUpMul<A, 1>, modup_mul_kernel<A, LOGN, KSH>>(kr, nl, ma.batch, ma.num_cus, ma.max_grid, eights, ma.stream);
+  else return launch_plain_loop<G, KModUpMul<A, 2>, modup_mul2_kernel<A, LOGN, KSH>>(kr, nl, ma.batch, ma.num_cus, ma.max_grid, eights, ma.stream);
 }
 
 #define NTT_DEFINE_LAUNCH_MODUP_MUL(A, KSH, NC)                                       \

@@ -103,13 +103,8 @@ template <class A, int LOGN, int KSH> hipError_t launch_rescale_fwd_n(const Resc
   kr.t  = ra.t;
   kr.qL = ra.qL;
   kr.hL = ra.hL;
-  /* the plain loop of the forward block kernel: no oversubscription of the persistent sizes, four table-filling workgroups per
-   * slot below them; the x extent a multiple of 8 (the header's note on the XCDs) */
-  const uint64_t wgs = block_grid<G>(ra.batch, 0, nl, ra.num_cus, ra.max_grid, G::PERSISTENT ? 1 : 4, true);
-  if(ra.batch == 0) return hipSuccess;
-  kr.k.wgs_per_limb = (uint32_t)wgs;
-  hipLaunchKernelGGL((rescale_fwd_kernel<A, LOGN, KSH>), dim3((unsigned)wgs, (unsigned)nl), dim3(G::WG), 0, ra.stream, kr);
-  return hipGetLastError();
+  /* the x extent a multiple of 8 (the header's note on the XCDs) */
+  return launch_plain_loop<G, KRescale<A>, rescale_fwd_kernel<A, LOGN, KSH>>(kr, nl, ra.batch, ra.num_cus, ra.max_grid, true, ra.stream);
 }
 
 #define NTT_DEFINE_LAUNCH_RESCALE_FWD(A, KSH)                                                                                                   \

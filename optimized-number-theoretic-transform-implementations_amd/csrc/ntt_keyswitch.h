@@ -2,7 +2,8 @@
  * ntt_keyswitch.h -- launchers of the RNS base-conversion kernels of hybrid key switching (ntt_rns_mod_up_batch,
  * ntt_rns_mod_down_batch): the host layer's view of them, and the integer arithmetic they share.
  *
- * The kernel templates live in ntt_kernels_keyswitch.h (moddown_fwd_kernel, instantiated in keyswitch_f64*.hip), in
+ * The kernel templates live in ntt_kernels_keyswitch.h (moddown_fwd_kernel, instantiated in keyswitch_f64*.hip; its body,
+ * moddown_fwd_body of ntt_kernels_moddown.h, is also that of the ksfold, BGV and exact ModDown kernels), in
  * ntt_kernels_modup_mul.h (modup_mul_kernel, modup_mul2_kernel; modup_mul_f64*.hip, modup_mul2_f64*.hip) and in keyswitch_coef.hip
  * (bconv_kernel, moddown_coef_kernel); this header declares the argument records and the launchers, nothing
  * that the host translation unit would instantiate.

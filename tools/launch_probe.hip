@@ -1,6 +1,6 @@
 /*
- * launch_probe.hip -- what every launcher of csrc/ntt_kernels_launch.h, ntt_kernels_rescale.h and ntt_kernels_keyswitch.h WOULD launch,
- * recorded instead of launched: a host-only program (no device, no HIP call) for comparing two versions of the launch layer.
+ * launch_probe.hip -- what every launcher of csrc/ntt_kernels_launch.h, ntt_kernels_rescale.h and the four fused ModDown headers
+ * (ntt_kernels_keyswitch.h, ntt_kernels_ksfold.h, ntt_kernels_bgv.h, ntt_kernels_exact.h) WOULD launch, recorded instead of launched: a host-only program (no device, no HIP call) for comparing two versions of the launch layer.
  *
  *   make launch-probe            builds build/launch_probe_<pair> for every (policy, class) pair the library instantiates
  *   make launch-probe PROBE_CSRC=<another csrc> PROBE_OUT=build/other      the same source against another version of the headers
@@ -51,6 +51,9 @@ template <class... T> static void record(const char *name, dim3 g, dim3 b, const
 #if PROBE_KIND == 1
 #include "ntt_kernels_rescale.h"
 #include "ntt_kernels_keyswitch.h"
+#include "ntt_kernels_ksfold.h"
+#include "ntt_kernels_bgv.h"
+#include "ntt_kernels_exact.h"
 #endif
 
 namespace ntt {
@@ -68,6 +71,9 @@ NTT_DEFINE_LAUNCH_PRODUCT(PROBE_POLICY, PROBE_KSH)
 NTT_DEFINE_LAUNCH_TEAM_PRODUCT(PROBE_POLICY, PROBE_KSH)
 NTT_DEFINE_LAUNCH_RESCALE_FWD(PROBE_POLICY, PROBE_KSH)
 NTT_DEFINE_LAUNCH_MODDOWN_FWD(PROBE_POLICY, PROBE_KSH)
+NTT_DEFINE_LAUNCH_KSFOLD_FWD(PROBE_POLICY, PROBE_KSH)
+NTT_DEFINE_LAUNCH_MODDOWN_BGV_FWD(PROBE_POLICY, PROBE_KSH)
+NTT_DEFINE_LAUNCH_MODDOWN_EXACT_FWD(PROBE_POLICY, PROBE_KSH)
 #endif
 } /* namespace ntt */
 
@@ -208,6 +214,28 @@ static void sweep_rescale_moddown(uint32_t logn)
             ma.max_grid = mg, ma.num_cus = cus;
             if(!probe::quiet) printf("moddown %u b%llu l%d p%d c%d g%d\n", logn, (unsigned long long)batch, nlimbs, np, cus, mg);
             done(launch_moddown_fwd<A, KSH>(ma));
+            /* the other variants of the fused ModDown over the same record: distinct constants in every array a launcher copies */
+            for(int i = 0; i < kBconvLimbs; i++) {
+              ma.pl[i].p = 1000003 + 2 * i, ma.pl[i].inv = 7 + i;
+              ma.ql[i].q = 2000003 + 2 * i, ma.ql[i].s = 11 + i;
+            }
+            for(int form = 0; form < 3; form++) { /* overwrite, dense; accumulate, dense; accumulate, padded strides */
+              KsFoldArgs ka{};
+              ka.m = ma, ka.accumulate = form > 0;
+              ka.out_limb_stride = form == 2 ? (batch << logn) + 64 : batch << logn, ka.out_poly_stride = form == 2 ? (1ull << logn) + 8 : 0;
+              if(!probe::quiet) printf("ksfold %u b%llu l%d p%d c%d g%d f%d\n", logn, (unsigned long long)batch, nlimbs, np, cus, mg, form);
+              done(launch_ksfold_fwd<A, KSH>(ka));
+              ModDownBgvArgs ba{};
+              ba.k = ka;
+              for(int i = 0; i < kBconvLimbs; i++) ba.ts[i] = BgvScale{65537ull + i, 3ull + i};
+              if(!probe::quiet) printf("bgv %u b%llu l%d p%d c%d g%d f%d\n", logn, (unsigned long long)batch, nlimbs, np, cus, mg, form);
+              done(launch_moddown_bgv_fwd<A, KSH>(ba));
+            }
+            ModDownExactFwdArgs xa{};
+            xa.ma = ma;
+            for(int i = 0; i < kBconvLimbs; i++) xa.rho[i] = 1.0 / (double)(1000003 + 2 * i), xa.mq[i] = 5 + i;
+            if(!probe::quiet) printf("exact %u b%llu l%d p%d c%d g%d\n", logn, (unsigned long long)batch, nlimbs, np, cus, mg);
+            done(launch_moddown_exact_fwd<A, KSH>(xa));
           }
         }
 }
