@@ -153,6 +153,10 @@ typedef enum ntt_option {
                           * lift in its prologue; 0 = every run takes the composition (the element-wise launch, then the forward
                           * transform; accumulating, the inverse transform first); -1 (default) = the rule quoted at
                           * ntt_rns_from_plain_batch.  Read from plans[0]; results are identical */
+  NTT_OPT_SLOTS_FUSED = 23, /* ntt_slots_encode_batch, ntt_slots_decode_batch: 1 = the fused kernels wherever they are built (FP64
+                          * policies, N = 2^6..2^14): ONE launch, the slot permutation applied by the transform's own loads / stores;
+                          * 0 = the composition everywhere (the element-wise permutation launch and the plan's transform in place);
+                          * -1 (default) = the rule quoted at ntt_slots_encode_batch.  Results are identical */
   NTT_OPT_FUSED_PRODUCT = 5 /* N = 2^8..2^17, FP64: 1 (default) = ntt_negacyclic_mul_batch as ONE launch that takes both
                           * operands through the forward stages, multiplies in registers and runs the inverse: 24N bytes up to
                           * 2^14; from 2^23 coefficients per operand of N >= 2^15 on likewise one launch (all limbs of an RNS set
@@ -191,7 +195,7 @@ NTT_API int  ntt_plan_info(const ntt_plan *p, uint64_t info[8]);
 /* copy a device table back (tests / debugging): which = 0 forward records, 1 inverse records (+16 folded N^-1 records),
  * 2 / 3 the FP64 policy's compact forward / inverse tables.  Records are 16 bytes: {w, floor(w 2^64/q)} as two
  * uint64_t (integer policies; 2N records of the expanded table for NTT_ARITH_U64_R4) or {balanced w, w/q} as two
- * doubles (FP64). */
+ * doubles (FP64).  which = 4 / 5: the slot tables pos / ipos (after ntt_plan_enable_slots), N uint32_t each. */
 NTT_API int  ntt_plan_export_table(const ntt_plan *p, int which, void *h_dst, size_t bytes);
 /* force the strided multi-pass path (self-check of the fused kernels) */
 NTT_API int  ntt_plan_set_generic(ntt_plan *p, int on);
@@ -839,6 +843,57 @@ NTT_API int ntt_rns_from_double_batch(int nlimbs, ntt_plan *const *plans, uint64
 NTT_API int ntt_rns_from_double_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, const double *d_y, double scale,
                                               uint64_t c_limb_stride, uint64_t c_poly_stride, uint64_t y_poly_stride, uint64_t batch,
                                               unsigned flags, void *stream);
+
+/* ---- BFV / BGV slots: encode and decode, fused with the transform mod t.  Everything above speaks of a plaintext as N coefficients
+ * mod t; a BFV / BGV user holds N SLOTS, a 2 x N/2 matrix of values mod t.  pt is a plan for (N, t, psi): t prime, 2N | t - 1, psi its
+ * primitive 2N-th root, m = log2 N, h = N / 2.  The forward transform stores a(psi^(2 bitrev_m(s) + 1)) at word s (the fact the
+ * NTT-domain Galois formula above rests on).  The convention: generator 5, rows = the sign of the exponent.
+ *     slot index   i = r h + j, row r in {0, 1}, column 0 <= j < h
+ *     exponent     e(i) = 5^j mod 2N for r = 0,  2N - (5^j mod 2N) for r = 1
+ *     position     pos(i) = bitrev_m((e(i) - 1) / 2): a permutation of 0..N-1, the identity for N = 2 (ntt_slot_position)
+ *     decode       v[i] = fwd(a)[pos(i)] = a(psi^e(i))
+ *     encode       a = inv(a^) with a^[pos(i)] = v[i]: the unique a of degree < N with a(psi^e(i)) = v[i]; decode(encode(v)) = v
+ * Consequences: products of polynomials (ntt_negacyclic_mul_batch on pt; the RNS products after a lift) are slot-wise products;
+ * sigma_g with g = ntt_galois_rotation(N, r) rotates BOTH rows left by r -- new (row, j) holds the old (row, (j + r) mod h); g = 2N - 1
+ * swaps the two rows.
+ * ntt_plan_enable_slots builds the two index tables pos and ipos (N uint32_t each) on the device, one thread per slot (5^j by
+ * square-and-multiply, ipos by scattering); idempotent; it allocates and synchronises, so call it outside stream capture; the tables
+ * are freed with the plan, and a plan that never calls it costs nothing more.  ntt_slot_position(N, i) is pos(i) on the host
+ * (UINT64_MAX for an N that is no power of two >= 2, or i >= N).
+ * ntt_slots_encode_batch: d_a ([batch][N] coefficients) = encode(d_v ([batch][N] slots)); d_v is left untouched.
+ * ntt_slots_decode_batch: d_v = decode(d_a).  It CONSUMES d_a: on return its words are unspecified (the fused route leaves them, the
+ * composition has transformed them in place).  Words are canonical in [0, t) on both sides (unchecked).  flags must be 0.
+ * _strided: the slot side's polynomials v_poly_stride and the coefficient side's a_poly_stride words apart, each >= N.
+ * Routes (identical words; NTT_OPT_SLOTS_FUSED on pt selects):
+ *     fused        FP64 policies, N = 2^6..2^14, ONE launch: slots_inv_kernel -- the inverse block stages, each lane loading v[ipos[s]]
+ *                  for the positions s it would have loaded --, slots_fwd_kernel -- the forward block stages storing word s to
+ *                  v[ipos[s]].  One polynomial is one workgroup, so every gathered or scattered line is in that workgroup's own
+ *                  <= 128 KiB; the 4N-byte table is shared by the batch.  16N bytes per polynomial.
+ *     composition  every policy, every N >= 2 (N < 2^6, N >= 2^15, NTT_ARITH_U64 plans for t >= 2^52): the element-wise
+ *                  slots_perm_kernel (out[p][s] = in[p][tab[s]]) and the plan's transform in place on d_a.  32N bytes.
+ * The default (-1) follows the measurement (profiles/r21/slots_bench.txt, t = 65537, 2^13 / 2^14, 64 / 1024 polynomials, composition
+ * time / fused time as ranges over five alternating rounds, a figure's own spread 1.00-1.04; the rule with its figures:
+ * csrc/host/host_slots.inc): encode is fused wherever built (1.40-1.61 at 64 polynomials, 2.33-2.39 at 1024); decode is fused through
+ * 2^13 (1.19-1.20 / 1.84-1.86) and composed at 2^14 (1.30-1.33 at 64, but 0.96-0.98 at 1024: the scattered stores of a full chip cost
+ * more than the launch they save).  Against the detour a caller had before (a torch gather with an index tensor of its own around
+ * ntt_inv_batch / ntt_fwd_batch) the fused calls take 1/1.15-1/3.92 of the time.  They reach 0.15-0.40 of ntt_copy_probe's rate at
+ * 16N bytes per polynomial (the composition 0.12-0.25).
+ * NTT_OPT_MAX_GRID of pt is honoured.  Allocate nothing, do not synchronise the host, issue no memset: capturable.
+ * NTT_ERR_ARG, nothing written: a plan without slot tables; a plan that lacks the inverse (encode) or forward (decode) table; a null
+ * pointer with batch > 0; a stride below N; any overlap of the two spans of words; any flag.  batch = 0 is NTT_OK.
+ *
+ * Recipes (BGV; BFV with NTT_LIFT_SCALE / NTT_PLAIN_SCALE):
+ *     slots -> plaintext operand   ntt_slots_encode_batch(pt, d_m, d_v, batch, 0, s), then ntt_rns_from_plain_batch(L, plans, d_c, d_m, t, ..)
+ *     decryption -> slots          ntt_rns_to_plain_batch(L, plans, d_m, d_a, t, ..), then ntt_slots_decode_batch(pt, d_v, d_m, batch, 0, s)
+ * (examples/rns_slots.c). ---- */
+NTT_API int      ntt_plan_enable_slots(ntt_plan *p);
+NTT_API uint64_t ntt_slot_position(uint64_t N, uint64_t i);
+NTT_API int ntt_slots_encode_batch(const ntt_plan *pt, uint64_t *d_a, const uint64_t *d_v, uint64_t batch, unsigned flags, void *stream);
+NTT_API int ntt_slots_encode_batch_strided(const ntt_plan *pt, uint64_t *d_a, const uint64_t *d_v, uint64_t v_poly_stride,
+                                           uint64_t a_poly_stride, uint64_t batch, unsigned flags, void *stream);
+NTT_API int ntt_slots_decode_batch(const ntt_plan *pt, uint64_t *d_v, uint64_t *d_a, uint64_t batch, unsigned flags, void *stream);
+NTT_API int ntt_slots_decode_batch_strided(const ntt_plan *pt, uint64_t *d_v, uint64_t *d_a, uint64_t v_poly_stride, uint64_t a_poly_stride,
+                                           uint64_t batch, unsigned flags, void *stream);
 
 /* ---- caller-native layouts (round 5).  The entry points above take RNS operands as [limb][batch][N].  SURVEY 8(d) config 5
  * -- and every FHE library -- keeps a polynomial's limbs side by side: [batch][prime][N].  The *_strided forms take the two

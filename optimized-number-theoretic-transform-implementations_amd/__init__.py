@@ -49,6 +49,7 @@ OPT_PAIR_FUSED = 19
 OPT_MODDOWN_ADD_FUSED = 20
 OPT_BGV_FUSED = 21
 OPT_LIFT_FUSED = 22
+OPT_SLOTS_FUSED = 23
 RESCALE_TRANSFORMED, RESCALE_FLOOR = 1, 2
 MODUP_TRANSFORMED = 1
 MODDOWN_TRANSFORMED, MODDOWN_FLOOR, MODDOWN_ACCUMULATE = 1, 2, 4
@@ -79,6 +80,8 @@ EXPORTED_SYMBOLS = [
     "ntt_rns_galois_dot_batch_strided", "ntt_rns_lincomb_batch", "ntt_rns_lincomb_batch_strided",
     "ntt_rns_to_plain_batch", "ntt_rns_to_plain_batch_strided", "ntt_rns_to_double_batch", "ntt_rns_to_double_batch_strided",
     "ntt_rns_from_plain_batch", "ntt_rns_from_plain_batch_strided", "ntt_rns_from_double_batch", "ntt_rns_from_double_batch_strided",
+    "ntt_plan_enable_slots", "ntt_slot_position", "ntt_slots_encode_batch", "ntt_slots_encode_batch_strided", "ntt_slots_decode_batch",
+    "ntt_slots_decode_batch_strided",
     "ntt_transform_batch_strided", "ntt_transform_ptrs", "ntt_rns_transform_ptrs", "ntt_transform_dev_ptrs", "ntt_rns_transform_dev_ptrs", "ntt_inv_dot_dev_ptrs", "ntt_fwd_mul_dev_ptrs", "ntt_negacyclic_mul_dev_ptrs",
     "ntt_rns_inv_dot_dev_ptrs", "ntt_rns_fwd_mul_dev_ptrs", "ntt_rns_negacyclic_mul_dev_ptrs", "ntt_dev_malloc", "ntt_dev_free", "ntt_dev_mem_info",
     "ntt_h2d", "ntt_d2h", "ntt_stream_create", "ntt_stream_destroy", "ntt_stream_sync",
@@ -127,6 +130,11 @@ _sig("ntt_plan_set_option", C.c_int, VOIDP, C.c_int, C.c_int64)
 _sig("ntt_plan_reserve", C.c_int, VOIDP, VOIDP, C.c_uint64)
 _sig("ntt_plan_get_option", C.c_int, VOIDP, C.c_int, C.POINTER(C.c_int64))
 _sig("ntt_plan_export_table", C.c_int, VOIDP, C.c_int, VOIDP, C.c_size_t)
+_sig("ntt_plan_enable_slots", C.c_int, VOIDP)
+_sig("ntt_slot_position", C.c_uint64, C.c_uint64, C.c_uint64)
+for _n in ("ntt_slots_encode_batch", "ntt_slots_decode_batch"):
+    _sig(_n, C.c_int, VOIDP, VOIDP, VOIDP, C.c_uint64, C.c_uint, VOIDP)
+    _sig(_n + "_strided", C.c_int, VOIDP, VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 for _n in ("ntt_fwd_batch", "ntt_inv_batch", "ntt_fwd_batch_wide", "ntt_inv_batch_wide", "ntt_fwd_batch_lazy",
            "ntt_inv_batch_lazy"):
     _sig(_n, C.c_int, VOIDP, VOIDP, C.c_uint64, VOIDP)
@@ -415,6 +423,17 @@ class Plan:
         out = np.zeros(n_records * width, dtype=dtype)
         _check(_lib.ntt_plan_export_table(self.h, which, out.ctypes.data, out.nbytes))
         return out.reshape(n_records, width) if width == 2 else out
+
+    def enable_slots(self):
+        """ntt_plan_enable_slots: builds the slot tables pos / ipos on the device (idempotent; outside stream capture)"""
+        _check(_lib.ntt_plan_enable_slots(self.h))
+        return self
+
+    def slot_table(self, inverse=False):
+        """the device table pos (inverse: ipos) as N uint32"""
+        out = np.zeros(self.N, dtype=np.uint32)
+        _check(_lib.ntt_plan_export_table(self.h, 5 if inverse else 4, out.ctypes.data, out.nbytes))
+        return out
 
     def set_option(self, option, value):
         _check(_lib.ntt_plan_set_option(self.h, option, value))
@@ -843,6 +862,26 @@ def rns_from_double(plans, dc, dy, scale, batch, flags=0, stream=None, layout=No
         _check(_lib.ntt_rns_from_double_batch_strided(len(plans), _plan_array(plans), dc, dy, scale, layout[0], layout[1], layout[2], batch,
                                                       flags, stream))
     else: _check(_lib.ntt_rns_from_double_batch(len(plans), _plan_array(plans), dc, dy, scale, batch, flags, stream))
+
+
+def slot_position(n, i):
+    """pos(i): the word of the forward transform that holds slot i = row * N/2 + column (None for a bad N or i)"""
+    v = int(_lib.ntt_slot_position(n, i))
+    return None if v == (1 << 64) - 1 else v
+
+
+def slots_encode(plan, da, dv, batch, flags=0, stream=None, layout=None):
+    """BFV / BGV: da ([batch][N] coefficients mod t) = the polynomial whose slots are dv ([batch][N], row-major 2 x N/2); dv is left
+    untouched.  plan: a plan for (N, t, psi) with enable_slots().  layout = (v_poly_stride, a_poly_stride) in words for padded
+    placements; OPT_SLOTS_FUSED on the plan selects the route"""
+    if layout is not None: _check(_lib.ntt_slots_encode_batch_strided(plan.h, da, dv, layout[0], layout[1], batch, flags, stream))
+    else: _check(_lib.ntt_slots_encode_batch(plan.h, da, dv, batch, flags, stream))
+
+
+def slots_decode(plan, dv, da, batch, flags=0, stream=None, layout=None):
+    """dv = the slots of the polynomials da; da is CONSUMED (its words are unspecified on return).  layout as slots_encode"""
+    if layout is not None: _check(_lib.ntt_slots_decode_batch_strided(plan.h, dv, da, layout[0], layout[1], batch, flags, stream))
+    else: _check(_lib.ntt_slots_decode_batch(plan.h, dv, da, batch, flags, stream))
 
 
 def batch_multi(plans, dptrs, batches, inverse=False):

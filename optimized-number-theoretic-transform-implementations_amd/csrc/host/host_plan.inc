@@ -180,6 +180,10 @@ struct ntt_plan {
                                       * -1 = where the recorded measurement says it is not slower (bgv_fused_applies); plans[0] */
   int              lift_fused = -1;  /* the lifts with NTT_LIFT_TRANSFORMED: 1 = lift_fwd_kernel where it is built, 0 = the composition
                                       * everywhere, -1 = the default rule (lift_fused_applies); plans[0] */
+  int              slots_fused = -1; /* ntt_slots_encode_batch, ntt_slots_decode_batch: 1 = slots_inv_kernel / slots_fwd_kernel where they are
+                                      * built, 0 = the composition everywhere, -1 = the default rule (slots_fused_applies) */
+  uint32_t *       d_pos  = nullptr; /* slot tables (ntt_plan_enable_slots; ntt_slots.h): pos and its inverse, N words each; null */
+  uint32_t *       d_ipos = nullptr; /* until enabled */
   int              block_oversub = 0; /* persistent block kernels: workgroups per resident slot (0 = the kernels' defaults) */
   int              num_cus    = 256;
   int              chunk_mib  = 256; /* bytes of one multi-pass chunk (Infinity Cache residency) */
@@ -496,6 +500,8 @@ extern "C" void ntt_plan_destroy(ntt_plan *p)
   if(p->d_inv) (void)hipFree(p->d_inv);
   if(p->d_fwd8) (void)hipFree(p->d_fwd8);
   if(p->d_inv8) (void)hipFree(p->d_inv8);
+  if(p->d_pos) (void)hipFree(p->d_pos);
+  if(p->d_ipos) (void)hipFree(p->d_ipos);
   for(const ntt_plan::TeamBuf &tb : p->team_bufs) {
     if(tb.d) (void)hipFree(tb.d);
     if(tb.g) (void)hipFree(tb.g);
@@ -544,6 +550,14 @@ extern "C" int ntt_plan_info(const ntt_plan *p, uint64_t info[8])
 extern "C" int ntt_plan_export_table(const ntt_plan *p, int which, void *h_dst, size_t bytes)
 {
   if(!p || !h_dst) return fail(NTT_ERR_ARG, "null argument");
+  if(which == 4 || which == 5) { /* the slot tables: N uint32_t each */
+    const void *tab = which == 4 ? p->d_pos : p->d_ipos;
+    if(!tab) return fail(NTT_ERR_ARG, "the plan has no such table");
+    if(bytes > p->N * sizeof(uint32_t)) return fail(NTT_ERR_ARG, "table is smaller than the request");
+    USE_DEVICE(p->device);
+    HIP_TRY(hipMemcpy(h_dst, tab, bytes, hipMemcpyDeviceToHost));
+    return NTT_OK;
+  }
   const void *src = which == 0 ? p->d_fwd : which == 1 ? p->d_inv : which == 2 ? p->d_fwd8 : which == 3 ? p->d_inv8 : nullptr;
   if(!src) return fail(NTT_ERR_ARG, "the plan has no such table");
   const size_t rec  = p->arith == NTT_ARITH_F64 ? sizeof(TwF64) : sizeof(TwU64);
@@ -594,6 +608,9 @@ extern "C" int ntt_plan_set_option(ntt_plan *p, int option, int64_t value)
       return NTT_OK;
     case NTT_OPT_LIFT_FUSED:
       p->lift_fused = value < 0 ? -1 : (value != 0);
+      return NTT_OK;
+    case NTT_OPT_SLOTS_FUSED:
+      p->slots_fused = value < 0 ? -1 : (value != 0);
       return NTT_OK;
     case NTT_OPT_MAX_BATCH_HINT:
       if(value < 0) return fail(NTT_ERR_ARG, "batch hint must be >= 0");
@@ -694,6 +711,7 @@ extern "C" int ntt_plan_get_option(const ntt_plan *p, int option, int64_t *value
     case NTT_OPT_MODDOWN_ADD_FUSED: *value = p->moddown_add_fused; return NTT_OK;
     case NTT_OPT_BGV_FUSED: *value = p->bgv_fused; return NTT_OK;
     case NTT_OPT_LIFT_FUSED: *value = p->lift_fused; return NTT_OK;
+    case NTT_OPT_SLOTS_FUSED: *value = p->slots_fused; return NTT_OK;
     case NTT_OPT_MAX_BATCH_HINT: *value = (int64_t)p->batch_hint; return NTT_OK;
     case NTT_OPT_CTL_ALLOCATIONS: {
       std::lock_guard<std::mutex> lock(p->team_mu);
