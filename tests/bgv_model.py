@@ -2,37 +2,25 @@
 include/ntt_mi355x.h in its own order -- t_j [T^-1]_{p_j}, + [h]_{p_j}, times [p^_j^-1]_{p_j}, the sum mod q_l, - [h]_{q_l}, times
 [T]_{q_l}, the difference times [P^-1]_{q_l} -- with the modular products through the oracle's pointwise product and the transforms
 through Oracle().ctx (nothing of the kernels' arithmetic, none of their folded constants); a Python-integer form for small sizes; a toy
-BGV (encryption, tensor, hybrid relinearisation with ModUp overshoot and key noise T e, modulus switch, decryption) on top of it; the case
+BGV (encryption, tensor, hybrid relinearisation with ModUp overshoot and key noise T e, modulus switch, decryption) on top of it; the
+same multiplication through the library calls (mul_on_device: tests/test_gpu_bgv.py and tests/test_gpu_plain.py run it); the case
 runners of tests/test_gpu_bgv.py and the model of examples/rns_bgv_mul.c.
 """
-import os
-import sys
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import ct_mul_model as cm  # noqa: E402
-import keyswitch_model as km  # noqa: E402
+import ct_mul_model as cm
+import keyswitch_model as km
+import rns_support as rs
 
 TRANSFORMED, FLOOR, ACCUMULATE = 1, 2, 4
+PT = 65537  # the plaintext modulus of the BGV tests
 prod = km.prod
-
-
-def _u64(a):
-    return np.asarray(a, dtype=np.uint64)
-
-
-def _full(n, v):
-    return np.full(n, v, dtype=np.uint64)
 
 
 def _mul(orc, x, k, q):
     """x * k mod q for an array x of canonical words and an integer k in [0, q)"""
-    x = _u64(x)
-    return orc.pointwise(x, _full(x.size, k), q) if k else np.zeros(x.size, dtype=np.uint64)
+    x = rs.u64(x)
+    return orc.pointwise(x, rs.full(x.size, k), q) if k else np.zeros(x.size, dtype=np.uint64)
 
 
 def subtrahend(orc, pr, t, q, T):
@@ -64,13 +52,13 @@ def mod_down_bgv(orc, primes, roots, np_, limbs, n, T, flags):
     nq = len(primes) - np_
     pr = primes[nq:]
     P = prod(pr)
-    t = [orc.ctx(n, p, w).inv(c) if flags & TRANSFORMED else _u64(c) for p, w, c in zip(pr, roots[nq:], limbs[nq:])]
+    t = [orc.ctx(n, p, w).inv(c) if flags & TRANSFORMED else rs.u64(c) for p, w, c in zip(pr, roots[nq:], limbs[nq:])]
     out = []
     for q, w, c in zip(primes[:nq], roots[:nq], limbs[:nq]):
         u = subtrahend(orc, pr, t, q, T)
         if flags & TRANSFORMED:
             u = orc.ctx(n, q, w).fwd(u)  # (linear: the transform of the difference is the difference of the transforms)
-        d = (_u64(c) + np.uint64(q) - u) % np.uint64(q)
+        d = (rs.u64(c) + np.uint64(q) - u) % np.uint64(q)
         out.append(_mul(orc, d, pow(P % q, -1, q), q))
     return out, t
 
@@ -79,7 +67,7 @@ def mod_down_bgv_add(orc, primes, roots, np_, c, a, n, T, flags):
     """mod_down_bgv of the accumulator a, then c_l = r_l or, with ACCUMULATE, (c_l + r_l) mod q_l"""
     r, t = mod_down_bgv(orc, primes, roots, np_, a, n, T, flags & TRANSFORMED)
     if flags & ACCUMULATE:
-        r = [(_u64(cl) + rl) % np.uint64(q) for cl, rl, q in zip(c, r, primes)]
+        r = [(rs.u64(cl) + rl) % np.uint64(q) for cl, rl, q in zip(c, r, primes)]
     return r, t
 
 
@@ -153,7 +141,7 @@ class Bgv:
         return [(np.uint64(q) - x) % np.uint64(q) for x, q in zip(a, self.primes)]
 
     def uniform(self, limbs):
-        return [_u64([self.rng.randrange(q) for _ in range(self.n)]) for q in self.primes[:limbs]]
+        return [rs.u64([self.rng.randrange(q) for _ in range(self.n)]) for q in self.primes[:limbs]]
 
     def noise(self):
         return [self.rng.choice((-1, 0, 1)) for _ in range(self.n)]
@@ -194,7 +182,7 @@ class Bgv:
         """m1 m2 in Z_T[X] / (X^n + 1): the coefficients stay below n T^2 < q_0, so one limb's transform is exact"""
         q = self.primes[0]
         assert self.n * self.T * self.T < q
-        a, b = (self.ctx[0].fwd(_u64(m)) for m in (m1, m2))
+        a, b = (self.ctx[0].fwd(rs.u64(m)) for m in (m1, m2))
         c = self.ctx[0].inv(self.orc.pointwise(a, b, q))
         return [centred(int(v), q) % self.T for v in c]
 
@@ -246,6 +234,42 @@ def example_model(lib, orc):
     return out
 
 
+# ---------------------------------------------------------------- BGV through the library calls
+
+def _image(polys, n):
+    return np.concatenate([np.concatenate([rs.u64(l) for l in p]) for p in polys])
+
+
+def mul_on_device(lib, bgv, ct1, ct2, keys):
+    """the sequence of examples/rns_bgv_mul.c; returns ((d0, d1) after relinearisation, (d0, d1) after the switch) as per-limb arrays"""
+    n, nq, nl, alpha, pt = bgv.n, bgv.nq, len(bgv.primes), bgv.alpha, bgv.T
+    plans = [lib.Plan(n, q, w) for q, w in zip(bgv.primes, bgv.roots)]
+    cp, ap = nq * n, nl * n
+    din = lib.DeviceBuffer(4 * cp).upload(_image([ct1[0], ct1[1], ct2[0], ct2[1]], n))
+    d, ext, acc = lib.DeviceBuffer(3 * cp), lib.DeviceBuffer(ap).upload(np.zeros(ap, dtype=np.uint64)), lib.DeviceBuffer(2 * ap)
+    kbufs = [lib.DeviceBuffer(2 * ap).upload(_image(key, n)) for key in keys]
+    try:
+        i = [din.ptr + 8 * j * cp for j in range(4)]
+        o = [d.ptr + 8 * j * cp for j in range(3)]
+        lib.rns_tensor(plans[:nq], o[0], o[1], o[2], i[0], i[1], i[2], i[3], 1, 0, layout=(n, cp))
+        lib.rns_inv(plans[:nq], o[2], 1, layout=(n, cp))
+        for k, kb in enumerate(kbufs):
+            lib.copy_probe(ext.ptr + 8 * alpha * k * n, o[2] + 8 * alpha * k * n, alpha * n)
+            lib.rns_mod_up_mul_pair(plans, acc.ptr, acc.ptr + 8 * ap, ext.ptr, alpha * k, alpha, kb.ptr, kb.ptr + 8 * ap, 1,
+                                    lib.MUL_B_BROADCAST | (lib.MUL_ACCUMULATE if k else 0), layout=(n, ap))
+        lib.rns_mod_down_bgv_add(plans, nl - nq, d.ptr, acc.ptr, pt, 2, TRANSFORMED | ACCUMULATE, layout=(n, cp, n, ap))
+        relin = d.download()
+        lib.rns_mod_down_bgv(plans[:nq], 1, d.ptr, pt, 2, TRANSFORMED, layout=(n, cp))
+        switched = d.download()
+    finally:
+        for b in [din, d, ext, acc] + kbufs:
+            b.free()
+        for p in plans:
+            p.destroy()
+    cut = lambda img, limbs: [[img[j * cp + l * n:j * cp + (l + 1) * n] for l in range(limbs)] for j in range(2)]
+    return cut(relin, nq), cut(switched, nq - 1)
+
+
 # ---------------------------------------------------------------- GPU case runners
 
 def _operand(orc, primes, roots, nq, n, batch, flags, seed, edges=False):
@@ -255,7 +279,7 @@ def _operand(orc, primes, roots, nq, n, batch, flags, seed, edges=False):
             plant(coef, primes, nq, n, batch)
         else:
             for l, q in enumerate(primes):
-                coef[l][:4] = [0, q - 1, (q - 1) // 2, (q + 1) // 2]
+                rs.edge_fill(coef[l], q)
     return [orc.ctx(n, q, w).fwd(c) for q, w, c in zip(primes, roots, coef)] if flags & TRANSFORMED else coef
 
 

@@ -7,24 +7,16 @@ Script mode (`python3 tests/ct_mul_model.py`, a fresh process under a kernel tra
 every ksfold_fwd_kernel (N = 2^6..2^14 x ArithF64 classes 0, 1, 18 and ArithF64W), tensor_kernel and ct_fold_kernel (the launch
 proof); `--route`: one fused NTT-domain call at 2^14 over 16 50-bit Q limbs and 2 60-bit P limbs (the route proof).
 """
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import keyswitch_model as km  # noqa: E402
-import rescale_model as rm  # noqa: E402
+import keyswitch_model as km
+import rescale_model as rm
+import rns_support as rs
 
 TRANSFORMED, FLOOR, ACCUMULATE = 1, 2, 4
 LAZY_IN = 1
-
-
-def _u64(a):
-    return np.asarray(a, dtype=np.uint64)
 
 
 def tensor(orc, primes, a0, a1, b0, b1):
@@ -32,7 +24,7 @@ def tensor(orc, primes, a0, a1, b0, b1):
     anywhere below 2^63 (reduced first: the product is a function of the residues)"""
     c0, c1, c2 = [], [], []
     for q, x0, x1, y0, y1 in zip(primes, a0, a1, b0, b1):
-        x0, x1, y0, y1 = (_u64(v) % np.uint64(q) for v in (x0, x1, y0, y1))
+        x0, x1, y0, y1 = (rs.u64(v) % np.uint64(q) for v in (x0, x1, y0, y1))
         c0.append(orc.pointwise(x0, y0, q))
         c1.append((orc.pointwise(x0, y1, q) + orc.pointwise(x1, y0, q)) % np.uint64(q))  # < 2^62: no wrap
         c2.append(orc.pointwise(x1, y1, q))
@@ -44,7 +36,7 @@ def mod_down_add(orc, primes, roots, np_, c, a, n, flags):
     Returns (the ciphertext's limbs after the call, the P limbs' slots of a after the call)"""
     r, t = km.mod_down(orc, primes, roots, np_, a, n, flags & (TRANSFORMED | FLOOR))
     if flags & ACCUMULATE:
-        r = [(_u64(cl) + rl) % np.uint64(q) for cl, rl, q in zip(c, r, primes)]
+        r = [(rs.u64(cl) + rl) % np.uint64(q) for cl, rl, q in zip(c, r, primes)]
     return r, t
 
 
@@ -58,8 +50,8 @@ class _Image:
         if isinstance(layout, tuple):
             self.ls, self.ps, self.words = layout
         else:
-            self.ls, self.ps, self.words = rm.layout_strides(layout, n, self.nl, batch)
-        self.img = rm.place(limbs, n, batch, self.ls, self.ps, self.words)
+            self.ls, self.ps, self.words = rs.layout_strides(layout, n, self.nl, batch)
+        self.img = rs.place(limbs, n, batch, self.ls, self.ps, self.words)
         self.buf = lib.DeviceBuffer(self.words).upload(self.img)
 
     @property
@@ -69,7 +61,7 @@ class _Image:
     def limbs(self):
         """the limbs now on the device; asserts that no word outside the operand changed"""
         got = self.buf.download()
-        out, used = rm.extract(got, self.nl, self.n, self.batch, self.ls, self.ps)
+        out, used = rs.extract(got, self.nl, self.n, self.batch, self.ls, self.ps)
         assert np.array_equal(got[~used], self.img[~used]), "a word outside the operand changed"
         return out
 
@@ -186,11 +178,6 @@ def run_down_add(lib, orc, primes, roots, np_, n, batch, flags, c_layout="limb",
     return got
 
 
-def launch_cases():
-    """(policy, class, logn) of every ksfold_fwd_kernel instance: those of the in-place ModDown kernel"""
-    return km.launch_cases()
-
-
 # ---------------------------------------------------------------- the example
 
 def example_primes(lib, n):
@@ -231,28 +218,26 @@ def route(lib, orc):
     """2^14, 16 Q limbs of 50-bit primes (one run of the FP64 policy) and 2 P limbs of 60-bit primes, NTT domain, accumulating, batch 2,
     the fused route forced"""
     n = 1 << 14
-    primes, roots = rm.chain(lib, n, [50] * 16 + [60, 60])
+    primes, roots = rs.chain(lib, n, [50] * 16 + [60, 60])
     run_down_add(lib, orc, primes, roots, 2, n, 2, TRANSFORMED | ACCUMULATE, fused=1, seed=17, a_untouched=True, cross_check=False)
     print("ksfold route: one call at 2^14 over 16 + 2 limbs")
 
 
 def main():
-    import ontt
-    from oracle_binding import Oracle
-    lib, orc = ontt.load(), Oracle()
+    lib, orc = rs.load()
     if "--route" in sys.argv[1:]:
         route(lib, orc)
         return
-    for pol, k, logn in launch_cases():
+    for pol, k, logn in rs.fused_launch_cases():
         n = 1 << logn
-        b = rm.CLASS_BITS[(pol, k)]
-        primes, roots = rm.chain(lib, n, [b, b, 60, 60])
+        b = rs.CLASS_BITS[(pol, k)]
+        primes, roots = rs.chain(lib, n, [b, b, 60, 60])
         run_down_add(lib, orc, primes, roots, 2, n, 2, TRANSFORMED | (ACCUMULATE if logn % 2 else 0), fused=1, seed=logn, a_untouched=True,
                      cross_check=False)
-    primes, roots = rm.chain(lib, 1 << 10, [50, 50, 50, 60])
+    primes, roots = rs.chain(lib, 1 << 10, [50, 50, 50, 60])
     run_down_add(lib, orc, primes, roots, 1, 1 << 10, 2, ACCUMULATE, cross_check=False)  # coefficients: ct_fold_kernel
     run_tensor(lib, orc, primes, 1 << 10, 2, tensor_inputs(orc, primes, 1 << 10, 2, 3))
-    print("ct_mul launch proof: %d instances driven" % (len(launch_cases()) + 2))
+    print("ct_mul launch proof: %d instances driven" % (len(rs.fused_launch_cases()) + 2))
 
 
 if __name__ == "__main__":

@@ -2,37 +2,23 @@
 tests: the formulas of include/ntt_mi355x.h with the integer sums reduced through the oracle's pointwise product (Python integers in
 the *_int forms) and the floating-point sum s in numpy.float64, in the header's operation order -- fl(z_i) * rho_i added left to
 right, rint to even; the transforms through Oracle().ctx (nothing of the kernels' arithmetic).  A toy BFV (encryption, the four-step
-tensor-and-scale, decryption) on top of the two primitives, and the case runners of tests/test_gpu_exact_bconv.py.
+tensor-and-scale, decryption) on top of the two primitives, the same four steps through the library calls (bfv_on_device:
+tests/test_gpu_exact_bconv.py and tests/test_gpu_plain.py run it), and the case runners of tests/test_gpu_exact_bconv.py.
 """
-import os
-import sys
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import ct_mul_model as cm  # noqa: E402
-import keyswitch_model as km  # noqa: E402
-import rescale_model as rm  # noqa: E402
+import ct_mul_model as cm
+import keyswitch_model as km
+import rns_support as rs
 
 TRANSFORMED, FLOOR, ACCUMULATE = 1, 2, 4
 prod = km.prod
 
 
-def _u64(a):
-    return np.asarray(a, dtype=np.uint64)
-
-
-def _full(n, v):
-    return np.full(n, v, dtype=np.uint64)
-
-
 def digits(orc, basis, words, mult=1):
     """z_i = [x_i * mult * b^_i^-1]_{b_i} per source prime (numpy uint64)"""
     B = prod(basis)
-    return [orc.pointwise(_u64(x), _full(len(x), mult % b * pow(B // b % b, -1, b) % b), b) for b, x in zip(basis, words)]
+    return [orc.pointwise(rs.u64(x), rs.full(len(x), mult % b * pow(B // b % b, -1, b) % b), b) for b, x in zip(basis, words)]
 
 
 def correction(basis, z):
@@ -52,8 +38,8 @@ def exact_bconv(orc, basis, words, q, mult=1):
     v = correction(basis, z)
     acc = np.zeros(len(z[0]), dtype=np.uint64)
     for b, zi in zip(basis, z):
-        acc = (acc + orc.pointwise(zi % np.uint64(q), _full(zi.size, B // b % q), q)) % np.uint64(q)  # < 2^62: no wrap
-    return (acc + orc.pointwise(v, _full(v.size, q - B % q), q)) % np.uint64(q), v
+        acc = (acc + orc.pointwise(zi % np.uint64(q), rs.full(zi.size, B // b % q), q)) % np.uint64(q)  # < 2^62: no wrap
+    return (acc + orc.pointwise(v, rs.full(v.size, q - B % q), q)) % np.uint64(q), v
 
 
 def exact_bconv_int(basis, words, q, mult=1):
@@ -67,11 +53,11 @@ def exact_bconv_int(basis, words, q, mult=1):
 def mod_up_exact(orc, primes, roots, limbs, n, first, count, flags):
     """limbs: the operand's arrays (batch * n words each) in the call's domain.  Returns every limb after the call."""
     basis = primes[first:first + count]
-    coef = [orc.ctx(n, primes[i], roots[i]).inv(limbs[i]) if flags & TRANSFORMED else _u64(limbs[i]) for i in range(first, first + count)]
+    coef = [orc.ctx(n, primes[i], roots[i]).inv(limbs[i]) if flags & TRANSFORMED else rs.u64(limbs[i]) for i in range(first, first + count)]
     out = []
     for l, (q, w) in enumerate(zip(primes, roots)):
         if first <= l < first + count:
-            out.append(_u64(limbs[l]))
+            out.append(rs.u64(limbs[l]))
             continue
         v, _ = exact_bconv(orc, basis, coef, q)
         out.append(orc.ctx(n, q, w).fwd(v) if flags & TRANSFORMED else v)
@@ -84,14 +70,14 @@ def mod_down_exact(orc, primes, roots, np_, limbs, n, mult, flags):
     nq = len(primes) - np_
     pr = primes[nq:]
     P = prod(pr)
-    t = [orc.ctx(n, p, w).inv(c) if flags & TRANSFORMED else _u64(c) for p, w, c in zip(pr, roots[nq:], limbs[nq:])]
+    t = [orc.ctx(n, p, w).inv(c) if flags & TRANSFORMED else rs.u64(c) for p, w, c in zip(pr, roots[nq:], limbs[nq:])]
     out = []
     for q, w, c in zip(primes[:nq], roots[:nq], limbs[:nq]):
         u, _ = exact_bconv(orc, pr, t, q, mult)
-        c = orc.ctx(n, q, w).inv(c) if flags & TRANSFORMED else _u64(c)
+        c = orc.ctx(n, q, w).inv(c) if flags & TRANSFORMED else rs.u64(c)
         pinv = pow(P % q, -1, q)
-        a = orc.pointwise(c, _full(c.size, mult % q * pinv % q), q)
-        b = orc.pointwise(u, _full(u.size, pinv), q)
+        a = orc.pointwise(c, rs.full(c.size, mult % q * pinv % q), q)
+        b = orc.pointwise(u, rs.full(u.size, pinv), q)
         r = (a + np.uint64(q) - b) % np.uint64(q)
         out.append(orc.ctx(n, q, w).fwd(r) if flags & TRANSFORMED else r)
     return out, t
@@ -162,10 +148,38 @@ def bfv_mul(orc, primes, roots, nr, t, a0, a1, b0, b1, n):
 def example_model(lib, orc):
     """{(component, Q limb): checksum} of examples/rns_bfv_mul.c"""
     n, nr, nq, t = 1 << 13, 5, 4, 65537
-    primes, roots = rm.chain(lib, n, [50] * (nr + nq))
+    primes, roots = rs.chain(lib, n, [50] * (nr + nq))
     ct = [[orc.fill_uniform(n, q, 100 + 16 * j + l) for l, q in enumerate(primes) if l >= nr] for j in range(4)]  # a0, a1, b0, b1
     d, _ = bfv_mul(orc, primes, roots, nr, t, *ct, n)
     return {(j, l): orc.checksum(d[j][l]) for j in range(3) for l in range(nq)}
+
+
+# ---------------------------------------------------------------- BFV through the library calls
+
+def bfv_on_device(lib, primes, roots, nr, t, ct_ntt, n):
+    """the example's four calls on [4][nr + nq][n] / [3][nr + nq][n] buffers; returns the three result polynomials' limbs"""
+    nl = len(primes)
+    plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
+    poly = nl * n
+    img = np.zeros(4 * poly, dtype=np.uint64)
+    for j, p in enumerate(ct_ntt):
+        for l, c in enumerate(p):
+            img[j * poly + (nr + l) * n:j * poly + (nr + l + 1) * n] = c
+    din, d = lib.DeviceBuffer(4 * poly).upload(img), lib.DeviceBuffer(3 * poly)
+    try:
+        lay = (n, poly)
+        lib.rns_mod_up_exact(plans, din.ptr, nr, nl - nr, 4, TRANSFORMED, layout=lay)
+        o = [d.ptr + 8 * j * poly for j in range(3)]
+        i = [din.ptr + 8 * j * poly for j in range(4)]
+        lib.rns_tensor(plans, o[0], o[1], o[2], i[0], i[1], i[2], i[3], 1, 0, layout=lay)
+        lib.rns_mod_down_exact(plans, nl - nr, d.ptr, t, 3, TRANSFORMED, layout=lay)
+        lib.rns_mod_up_exact(plans, d.ptr, 0, nr, 3, TRANSFORMED, layout=lay)
+        out = d.download()
+    finally:
+        din.free(), d.free()
+        for p in plans:
+            p.destroy()
+    return [[out[j * poly + l * n:j * poly + (l + 1) * n] for l in range(nl)] for j in range(3)]
 
 
 # ---------------------------------------------------------------- GPU case runners
@@ -183,7 +197,7 @@ def _operand(orc, primes, roots, n, batch, flags, seed, plant=None):
     coef = [orc.fill_uniform(batch * n, q, seed * 1000 + l) for l, q in enumerate(primes)]
     if batch and n >= 8:
         for l, q in enumerate(primes):
-            coef[l][:4] = [0, q - 1, (q - 1) // 2, (q + 1) // 2]
+            rs.edge_fill(coef[l], q)
         if plant:
             words = band_words(primes[plant[0]:plant[0] + plant[1]], 4)
             for i, w in enumerate(words):

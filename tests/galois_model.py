@@ -7,17 +7,11 @@ the inputs and canaries for being untouched.
 Script mode (`python3 tests/galois_model.py --route`, a fresh process under a kernel trace): one NTT-domain automorphism over 17
 limbs, then one rotation key product over 16 limbs, each checked (the route proof).
 """
-import os
 import random
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import rescale_model as rm  # noqa: E402  (chain, layout_strides, place, extract, CANARY, SETUP_KERNELS)
+import rns_support as rs
 
 TRANSFORMED, ACCUMULATE, KEY_BROADCAST = 1, 2, 4
 
@@ -104,15 +98,15 @@ class Placed:
         if bcast:
             self.ls, self.ps, self.words = n, n, self.nl * n
         else:
-            self.ls, self.ps, self.words = rm.layout_strides(layout, n, self.nl, batch)
-        self.img = rm.place(limbs, n, self.batch, self.ls, self.ps, self.words)
+            self.ls, self.ps, self.words = rs.layout_strides(layout, n, self.nl, batch)
+        self.img = rs.place(limbs, n, self.batch, self.ls, self.ps, self.words)
         self.buf = lib.DeviceBuffer(self.words).upload(self.img)
         self.ptr = self.buf.ptr
 
     def download(self):
         """(limbs, whether every word outside the operand still holds what was uploaded)"""
         got = self.buf.download()
-        limbs, used = rm.extract(got, self.nl, self.n, self.batch, self.ls, self.ps)
+        limbs, used = rs.extract(got, self.nl, self.n, self.batch, self.ls, self.ps)
         return limbs, np.array_equal(got[~used], self.img[~used])
 
     def unchanged(self):
@@ -123,7 +117,7 @@ class Placed:
 
 
 def _lay(layout, n, nl, batch):
-    ls, ps, _ = rm.layout_strides(layout, n, nl, batch)
+    ls, ps, _ = rs.layout_strides(layout, n, nl, batch)
     return None if layout == "limb" else (ls, ps)
 
 
@@ -194,7 +188,7 @@ def route(lib, orc):
     """2^12, 4 polynomials: an NTT-domain automorphism over 17 limbs (two launches), then a rotation key product of k = 3 over 16
     limbs (one launch)"""
     n = 1 << 12
-    primes, roots = rm.chain(lib, n, [60] + [50] * 16)
+    primes, roots = rs.chain(lib, n, [60] + [50] * 16)
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     g = rotation(n, 3)
     run_galois(lib, orc, primes, roots, n, 4, g, TRANSFORMED, plans=plans, seed=17)
@@ -205,9 +199,7 @@ def route(lib, orc):
 
 
 def main():
-    import ontt
-    from oracle_binding import Oracle
-    lib, orc = ontt.load(), Oracle()
+    lib, orc = rs.load()
     route(lib, orc)
 
 

@@ -51,10 +51,9 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import kernel_inventory  # noqa: E402
+import rns_support as rs  # noqa: E402
 
 # instances no recipe covers yet, one normalised key per line: fused_kernel and the plain host kernels.  Pinned so that a new instantiation in any family fails
 # tests/test_kernel_inventory.py until a recipe claims it, and so that the list can only shrink as recipes land.
@@ -1096,9 +1095,7 @@ def precedence_probe(lib, oracle, route):
 
 
 def main(argv):
-    import ontt
-    from oracle_binding import Oracle
-    lib, oracle = ontt.load(), Oracle()
+    lib, oracle = rs.load()
     if argv and argv[0] == "--precedence":
         precedence_probe(lib, oracle, argv[1])
         print("precedence probe ok:", argv[1], flush=True)

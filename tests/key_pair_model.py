@@ -8,18 +8,12 @@ Script mode (`python3 tests/key_pair_model.py`, a fresh process under a kernel t
 instance (N = 2^6..2^14 x ArithF64 classes 0, 1, 18 and ArithF64W; <ArithF64,14,1> by the route call alone) and the route call: 2^14,
 16 50-bit limbs and 2 60-bit limbs, digit (0, 2), NTT_OPT_PAIR_FUSED 1.
 """
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import galois_model as gm  # noqa: E402
-import modup_mul_model as mm  # noqa: E402
-import rescale_model as rm  # noqa: E402
+import galois_model as gm
+import modup_mul_model as mm
+import rns_support as rs
 
 LAZY_IN, BROADCAST, ACCUMULATE = mm.LAZY_IN, mm.BROADCAST, mm.ACCUMULATE
 SENTINEL = mm.SENTINEL
@@ -72,7 +66,7 @@ def _options(lib, plans, fused, max_grid):
 def _check_pair(got_c, c_imgs, want, nl, n, batch, ls, ps, what):
     cs = []
     for j in range(2):
-        c, used = rm.extract(got_c[j], nl, n, batch, ls, ps)
+        c, used = rs.extract(got_c[j], nl, n, batch, ls, ps)
         for l in range(nl):
             assert np.array_equal(c[l], want[j][l]), "c%d^ limb %d of %d differs from the model (%s)" % (j, l, nl, what)
         assert np.array_equal(got_c[j][~used], c_imgs[j][~used]), "a word outside c%d^ changed" % j
@@ -90,12 +84,12 @@ def run(lib, orc, primes, roots, first, count, n, batch, flags, layout="limb", f
     if own:
         plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     digit, keys, accs = operands(orc, primes, n, batch, first, count, flags, seed, digit_max)
-    ls, ps, words = rm.layout_strides(layout, n, nl, batch)
+    ls, ps, words = rs.layout_strides(layout, n, nl, batch)
     lay = None if layout == "limb" else (ls, ps)
     ext_limbs = [digit[l - first] if first <= l < first + count else np.full(batch * n, SENTINEL, dtype=np.uint64) for l in range(nl)]
-    ext_img = rm.place(ext_limbs, n, batch, ls, ps, words)
-    c_imgs = [rm.place(accs[j], n, batch, ls, ps, words) for j in range(2)]
-    key_imgs = [np.concatenate(keys[j]) if flags & BROADCAST else rm.place(keys[j], n, batch, ls, ps, words) for j in range(2)]
+    ext_img = rs.place(ext_limbs, n, batch, ls, ps, words)
+    c_imgs = [rs.place(accs[j], n, batch, ls, ps, words) for j in range(2)]
+    key_imgs = [np.concatenate(keys[j]) if flags & BROADCAST else rs.place(keys[j], n, batch, ls, ps, words) for j in range(2)]
     dext = lib.DeviceBuffer(words).upload(ext_img)
     dc = [lib.DeviceBuffer(words).upload(c_imgs[j]) for j in range(2)]
     dk = [lib.DeviceBuffer(key_imgs[j].size).upload(key_imgs[j]) for j in range(2)]
@@ -118,7 +112,7 @@ def run(lib, orc, primes, roots, first, count, n, batch, flags, layout="limb", f
     want, up = model(orc, primes, roots, digit, keys, accs, n, batch, first, count, flags)
     what = "N=%d, batch %d, digit [%d, %d), flags %d, %s" % (n, batch, first, first + count, flags, layout)
     cs = _check_pair(got_c, c_imgs, want, nl, n, batch, ls, ps, what)
-    ext, used = rm.extract(got_ext, nl, n, batch, ls, ps)
+    ext, used = rs.extract(got_ext, nl, n, batch, ls, ps)
     assert np.array_equal(got_ext[~used], ext_img[~used]), "a word outside d_ext changed"
     for j in range(2):
         assert np.array_equal(got_key[j], key_imgs[j]), "key%d changed" % j
@@ -133,11 +127,11 @@ def run_fwd(lib, orc, primes, roots, n, batch, flags, layout="limb", fused=None,
     if own:
         plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     a, keys, accs = operands(orc, primes, n, batch, 0, nl, flags, seed)
-    ls, ps, words = rm.layout_strides(layout, n, nl, batch)
+    ls, ps, words = rs.layout_strides(layout, n, nl, batch)
     lay = None if layout == "limb" else (ls, ps)
-    a_img = rm.place(a, n, batch, ls, ps, words)
-    c_imgs = [rm.place(accs[j], n, batch, ls, ps, words) for j in range(2)]
-    key_imgs = [np.concatenate(keys[j]) if flags & BROADCAST else rm.place(keys[j], n, batch, ls, ps, words) for j in range(2)]
+    a_img = rs.place(a, n, batch, ls, ps, words)
+    c_imgs = [rs.place(accs[j], n, batch, ls, ps, words) for j in range(2)]
+    key_imgs = [np.concatenate(keys[j]) if flags & BROADCAST else rs.place(keys[j], n, batch, ls, ps, words) for j in range(2)]
     da = lib.DeviceBuffer(words).upload(a_img)
     dc = [lib.DeviceBuffer(words).upload(c_imgs[j]) for j in range(2)]
     dk = [lib.DeviceBuffer(key_imgs[j].size).upload(key_imgs[j]) for j in range(2)]
@@ -159,7 +153,7 @@ def run_fwd(lib, orc, primes, roots, n, batch, flags, layout="limb", fused=None,
                 p.destroy()
     want, fa = fwd_model(orc, primes, roots, a, keys, accs, n, batch, flags)
     cs = _check_pair(got_c, c_imgs, want, nl, n, batch, ls, ps, "fwd_mul_pair N=%d, batch %d, flags %d, %s" % (n, batch, flags, layout))
-    after, used = rm.extract(got_a, nl, n, batch, ls, ps)
+    after, used = rs.extract(got_a, nl, n, batch, ls, ps)
     assert np.array_equal(got_a[~used], a_img[~used]), "a word outside d_a changed"
     for j in range(2):
         assert np.array_equal(got_key[j], key_imgs[j]), "key%d changed" % j
@@ -225,32 +219,25 @@ def untouched(ext, first, count):
     return mm.untouched(ext, first, count)
 
 
-def launch_cases():
-    """(policy, class, logn) of every modup_mul2_kernel instance"""
-    return rm.launch_cases()
-
-
 def route(lib, orc):
     """2^14, 16 limbs of 50-bit primes (one run of the FP64 policy) and 2 of 60-bit primes, digit (0, 2), the fused pair kernel asked
     for: the FP64 run's slots of d_ext keep the sentinel"""
     n, first, count = 1 << 14, 0, 2
-    primes, roots = rm.chain(lib, n, [50] * 16 + [60, 60])
+    primes, roots = rs.chain(lib, n, [50] * 16 + [60, 60])
     _, ext, _ = run(lib, orc, primes, roots, first, count, n, 2, BROADCAST | ACCUMULATE, fused=1, seed=17)
     assert untouched(ext, first, count)[:14] == list(range(2, 16)), "the FP64 run's slots of d_ext were written"
     print("key pair route: one call at 2^14 over 16 + 2 limbs")
 
 
 def main():
-    import ontt
-    from oracle_binding import Oracle
-    lib, orc = ontt.load(), Oracle()
+    lib, orc = rs.load()
     driven = 0
-    for pol, k, logn in launch_cases():
+    for pol, k, logn in rs.fused_launch_cases():
         if (pol, k, logn) == ("ArithF64", 1, 14):
             continue  # the route call's instance: launched exactly once in this process
         n = 1 << logn
-        b = rm.CLASS_BITS[(pol, k)]
-        primes, roots = rm.chain(lib, n, [b, b, b])
+        b = rs.CLASS_BITS[(pol, k)]
+        primes, roots = rs.chain(lib, n, [b, b, b])
         run(lib, orc, primes, roots, 1, 2, n, 2, BROADCAST | ACCUMULATE, fused=1, seed=logn)
         driven += 1
     route(lib, orc)

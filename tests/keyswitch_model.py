@@ -7,16 +7,11 @@ Script mode (`python3 tests/keyswitch_model.py`, a fresh process under a kernel 
 every moddown_fwd_kernel (N = 2^6..2^14 x ArithF64 classes 0, 1, 18 and ArithF64W), moddown_coef_kernel and bconv_kernel (the
 launch proof); `--route`: one NTT-domain ModDown at 2^14 over 16 50-bit Q limbs and 2 60-bit P limbs (the route proof).
 """
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import rescale_model as rm  # noqa: E402  (chain, layout_strides, place, extract, CANARY, CLASS_BITS, LOGNS, SETUP_KERNELS)
+import rns_support as rs
 
 TRANSFORMED, FLOOR = 1, 2
 
@@ -28,26 +23,18 @@ def prod(xs):
     return r
 
 
-def _u64(a):
-    return np.asarray(a, dtype=np.uint64)
-
-
-def _full(n, v):
-    return np.full(n, v, dtype=np.uint64)
-
-
 def bconv(orc, basis, digits, q, offsets=None):
     """FastBConv_{B->q}: ( sum_i [ (x_i + o_i) * b^_i^-1 ]_{b_i} * b^_i ) mod q, for digits x_i canonical mod b_i (numpy uint64),
     offsets o_i added mod b_i first (ModDown's [h]_{p_i}).  The products through orc.pointwise."""
     B = prod(basis)
     acc = np.zeros(len(digits[0]), dtype=np.uint64)
     for i, (b, x) in enumerate(zip(basis, digits)):
-        w = _u64(x)
+        w = rs.u64(x)
         if offsets:
             w = (w + np.uint64(offsets[i])) % np.uint64(b)  # < 2^62: no wrap
         hat = B // b
-        z = orc.pointwise(w, _full(w.size, pow(hat % b, -1, b)), b)
-        term = orc.pointwise(z % np.uint64(q), _full(w.size, hat % q), q)
+        z = orc.pointwise(w, rs.full(w.size, pow(hat % b, -1, b)), b)
+        term = orc.pointwise(z % np.uint64(q), rs.full(w.size, hat % q), q)
         acc = (acc + term) % np.uint64(q)  # < 2^62: no wrap
     return acc
 
@@ -56,11 +43,11 @@ def mod_up(orc, primes, roots, limbs, n, first, count, flags):
     """limbs: the operand's arrays (batch * n words each) in the call's domain.  Returns every limb after the call."""
     digit = list(range(first, first + count))
     basis = [primes[i] for i in digit]
-    coef = [orc.ctx(n, primes[i], roots[i]).inv(limbs[i]) if flags & TRANSFORMED else _u64(limbs[i]) for i in digit]
+    coef = [orc.ctx(n, primes[i], roots[i]).inv(limbs[i]) if flags & TRANSFORMED else rs.u64(limbs[i]) for i in digit]
     out = []
     for l, (q, w) in enumerate(zip(primes, roots)):
         if first <= l < first + count:
-            out.append(_u64(limbs[l]))
+            out.append(rs.u64(limbs[l]))
             continue
         v = bconv(orc, basis, coef, q)
         out.append(orc.ctx(n, q, w).fwd(v) if flags & TRANSFORMED else v)
@@ -80,15 +67,15 @@ def mod_down(orc, primes, roots, np_, limbs, n, flags):
     nq = len(primes) - np_
     pr = primes[nq:]
     floor = bool(flags & FLOOR)
-    t = [orc.ctx(n, p, w).inv(c) if flags & TRANSFORMED else _u64(c) for p, w, c in zip(pr, roots[nq:], limbs[nq:])]
+    t = [orc.ctx(n, p, w).inv(c) if flags & TRANSFORMED else rs.u64(c) for p, w, c in zip(pr, roots[nq:], limbs[nq:])]
     P = prod(pr)
     out = []
     for q, w, c in zip(primes[:nq], roots[:nq], limbs[:nq]):
         u = mod_down_digits(orc, pr, t, q, floor)
         if flags & TRANSFORMED:
             u = orc.ctx(n, q, w).fwd(u)
-        d = (_u64(c) + np.uint64(q) - u) % np.uint64(q)
-        out.append(orc.pointwise(d, _full(d.size, pow(P % q, -1, q)), q))
+        d = (rs.u64(c) + np.uint64(q) - u) % np.uint64(q)
+        out.append(orc.pointwise(d, rs.full(d.size, pow(P % q, -1, q)), q))
     return out, t
 
 
@@ -118,27 +105,33 @@ def residues(x, primes):
     return [np.array([v % q for v in x], dtype=np.uint64) for q in primes]
 
 
+# (limb bit sizes, first, count) of the ModUp digits the CPU tests of the key-switch models use: at the start, in the middle, at the
+# end, one limb, sixteen limbs
+UP_CHAINS = [([50, 50, 50, 50, 60, 60], 0, 2), ([60, 50, 50, 50, 50, 60, 60], 1, 3), ([50] * 6 + [60, 60], 6, 2), ([30, 52, 50, 60], 1, 1),
+             ([50] * 18, 1, 16)]
+
+
 # ---------------------------------------------------------------- GPU case runners
 
 def _operand(orc, primes, roots, n, batch, flags, seed):
     coef = [orc.fill_uniform(batch * n, q, seed * 1000 + l) for l, q in enumerate(primes)]
     if batch and n >= 4:  # the extremes of the canonical range
         for l, q in enumerate(primes):
-            coef[l][:4] = [0, q - 1, (q - 1) // 2, (q + 1) // 2]
+            rs.edge_fill(coef[l], q)
     return [orc.ctx(n, q, w).fwd(c) for q, w, c in zip(primes, roots, coef)] if flags & TRANSFORMED else coef
 
 
 def _call(lib, fn, primes, n, batch, limbs, layout):
     nl = len(primes)
-    ls, ps, words = rm.layout_strides(layout, n, nl, batch)
-    img = rm.place(limbs, n, batch, ls, ps, words)
+    ls, ps, words = rs.layout_strides(layout, n, nl, batch)
+    img = rs.place(limbs, n, batch, ls, ps, words)
     buf = lib.DeviceBuffer(words).upload(img)
     try:
         fn(buf.ptr, None if layout == "limb" else (ls, ps))
         got_img = buf.download()
     finally:
         buf.free()
-    got, used = rm.extract(got_img, nl, n, batch, ls, ps)
+    got, used = rs.extract(got_img, nl, n, batch, ls, ps)
     assert np.array_equal(got_img[~used], img[~used]), "a word outside the operand changed"
     return got
 
@@ -188,35 +181,28 @@ def run_up(lib, orc, primes, roots, first, count, n, batch, flags, layout="limb"
     return got
 
 
-def launch_cases():
-    """(policy, class, logn) of every moddown_fwd_kernel instance"""
-    return rm.launch_cases()
-
-
 def route(lib, orc):
     """2^14, 16 Q limbs of 50-bit primes (one run of the FP64 policy) and 2 P limbs of 60-bit primes, NTT domain, 4 polynomials"""
     n = 1 << 14
-    primes, roots = rm.chain(lib, n, [50] * 16 + [60, 60])
+    primes, roots = rs.chain(lib, n, [50] * 16 + [60, 60])
     run_down(lib, orc, primes, roots, 2, n, 4, TRANSFORMED, seed=17)
     print("moddown route: one call at 2^14 over 16 + 2 limbs")
 
 
 def main():
-    import ontt
-    from oracle_binding import Oracle
-    lib, orc = ontt.load(), Oracle()
+    lib, orc = rs.load()
     if "--route" in sys.argv[1:]:
         route(lib, orc)
         return
-    for pol, k, logn in launch_cases():
+    for pol, k, logn in rs.fused_launch_cases():
         n = 1 << logn
-        b = rm.CLASS_BITS[(pol, k)]
-        primes, roots = rm.chain(lib, n, [b, b, 60, 60])
+        b = rs.CLASS_BITS[(pol, k)]
+        primes, roots = rs.chain(lib, n, [b, b, 60, 60])
         run_down(lib, orc, primes, roots, 2, n, 2, TRANSFORMED, seed=logn)
-    primes, roots = rm.chain(lib, 1 << 10, [50, 50, 50, 60])
+    primes, roots = rs.chain(lib, 1 << 10, [50, 50, 50, 60])
     run_down(lib, orc, primes, roots, 1, 1 << 10, 2, 0)
     run_up(lib, orc, primes, roots, 1, 2, 1 << 10, 2, 0)
-    print("keyswitch launch proof: %d instances driven" % (len(launch_cases()) + 2))
+    print("keyswitch launch proof: %d instances driven" % (len(rs.fused_launch_cases()) + 2))
 
 
 if __name__ == "__main__":

@@ -6,17 +6,12 @@ Script mode (`python3 tests/lift_model.py`, a fresh process under a kernel trace
 lift_fwd_kernel (N = 2^6..2^14 x ArithF64 classes 0, 1, 18 and ArithF64W) and lift_coef_kernel -- each checked against the model (the
 launch proof); `--route`: one NTT-domain call at 2^14 over 17 FP64 limbs (the route proof).
 """
-import os
 import sys
 from math import prod
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import rescale_model as rm  # noqa: E402  (chain, layouts, the instance list)
+import rns_support as rs
 
 SCALE, TRANSFORMED, ACCUMULATE = 1, 2, 4
 CENTRED, SCALED, DOUBLE = "centred", "scaled", "double"
@@ -135,7 +130,7 @@ def expected(orc, kind, plain, primes, roots, n, flags, t=0, scale=1.0, acc_in=N
 
 def check_lift(lib, orc, primes, roots, n, batch, kind, flags, t=65537, scale=1.0, plain=None, layout="limb", m_stride=None, fused=None,
                max_grid=None, arith=None, seed=1, plans=None):
-    """one call, checked word for word.  The plaintext ([batch][N] at stride m_stride) and the output (layout: rescale_model's kinds)
+    """one call, checked word for word.  The plaintext ([batch][N] at stride m_stride) and the output (layout: rns_support's kinds)
     sit among canaries (64 words either side and in every gap), which must stay untouched, as the plaintext must.  Without ACCUMULATE
     the output slots start as canaries too: every word must be written.  kind: "plain" or "double".  Returns the output limbs."""
     nl, pad = len(primes), 64
@@ -151,12 +146,12 @@ def check_lift(lib, orc, primes, roots, n, batch, kind, flags, t=65537, scale=1.
         plain = with_corners(kind, batch * n, t, seed, flags, primes)
     plain = np.asarray(plain, dtype=np.uint64)
     ms = m_stride or n
-    ls, ps, words = rm.layout_strides(layout, n, nl, batch)
+    ls, ps, words = rs.layout_strides(layout, n, nl, batch)
     acc_in = [orc.fill_uniform(batch * n, q, seed * 977 + l) for l, q in enumerate(primes)] if flags & ACCUMULATE else None
     if acc_in is not None and batch * n >= 2:
         for a, q in zip(acc_in, primes):
             a[:2] = [q - 1, 0]
-    img_c = rm.place(acc_in, n, batch, ls, ps, words) if acc_in is not None else np.full(words, rm.CANARY, dtype=np.uint64)
+    img_c = rs.place(acc_in, n, batch, ls, ps, words) if acc_in is not None else np.full(words, rs.CANARY, dtype=np.uint64)
     host_c = np.concatenate([np.full(pad, CANARY, dtype=np.uint64), img_c, np.full(pad, CANARY, dtype=np.uint64)])
     host_m = np.full((batch - 1) * ms + n + 2 * pad, CANARY, dtype=np.uint64)
     for p in range(batch):
@@ -179,7 +174,7 @@ def check_lift(lib, orc, primes, roots, n, batch, kind, flags, t=65537, scale=1.
                 p.destroy()
     assert np.array_equal(got_m, host_m), "the plaintext changed"
     assert np.array_equal(got_c[:pad], host_c[:pad]) and np.array_equal(got_c[-pad:], host_c[-pad:]), "a word around the output changed"
-    got, used = rm.extract(got_c[pad:-pad], nl, n, batch, ls, ps)
+    got, used = rs.extract(got_c[pad:-pad], nl, n, batch, ls, ps)
     assert np.array_equal(got_c[pad:-pad][~used], img_c[~used]), "a word in a gap of the output changed"
     want = expected(orc, kind, plain, primes, roots, n, flags, t, scale, acc_in)
     for l in range(nl):
@@ -187,11 +182,6 @@ def check_lift(lib, orc, primes, roots, n, batch, kind, flags, t=65537, scale=1.
         assert bad.size == 0, "limb %d of %d (N=%d, batch %d, %s, flags %d, %s): words %s got %s want %s" % (
             l, nl, n, batch, kind, flags, layout, bad[:6].tolist(), got[l][bad[:6]].tolist(), want[l][bad[:6]].tolist())
     return got
-
-
-def launch_cases():
-    """(policy, class, logn) of every lift_fwd_kernel instance: rescale_fwd_kernel's list"""
-    return rm.launch_cases()
 
 
 def instance_case(logn):
@@ -202,7 +192,7 @@ def instance_case(logn):
 
 def run_instance(lib, orc, pol, k, logn, **kw):
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [rm.CLASS_BITS[(pol, k)]] * 3)
+    primes, roots = rs.chain(lib, n, [rs.CLASS_BITS[(pol, k)]] * 3)
     kind, flags, par = instance_case(logn)
     arg = {"scale": par} if kind == DOUBLE else {"t": par}
     return check_lift(lib, orc, primes, roots, n, 3 if logn < 9 else 2, kind, flags, seed=logn, fused=1, **arg, **kw)
@@ -212,7 +202,7 @@ def route(lib, orc):
     """2^14, 17 limbs of 50-bit primes (two runs of the FP64 policy: 16 + 1), NTT domain, 2 polynomials, the fused kernel selected
     (NTT_OPT_LIFT_FUSED 1: the measured default stores a centred lift at 2^14 through the composition): the route proof's call"""
     n = 1 << 14
-    primes, roots = rm.chain(lib, n, [50] * 17)
+    primes, roots = rs.chain(lib, n, [50] * 17)
     check_lift(lib, orc, primes, roots, n, 2, "plain", TRANSFORMED, fused=1, seed=17)
     print("lift route: one call at 2^14 over 17 limbs")
 
@@ -220,7 +210,7 @@ def route(lib, orc):
 def example_model(lib, orc):
     """the lines examples/rns_encrypt.c prints: c0^ = pk0^ (.) u^ + e^ + fwd(the lift) per limb, pk0^ = -(a^ (.) s^)"""
     n, t, L, delta = 1 << 13, 65537, 3, 2.0 ** 30
-    primes, roots = rm.chain(lib, n, [50] * L)
+    primes, roots = rs.chain(lib, n, [50] * L)
     m = orc.fill_uniform(n, t, 1)
     u, e, s = orc.fill_uniform(n, 2, 2), orc.fill_uniform(n, 2, 3), orc.fill_uniform(n, 2, 4)
     y = (orc.fill_uniform(n, 1 << 20, 5).astype(np.float64) - 524288.0) / 1024.0
@@ -238,17 +228,15 @@ def example_model(lib, orc):
 
 
 def main():
-    import ontt
-    from oracle_binding import Oracle
-    lib, orc = ontt.load(), Oracle()
+    lib, orc = rs.load()
     if "--route" in sys.argv[1:]:
         route(lib, orc)
         return
-    for pol, k, logn in launch_cases():
+    for pol, k, logn in rs.fused_launch_cases():
         run_instance(lib, orc, pol, k, logn)
-    primes, roots = rm.chain(lib, 1 << 10, [50, 50, 50])
+    primes, roots = rs.chain(lib, 1 << 10, [50, 50, 50])
     check_lift(lib, orc, primes, roots, 1 << 10, 2, "plain", 0)
-    print("lift launch proof: %d instances driven" % (len(launch_cases()) + 1))
+    print("lift launch proof: %d instances driven" % (len(rs.fused_launch_cases()) + 1))
 
 
 if __name__ == "__main__":

@@ -7,18 +7,12 @@ inputs and canaries for being untouched.
 Script mode (`python3 tests/lincomb_model.py --route`, a fresh process under a kernel trace): one call over 16 limbs, then one over 17,
 each behind the creation of its own plans (whose table kernels separate the two calls in the trace).
 """
-import os
 import random
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import galois_model as gm  # noqa: E402
-import rescale_model as rm  # noqa: E402
+import galois_model as gm
+import rns_support as rs
 
 ACCUMULATE, M_BROADCAST, LAZY_IN = 1, 2, 4
 
@@ -93,7 +87,7 @@ class Placed(gm.Placed):
             return
         self.nl, self.n, self.batch = len(limbs), n, batch
         self.ls, self.ps, self.words = layout
-        self.img = rm.place(limbs, n, batch, self.ls, self.ps, self.words)
+        self.img = rs.place(limbs, n, batch, self.ls, self.ps, self.words)
         self.buf = lib.DeviceBuffer(self.words).upload(self.img)
         self.ptr = self.buf.ptr
 
@@ -167,15 +161,13 @@ def route(lib, orc):
     with plans of its own"""
     n = 1 << 10
     for nlimbs in (16, 17):
-        primes, roots = rm.chain(lib, n, [60] + [50] * (nlimbs - 1))
+        primes, roots = rs.chain(lib, n, [60] + [50] * (nlimbs - 1))
         run_case(lib, orc, primes, roots, n, 3, [1, 5, 2 * n - 1], poly=(1,), seed=17)
     print("lincomb route: one call over 16 limbs, one over 17")
 
 
 def main():
-    import ontt
-    from oracle_binding import Oracle
-    lib, orc = ontt.load(), Oracle()
+    lib, orc = rs.load()
     route(lib, orc)
 
 

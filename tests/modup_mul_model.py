@@ -6,17 +6,11 @@ Script mode (`python3 tests/modup_mul_model.py`, a fresh process under a kernel 
 instance (N = 2^6..2^14 x ArithF64 classes 0, 1, 18 and ArithF64W; <ArithF64,14,1> by the route call alone) and the route call: 2^14,
 16 50-bit limbs and 2 60-bit limbs, digit (0, 2), NTT_OPT_MODUP_FUSED 1.
 """
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import keyswitch_model as km  # noqa: E402
-import rescale_model as rm  # noqa: E402
+import keyswitch_model as km
+import rns_support as rs
 
 LAZY_IN, BROADCAST, ACCUMULATE = 1, 2, 4
 SENTINEL = 0x5E47195E47195E47  # what d_ext's non-digit slots hold before the call
@@ -67,11 +61,11 @@ def run(lib, orc, primes, roots, first, count, n, batch, flags, layout="limb", f
     if own:
         plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     digit, key, acc = operands(orc, primes, n, batch, first, count, flags, seed, digit_max)
-    ls, ps, words = rm.layout_strides(layout, n, nl, batch)
+    ls, ps, words = rs.layout_strides(layout, n, nl, batch)
     ext_limbs = [digit[l - first] if first <= l < first + count else np.full(batch * n, SENTINEL, dtype=np.uint64) for l in range(nl)]
-    ext_img = rm.place(ext_limbs, n, batch, ls, ps, words)
-    c_img = rm.place(acc, n, batch, ls, ps, words)
-    key_img = np.concatenate(key) if flags & BROADCAST else rm.place(key, n, batch, ls, ps, words)
+    ext_img = rs.place(ext_limbs, n, batch, ls, ps, words)
+    c_img = rs.place(acc, n, batch, ls, ps, words)
+    key_img = np.concatenate(key) if flags & BROADCAST else rs.place(key, n, batch, ls, ps, words)
     dext, dc, dk = lib.DeviceBuffer(words).upload(ext_img), lib.DeviceBuffer(words).upload(c_img), lib.DeviceBuffer(key_img.size).upload(key_img)
     try:
         if fused is not None:
@@ -87,8 +81,8 @@ def run(lib, orc, primes, roots, first, count, n, batch, flags, layout="limb", f
             for p in plans:
                 p.destroy()
     want, up = model(orc, primes, roots, digit, key, acc, n, batch, first, count, flags)
-    c, used = rm.extract(got_c, nl, n, batch, ls, ps)
-    ext, _ = rm.extract(got_ext, nl, n, batch, ls, ps)
+    c, used = rs.extract(got_c, nl, n, batch, ls, ps)
+    ext, _ = rs.extract(got_ext, nl, n, batch, ls, ps)
     for l in range(nl):
         assert np.array_equal(c[l], want[l]), "c^ limb %d of %d differs from the model (N=%d, batch %d, digit [%d, %d), flags %d, %s)" % (
             l, nl, n, batch, first, first + count, flags, layout)
@@ -103,32 +97,25 @@ def untouched(ext, first, count):
     return [l for l, e in enumerate(ext) if not first <= l < first + count and bool(np.all(e == np.uint64(SENTINEL)))]
 
 
-def launch_cases():
-    """(policy, class, logn) of every modup_mul_kernel instance"""
-    return rm.launch_cases()
-
-
 def route(lib, orc):
     """2^14, 16 limbs of 50-bit primes (one run of the FP64 policy) and 2 of 60-bit primes, digit (0, 2), the fused kernel asked for:
     the FP64 run's slots of d_ext keep the sentinel"""
     n, first, count = 1 << 14, 0, 2
-    primes, roots = rm.chain(lib, n, [50] * 16 + [60, 60])
+    primes, roots = rs.chain(lib, n, [50] * 16 + [60, 60])
     _, ext, _ = run(lib, orc, primes, roots, first, count, n, 2, BROADCAST | ACCUMULATE, fused=1, seed=17)
     assert untouched(ext, first, count)[:14] == list(range(2, 16)), "the FP64 run's slots of d_ext were written"
     print("modup_mul route: one call at 2^14 over 16 + 2 limbs")
 
 
 def main():
-    import ontt
-    from oracle_binding import Oracle
-    lib, orc = ontt.load(), Oracle()
+    lib, orc = rs.load()
     driven = 0
-    for pol, k, logn in launch_cases():
+    for pol, k, logn in rs.fused_launch_cases():
         if (pol, k, logn) == ("ArithF64", 1, 14):
             continue  # the route call's instance: launched exactly once in this process
         n = 1 << logn
-        b = rm.CLASS_BITS[(pol, k)]
-        primes, roots = rm.chain(lib, n, [b, b, b])
+        b = rs.CLASS_BITS[(pol, k)]
+        primes, roots = rs.chain(lib, n, [b, b, b])
         run(lib, orc, primes, roots, 1, 2, n, 2, BROADCAST | ACCUMULATE, fused=1, seed=logn)
         driven += 1
     route(lib, orc)

@@ -185,9 +185,9 @@ def random_limbs(primes, count, seed):
 
 def example_model(lib, orc):
     """the lines examples/rns_decrypt.c prints: the phase is Delta m + e exactly, the plaintext the message"""
-    import rescale_model as rm
+    import rns_support as rs
     n, t = 1 << 13, 65537
-    primes, _ = rm.chain(lib, n, [50] * 4)
+    primes, _ = rs.chain(lib, n, [50] * 4)
     delta = prod(primes) // t
     m, e = orc.fill_uniform(n, t, 1), orc.fill_uniform(n, 2, 2)
     lines = []

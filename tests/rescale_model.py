@@ -1,25 +1,18 @@
 """Model of the RNS rescale (ntt_rns_rescale_batch) for the tests: the formula of include/ntt_mi355x.h in numpy, its products through
 the oracle's pointwise product and its transforms through Oracle().ctx; a Python-integer CRT reference for small sizes; the case
-generator of tests/test_gpu_rescale.py.
+runner of tests/test_gpu_rescale.py.  Prime chains, layouts and the instance list are in tests/rns_support.py.
 
 Script mode (`python3 tests/rescale_model.py`, a fresh process under a kernel trace): one call per rescale kernel instance -- every
 rescale_fwd_kernel (N = 2^6..2^14 x ArithF64 classes 0, 1, 18 and ArithF64W) and rescale_coef_kernel -- each checked against the
 model (the launch proof); `--route`: one NTT-domain call at 2^14 over 17 FP64 limbs (the route proof).
 """
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import rns_support as rs
 
 TRANSFORMED, FLOOR = 1, 2
-
-# the bit sizes that land a 2^6..2^14 plan in each FP64 policy / headroom class (ntt_tables.h h_f64_ksh, host_plan.inc kcls)
-CLASS_BITS = {("ArithF64", 0): 51, ("ArithF64", 1): 50, ("ArithF64", 18): 30, ("ArithF64W", 0): 52}
-LOGNS = range(6, 15)
 
 
 def digits(t, qL, q, floor):
@@ -77,58 +70,6 @@ def residues(x, primes):
     return [np.array([v % q for v in x], dtype=np.uint64) for q in primes]
 
 
-def chain(lib, n, bits_list):
-    """distinct primes = 1 mod 2n of the given bit sizes (in order) and their minimal roots"""
-    seen, primes = {}, []
-    for b in bits_list:
-        k = seen.get(b, 0)
-        q = lib.find_prime(b, n, k)
-        seen[b] = k + 1
-        primes.append(q)
-    return primes, [lib.min_root(q, n) for q in primes]
-
-
-def layout_strides(kind, n, nlimbs, batch):
-    """(limb_stride, poly_stride, words) of a layout: [limb][batch][N], [batch][limb][N] or padded forms of either"""
-    if kind == "limb":
-        return batch * n, n, nlimbs * batch * n
-    if kind == "batch":
-        return n, nlimbs * n, nlimbs * batch * n
-    if kind == "batch_padded":
-        ls, ps = n + 64, nlimbs * (n + 64) + 128
-        return ls, ps, (batch - 1) * ps + (nlimbs - 1) * ls + n + 96
-    if kind == "limb_padded":
-        ls, ps = batch * (n + 32) + 256, n + 32
-        return ls, ps, (nlimbs - 1) * ls + (batch - 1) * ps + n + 96
-    raise ValueError(kind)
-
-
-CANARY = 0xC0FFEE5EEDC0FFEE
-
-
-def place(limbs, n, batch, ls, ps, words):
-    """host image of an operand: limb l, polynomial p at l * ls + p * ps; every other word a canary"""
-    img = np.full(words, CANARY, dtype=np.uint64)
-    for l, c in enumerate(limbs):
-        for p in range(batch):
-            img[l * ls + p * ps:l * ls + p * ps + n] = c[p * n:(p + 1) * n]
-    return img
-
-
-def extract(img, nlimbs, n, batch, ls, ps):
-    """(limbs, mask of the words the operand occupies)"""
-    used = np.zeros(img.size, dtype=bool)
-    out = []
-    for l in range(nlimbs):
-        parts = []
-        for p in range(batch):
-            o = l * ls + p * ps
-            parts.append(img[o:o + n])
-            used[o:o + n] = True
-        out.append(np.concatenate(parts))
-    return out, used
-
-
 def run_case(lib, orc, primes, roots, n, batch, flags, layout="limb", fused=None, seed=1, plans=None, crt=False):
     """one call on random canonical operands, checked word for word against the model (crt: also against the CRT definition),
     canaries and the dropped-limb contract included.  Returns the kept limbs after the call."""
@@ -141,15 +82,15 @@ def run_case(lib, orc, primes, roots, n, batch, flags, layout="limb", fused=None
     coef = [orc.fill_uniform(batch * n, q, seed * 1000 + l) for l, q in enumerate(primes)]
     if batch and n >= 4:  # the extremes of the canonical range
         for l, q in enumerate(primes):
-            coef[l][:4] = [0, q - 1, (q - 1) // 2, (q + 1) // 2]
+            rs.edge_fill(coef[l], q)
     limbs = [orc.ctx(n, q, w).fwd(c) for q, w, c in zip(primes, roots, coef)] if flags & TRANSFORMED else coef
-    ls, ps, words = layout_strides(layout, n, nl, batch)
-    img = place(limbs, n, batch, ls, ps, words)
+    ls, ps, words = rs.layout_strides(layout, n, nl, batch)
+    img = rs.place(limbs, n, batch, ls, ps, words)
     buf = lib.DeviceBuffer(words).upload(img)
     lib.rns_rescale(plans, buf.ptr, batch, flags, layout=None if layout == "limb" else (ls, ps))
     got_img = buf.download()
     buf.free()
-    got, used = extract(got_img, nl, n, batch, ls, ps)
+    got, used = rs.extract(got_img, nl, n, batch, ls, ps)
     assert np.array_equal(got_img[~used], img[~used]), "a word outside the operand changed"
     want, t = model(orc, primes, roots, limbs, n, flags)
     for l in range(nl - 1):
@@ -167,37 +108,26 @@ def run_case(lib, orc, primes, roots, n, batch, flags, layout="limb", fused=None
     return got
 
 
-def launch_cases():
-    """(policy, class, logn) of every rescale_fwd_kernel instance"""
-    return [(pol, k, logn) for (pol, k) in CLASS_BITS for logn in LOGNS]
-
-
-# kernels a plan's creation launches (table builds): not part of a call
-SETUP_KERNELS = ("power_table_kernel", "records_u64_kernel", "records_f64_kernel", "records_r4_kernel")
-
-
 def route(lib, orc):
     """2^14, 17 limbs of 50-bit primes (16 kept: one run of the FP64 policy), NTT domain, 8 polynomials: the route proof's call"""
     n = 1 << 14
-    primes, roots = chain(lib, n, [50] * 17)
+    primes, roots = rs.chain(lib, n, [50] * 17)
     run_case(lib, orc, primes, roots, n, 8, TRANSFORMED, seed=17)
     print("rescale route: one call at 2^14 over 17 limbs")
 
 
 def main():
-    import ontt
-    from oracle_binding import Oracle
-    lib, orc = ontt.load(), Oracle()
+    lib, orc = rs.load()
     if "--route" in sys.argv[1:]:
         route(lib, orc)
         return
-    for pol, k, logn in launch_cases():
+    for pol, k, logn in rs.fused_launch_cases():
         n = 1 << logn
-        primes, roots = chain(lib, n, [CLASS_BITS[(pol, k)]] * 3)
+        primes, roots = rs.chain(lib, n, [rs.CLASS_BITS[(pol, k)]] * 3)
         run_case(lib, orc, primes, roots, n, 2, TRANSFORMED, seed=logn)
-    primes, roots = chain(lib, 1 << 10, [50, 50, 50])
+    primes, roots = rs.chain(lib, 1 << 10, [50, 50, 50])
     run_case(lib, orc, primes, roots, 1 << 10, 2, 0)
-    print("rescale launch proof: %d instances driven" % (len(launch_cases()) + 1))
+    print("rescale launch proof: %d instances driven" % (len(rs.fused_launch_cases()) + 1))
 
 
 if __name__ == "__main__":

@@ -11,20 +11,15 @@ the canaries and, for encode, the input for being untouched.
 Script mode (a fresh process under a kernel trace): `python3 tests/slots_model.py --route` runs one fused encode and one fused decode at
 2^14 x 4; without arguments every new kernel instance is launched once, each checked.
 """
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import galois_model as gm  # noqa: E402  (Placed, rotation)
-import rescale_model as rm  # noqa: E402  (CLASS_BITS, LOGNS, SETUP_KERNELS)
+import galois_model as gm
+import rns_support as rs
 
 OPT_MAX_GRID, OPT_F64_CLASS, OPT_SLOTS_FUSED = 1, 3, 23
-SETUP_KERNELS = rm.SETUP_KERNELS + ("slots_table_kernel",)
+SETUP_KERNELS = rs.SETUP_KERNELS + ("slots_table_kernel",)
 
 
 def bitrev_int(x, m):
@@ -120,13 +115,13 @@ class Side:
     def __init__(self, lib, data, n, batch, pad):
         self.n, self.batch = n, batch
         self.ps, self.words = _strides(n, batch, pad)
-        self.img = rm.place([np.asarray(data, dtype=np.uint64)], n, batch, 0, self.ps, self.words)
+        self.img = rs.place([np.asarray(data, dtype=np.uint64)], n, batch, 0, self.ps, self.words)
         self.buf = lib.DeviceBuffer(self.words).upload(self.img)
         self.ptr = self.buf.ptr
 
     def download(self):
         got = self.buf.download()
-        limbs, used = rm.extract(got, 1, self.n, self.batch, 0, self.ps)
+        limbs, used = rs.extract(got, 1, self.n, self.batch, 0, self.ps)
         return limbs[0], np.array_equal(got[~used], self.img[~used])
 
     def unchanged(self):
@@ -173,14 +168,9 @@ def run_case(lib, orc, n, t, batch, direction, fused=None, v_pad=0, a_pad=0, max
 
 # ---------------------------------------------------------------- kernel instances
 
-def launch_cases():
-    """(policy, class, logn) of every fused instance; each has a slots_inv_kernel and a slots_fwd_kernel"""
-    return [(pol, k, logn) for (pol, k) in rm.CLASS_BITS for logn in rm.LOGNS]
-
-
 def class_modulus(lib, pol, k, n):
-    """a prime t = 1 mod 2n whose plan lands in the class: 30, 50, 51 and 52 bits (rescale_model.CLASS_BITS)"""
-    return lib.find_prime(rm.CLASS_BITS[(pol, k)], n)
+    """a prime t = 1 mod 2n whose plan lands in the class: 30, 50, 51 and 52 bits (rns_support.CLASS_BITS)"""
+    return lib.find_prime(rs.CLASS_BITS[(pol, k)], n)
 
 
 def run_instance(lib, orc, pol, k, logn):
@@ -199,7 +189,7 @@ def run_instance(lib, orc, pol, k, logn):
 
 def kernel_names():
     out = {"slots_perm_kernel", "slots_table_kernel"}
-    for pol, k, logn in launch_cases():
+    for pol, k, logn in rs.fused_launch_cases():
         out |= {"slots_inv_kernel<%s,%d,%d>" % (pol, logn, k), "slots_fwd_kernel<%s,%d,%d>" % (pol, logn, k)}
     return out
 
@@ -226,16 +216,14 @@ def example_model(lib, orc):
 
 
 def main():
-    import ontt
-    from oracle_binding import Oracle
-    lib, orc = ontt.load(), Oracle()
+    lib, orc = rs.load()
     if "--route" in sys.argv[1:]:
         route(lib, orc)
         return
-    for pol, k, logn in launch_cases():
+    for pol, k, logn in rs.fused_launch_cases():
         run_instance(lib, orc, pol, k, logn)
     run_case(lib, orc, 1 << 5, 65537, 2, "encode", seed=5)
-    print("slots launch proof: %d instances driven" % (2 * len(launch_cases()) + 2))
+    print("slots launch proof: %d instances driven" % (2 * len(rs.fused_launch_cases()) + 2))
 
 
 if __name__ == "__main__":

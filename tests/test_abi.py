@@ -6,6 +6,8 @@ import subprocess
 
 import pytest
 
+import children
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -48,8 +50,7 @@ def test_mul_op_by_value_through_ctypes(lib, tmp_path):
                    "{(void)a;(void)b;(void)c;(void)d;(void)e;(void)f;"
                    " return (uint64_t)m.op + 3*(uint64_t)(m.op>>64) + 5*(uint64_t)m.con + 7*(uint64_t)(m.con>>64) + (uint64_t)g;}\n")
     so = tmp_path / "probe.so"
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-shared", "-fPIC", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "include", "internal"), "-o", str(so), str(src)])
+    children.gcc("-shared", "-fPIC", "-I" + os.path.join(ROOT, "include", "internal"), "-o", so, src)
     probe = C.CDLL(str(so)).probe
     probe.restype = C.c_uint64
     probe.argtypes = [C.c_long] * 7 + [lib.MulOp]
@@ -129,8 +130,7 @@ int main(int argc,char**argv){uint64_t m=strtoull(argv[1],0,0),q=strtoull(argv[2
  printf("%016llx %016llx %016llx %016llx\n",fnv(t,n),fnv(c,n),fnv(e,2*n),fnv(ec,2*n));return 0;}
 ''')
     exe = tmp_path / "t"
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "include", "internal"), "-o", str(exe), str(prog)])
+    children.gcc("-I" + os.path.join(ROOT, "include", "internal"), "-o", exe, prog)
     for i in (0, 4, 12, 13, 18):
         c = kat["cases"][i]
         out = subprocess.check_output([str(exe), str(c["m"]), str(c["q"]), str(c["w"])], text=True).split()
@@ -181,12 +181,7 @@ def test_reference_drivers_compile_unchanged_against_our_headers(lib):
 def test_c_example_builds_against_the_public_header(lib, example):
     """examples/*.c that need nothing but the public header: plain-C callers (gcc, no HIP headers) compile and link against
     include/ntt_mi355x.h + libntt_mi355x.so; the GPU suite runs them (test_c_example_*_runs)"""
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", example + ".c"), "-L" + os.path.dirname(lib.LIB_PATH),
-                           "-lntt_mi355x", "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH),
-                           "-o", os.path.join(ROOT, "build", example)])
-    assert os.path.exists(os.path.join(ROOT, "build", example))
+    assert os.path.exists(children.build_example(lib, example, *children.STRICT))
 
 
 def _last_template_bool_is_multi(name):

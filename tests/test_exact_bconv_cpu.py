@@ -11,8 +11,10 @@ import sys
 import numpy as np
 import pytest
 
+import children
 import exact_bconv_model as xm
 import keyswitch_model as km
+import rns_support as rs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_amd", "csrc")
@@ -23,15 +25,6 @@ N = 64
 MULTS = [1, 65537, (1 << 59) + 12345]
 
 
-def _chain(orc, n, bits_list):
-    seen, primes = {}, []
-    for b in bits_list:
-        k = seen.get(b, 0)
-        primes.append(orc.find_prime(b, n, k))
-        seen[b] = k + 1
-    return primes, [orc.min_root(q, n) for q in primes]
-
-
 # (source bits, destination bits) and the reverse directions
 _FWD = [([30], [30, 30]), ([50] * 2, [60] * 3), ([50] * 4, [50] * 5), ([60] * 8, [60] * 9), ([60] * 16, [52] * 16)]
 CHAINS = _FWD + [(d, s) for s, d in _FWD]
@@ -40,7 +33,7 @@ CHAIN_IDS = ["%dx%d-%dx%d" % (len(s), s[0], len(d), d[0]) for s, d in CHAINS]
 
 def _split(orc, src_bits, dst_bits):
     """(source primes, roots), (destination primes, roots): distinct primes even where the bit sizes coincide"""
-    primes, roots = _chain(orc, N, src_bits + dst_bits)
+    primes, roots = rs.chain(orc, N, src_bits + dst_bits)
     ns = len(src_bits)
     return (primes[:ns], roots[:ns]), (primes[ns:], roots[ns:])
 
@@ -129,7 +122,7 @@ def test_band_values_take_one_choice_in_every_limb(oracle, nb, bits):
 def test_exact_mod_down_is_the_approximate_one_plus_its_error(oracle, qbits, pbits):
     """mult = 1: exact = round(x / P), the existing call's round(x / P) - v with 0 <= v < np: the difference is that v in every limb,
     and the words are equal where v = 0"""
-    primes, roots = _chain(oracle, N, qbits + pbits)
+    primes, roots = rs.chain(oracle, N, qbits + pbits)
     nq, np_ = len(qbits), len(pbits)
     P = km.prod(primes[nq:])
     coef = [oracle.fill_uniform(N, q, 70 + l) for l, q in enumerate(primes)]
@@ -152,7 +145,7 @@ def test_toy_bfv_multiplication_decrypts(oracle):
     """N = 64, Q = 2 x 50 bits, R = 3 x 50 bits, t = 65537, real encryptions under a ternary key: the five-call sequence on the model
     decrypts to m1 m2 mod t"""
     nr, nq, t = 3, 2, 65537
-    primes, roots = _chain(oracle, N, [50] * (nr + nq))
+    primes, roots = rs.chain(oracle, N, [50] * (nr + nq))
     qp, qr = primes[nr:], roots[nr:]
     Q = km.prod(qp)
     rng = random.Random(2024)
@@ -170,12 +163,7 @@ def test_toy_bfv_multiplication_decrypts(oracle):
 
 @pytest.fixture(scope="module")
 def host_check():
-    exe = os.path.join(ROOT, "build", "exact_host_check")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.check_call([hipcc, "--cuda-host-only", "-O2", "-std=c++17", "-ffp-contract=off", "-I" + CSRC,
-                           os.path.join(ROOT, "tests", "exact_host_check.cpp"), "-o", exe])
-    return exe
+    return children.build_host_check("exact_host_check", "-O2 -std=c++17 -ffp-contract=off")
 
 
 def _host(exe, tmp_path, mode, basis, dest, mult, rows):
@@ -225,12 +213,7 @@ def test_exports_the_four_symbols_and_binds_them(lib):
 
 
 def test_bfv_example_builds_against_the_public_header(lib):
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    exe = os.path.join(ROOT, "build", "rns_bfv_mul")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "rns_bfv_mul.c"), "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x",
-                           "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-    assert os.path.exists(exe)
+    assert os.path.exists(children.build_example(lib, "rns_bfv_mul", *children.STRICT))
 
 
 def test_exact_objects_hold_exactly_the_expected_instances_without_spills():
@@ -245,7 +228,7 @@ def test_exact_objects_hold_exactly_the_expected_instances_without_spills():
         [k for k in check_spills.kernels_of(LIB) if "exact_" in k["name"]]
     names = [k["name"] for k in ks]
     by = {kernel_inventory.normalise(d): k for d, k in zip(kernel_inventory.demangle(names), ks)}
-    want = {"moddown_exact_fwd_kernel<%s,%d,%d>" % (pol, logn, k) for pol, k, logn in km.launch_cases()}
+    want = rs.kernel_names("moddown_exact_fwd_kernel", rs.fused_launch_cases())
     want |= {"exact_up_coef_kernel", "exact_down_coef_kernel"}
     assert len(want) == 38
     assert set(by) == want, ("missing %s, unexpected %s" % (sorted(want - set(by))[:8], sorted(set(by) - want)[:8]))

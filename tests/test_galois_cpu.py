@@ -13,7 +13,9 @@ import sys
 import numpy as np
 import pytest
 
+import children
 import galois_model as gm
+import rns_support as rs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_amd", "csrc")
@@ -22,25 +24,16 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 BITS = [30, 50, 52, 60]
 
 
-def _chain(orc, n, bits_list):
-    seen, primes = {}, []
-    for b in bits_list:
-        k = seen.get(b, 0)
-        primes.append(orc.find_prime(b, n, k))
-        seen[b] = k + 1
-    return primes, [orc.min_root(q, n) for q in primes]
-
-
 def _edges(orc, n, q, seed, batch=1):
     a = orc.fill_uniform(batch * n, q, seed)
-    a[:4] = [0, q - 1, (q - 1) // 2, (q + 1) // 2]
+    rs.edge_fill(a, q)
     return a
 
 
 @pytest.mark.parametrize("n", [64, 256])
 def test_both_domains_agree_through_the_oracle(oracle, n):
     """fwd(coef_model(a, g)) == ntt_model(fwd(a), g)"""
-    primes, roots = _chain(oracle, n, BITS)
+    primes, roots = rs.chain(oracle, n, BITS)
     for q, w in zip(primes, roots):
         cx = oracle.ctx(n, q, w)
         a = _edges(oracle, n, q, 3, batch=2)
@@ -64,7 +57,7 @@ def test_composition(oracle, n):
 def test_multiplicative_against_the_schoolbook_product(oracle):
     """sigma_g(a) sigma_g(b) = sigma_g(a b) at N = 64"""
     n = 64
-    primes, _ = _chain(oracle, n, BITS)
+    primes, _ = rs.chain(oracle, n, BITS)
     for q in primes:
         a, b = _edges(oracle, n, q, 7), _edges(oracle, n, q, 8)
         ab = oracle.schoolbook(a, b, n, q)
@@ -76,7 +69,7 @@ def test_multiplicative_against_the_schoolbook_product(oracle):
 def test_dot_model_is_the_sum_of_schoolbook_products(oracle, flags):
     """inv(dot_model) = (c +) sum_i sigma_g(a_i) key_i at N = 64, k = 3, two polynomials"""
     n, k, batch = 64, 3, 2
-    primes, roots = _chain(oracle, n, BITS)
+    primes, roots = rs.chain(oracle, n, BITS)
     for q, w in zip(primes, roots):
         cx = oracle.ctx(n, q, w)
         a = [_edges(oracle, n, q, 20 + i, batch) for i in range(k)]
@@ -162,12 +155,7 @@ def test_exports_the_six_symbols(lib):
 
 
 def test_rotate_example_builds_against_the_public_header(lib):
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    exe = os.path.join(ROOT, "build", "rns_rotate")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "rns_rotate.c"), "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x",
-                           "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-    assert os.path.exists(exe)
+    assert os.path.exists(children.build_example(lib, "rns_rotate", *children.STRICT))
 
 
 EXPECTED = {"galois_ntt_kernel<true>", "galois_ntt_kernel<false>", "galois_coef_kernel", "galois_dot_kernel"}

@@ -3,35 +3,31 @@ the model of tests/bgv_model.py: every moddown_bgv_fwd_kernel instance with 1, 2
 against the approximate calls, the sandwich at 2^15 and 2^16, integer-policy limbs, Q counts across the 16-limb run boundary, the edge
 words planted in the inputs for every edge T, layouts with canaries, argument errors that write nothing, a BGV multiplication on real
 encryptions through the library calls, the plain-C example, and one call of each form captured into a HIP graph."""
-import os
 import random
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import bgv_model as bm
+import children
 import ct_mul_model as cm
 import keyswitch_model as km
-import rescale_model as rm
-import test_gpu_rescale as tgr
+import rns_support as rs
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 T, A = bm.TRANSFORMED, bm.ACCUMULATE
-PT = 65537
+PT = bm.PT
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("np_", [1, 2, 4])
-@pytest.mark.parametrize("pol,k,logn", km.launch_cases(), ids=["%s-k%d-logn%d" % c for c in km.launch_cases()])
+@pytest.mark.parametrize("pol,k,logn", rs.fused_launch_cases(), ids=["%s-k%d-logn%d" % c for c in rs.fused_launch_cases()])
 def test_every_fused_instance(lib, oracle, pol, k, logn, np_):
     """each moddown_bgv_fwd_kernel<policy, LOGN, class>: three Q limbs of the class, np 60-bit P limbs, NTT domain, batch 3, T = 65537,
     the in-place form; at np = 2 the add form with ACCUMULATE as well"""
     n = 1 << logn
-    b = rm.CLASS_BITS[(pol, k)]
-    primes, roots = rm.chain(lib, n, [b] * 3 + [60] * np_)
+    b = rs.CLASS_BITS[(pol, k)]
+    primes, roots = rs.chain(lib, n, [b] * 3 + [60] * np_)
     bm.run_down(lib, oracle, primes, roots, np_, n, 3, PT, T, fused=1, seed=logn + np_)
     if np_ == 2:
         bm.run_down_add(lib, oracle, primes, roots, np_, n, 3, PT, T | A, fused=1, seed=logn, a_untouched=True)
@@ -41,7 +37,7 @@ def test_every_fused_instance(lib, oracle, pol, k, logn, np_):
 @pytest.mark.parametrize("logn,nq,np_", [(14, 16, 2), (9, 5, 1), (12, 20, 3), (13, 8, 8)])
 def test_fused_equals_sandwich_bit_for_bit(lib, oracle, logn, nq, np_):
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50] * nq + [60] * np_)
+    primes, roots = rs.chain(lib, n, [50] * nq + [60] * np_)
     fused = bm.run_down(lib, oracle, primes, roots, np_, n, 2, PT, T, fused=1, seed=3)
     sandwich = bm.run_down(lib, oracle, primes, roots, np_, n, 2, PT, T, fused=0, seed=3)
     for a, b in zip(fused, sandwich):
@@ -56,7 +52,7 @@ def test_fused_equals_sandwich_bit_for_bit(lib, oracle, logn, nq, np_):
 @pytest.mark.parametrize("flags", [0, T])
 def test_t_1_equals_the_approximate_calls_bit_for_bit(lib, oracle, flags):
     n, np_ = 1 << 10, 2
-    primes, roots = rm.chain(lib, n, [50] * 5 + [60] * np_)
+    primes, roots = rs.chain(lib, n, [50] * 5 + [60] * np_)
     for fused in ((1, 0) if flags & T else (None,)):
         got = bm.run_down(lib, oracle, primes, roots, np_, n, 2, 1, flags, fused=fused, seed=6)
         want = km.run_down(lib, oracle, primes, roots, np_, n, 2, flags, seed=6)
@@ -73,7 +69,7 @@ def test_t_1_equals_the_approximate_calls_bit_for_bit(lib, oracle, flags):
 @pytest.mark.parametrize("logn", [15, 16])
 def test_sandwich_at_large_sizes(lib, oracle, logn):
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50, 50, 50, 60, 60])
+    primes, roots = rs.chain(lib, n, [50, 50, 50, 60, 60])
     bm.run_down(lib, oracle, primes, roots, 2, n, 2, PT, T, seed=logn)
     bm.run_down_add(lib, oracle, primes, roots, 2, n, 2, PT, T | A, seed=logn + 1)
 
@@ -83,7 +79,7 @@ def test_sandwich_at_large_sizes(lib, oracle, logn):
 def test_integer_policy_limbs(lib, oracle, flags):
     """60-bit kept limbs (the wide integer policy): the coefficient kernel, or the sandwich around it"""
     n = 1 << 12
-    primes, roots = rm.chain(lib, n, [60] * 5)
+    primes, roots = rs.chain(lib, n, [60] * 5)
     bm.run_down(lib, oracle, primes, roots, 2, n, 3, PT, flags, seed=7)
     bm.run_down_add(lib, oracle, primes, roots, 2, n, 3, PT, flags | A, seed=8)
 
@@ -93,7 +89,7 @@ def test_integer_policy_limbs(lib, oracle, flags):
 @pytest.mark.parametrize("flags", [0, T])
 def test_q_counts_across_the_run_boundary(lib, oracle, nq, flags):
     n = 1 << 10
-    primes, roots = rm.chain(lib, n, [50] * nq + [60, 60, 60])
+    primes, roots = rs.chain(lib, n, [50] * nq + [60, 60, 60])
     bm.run_down(lib, oracle, primes, roots, 3, n, 2, PT, flags, seed=nq)
     bm.run_down_add(lib, oracle, primes, roots, 3, n, 2, PT, flags | A, seed=nq + 1)
 
@@ -105,7 +101,7 @@ def test_edge_words_planted_in_the_inputs(lib, oracle, np_, ti):
     """t_j in {0, 1, (p - 1) / 2, (p + 1) / 2, p - 1} with c in {0, q - 1} in front of every polynomial, for every edge T (T = q_0 makes
     [T]_{q_0} = 0): coefficients, the fused kernel and the sandwich, the add form beside the in-place one"""
     n = 1 << 8
-    primes, roots = rm.chain(lib, n, [50, 52, 51] + [60] * np_)
+    primes, roots = rs.chain(lib, n, [50, 52, 51] + [60] * np_)
     pt = bm.edge_ts(primes)[ti]
     bm.run_down(lib, oracle, primes, roots, np_, n, 2, pt, 0, seed=ti, edges=True)
     for fused in (1, 0):
@@ -118,7 +114,7 @@ def test_edge_words_planted_in_the_inputs(lib, oracle, np_, ti):
 @pytest.mark.parametrize("batch", [1, 3, 130])
 def test_layouts(lib, oracle, layout, batch):
     n = 1 << 8
-    primes, roots = rm.chain(lib, n, [50, 50, 50, 52, 60, 60])
+    primes, roots = rs.chain(lib, n, [50, 50, 50, 52, 60, 60])
     other = {"limb": "batch_padded", "batch": "limb_padded", "limb_padded": "batch", "batch_padded": "limb"}[layout]
     for flags in (0, T):
         bm.run_down(lib, oracle, primes, roots, 2, n, batch, PT, flags, layout=layout, seed=11)
@@ -130,11 +126,11 @@ def test_layouts(lib, oracle, layout, batch):
 @pytest.mark.gpu
 def test_argument_errors_write_nothing(lib, oracle):
     n, batch = 1 << 10, 2
-    primes, roots = rm.chain(lib, n, [50] * 18)
+    primes, roots = rs.chain(lib, n, [50] * 18)
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     other = lib.Plan(2 * n, lib.find_prime(50, 2 * n), lib.min_root(lib.find_prime(50, 2 * n), 2 * n))
     same = lib.Plan(n, primes[0], roots[0])
-    fwd_only = tgr._forward_only_plan(lib, n, primes[3], roots[3])
+    fwd_only = rs.forward_only_plan(lib, n, primes[3], roots[3])
     words = 18 * batch * n
     img = oracle.fill_uniform(words, primes[0], 5)
     cimg = oracle.fill_uniform(words, primes[0], 6)
@@ -180,7 +176,7 @@ def test_argument_errors_write_nothing(lib, oracle):
             call()
         unchanged(what)
     # a Q limb without the inverse table: refused where the sandwich serves it, served by the fused route
-    fwd_only_q = tgr._forward_only_plan(lib, n, primes[1], roots[1])
+    fwd_only_q = rs.forward_only_plan(lib, n, primes[1], roots[1])
     ps = [plans[0], fwd_only_q, plans[2], plans[3]]
     plans[0].set_option(lib.OPT_BGV_FUSED, 0)
     with pytest.raises(lib.NttError):
@@ -195,47 +191,13 @@ def test_argument_errors_write_nothing(lib, oracle):
 
 # ---------------------------------------------------------------- BGV through the library calls
 
-def _image(polys, n):
-    return np.concatenate([np.concatenate([np.asarray(l, dtype=np.uint64) for l in p]) for p in polys])
-
-
-def _bgv_mul_on_device(lib, bgv, ct1, ct2, keys):
-    """the sequence of examples/rns_bgv_mul.c; returns ((d0, d1) after relinearisation, (d0, d1) after the switch) as per-limb arrays"""
-    n, nq, nl, alpha, pt = bgv.n, bgv.nq, len(bgv.primes), bgv.alpha, bgv.T
-    plans = [lib.Plan(n, q, w) for q, w in zip(bgv.primes, bgv.roots)]
-    cp, ap = nq * n, nl * n
-    din = lib.DeviceBuffer(4 * cp).upload(_image([ct1[0], ct1[1], ct2[0], ct2[1]], n))
-    d, ext, acc = lib.DeviceBuffer(3 * cp), lib.DeviceBuffer(ap).upload(np.zeros(ap, dtype=np.uint64)), lib.DeviceBuffer(2 * ap)
-    kbufs = [lib.DeviceBuffer(2 * ap).upload(_image(key, n)) for key in keys]
-    try:
-        i = [din.ptr + 8 * j * cp for j in range(4)]
-        o = [d.ptr + 8 * j * cp for j in range(3)]
-        lib.rns_tensor(plans[:nq], o[0], o[1], o[2], i[0], i[1], i[2], i[3], 1, 0, layout=(n, cp))
-        lib.rns_inv(plans[:nq], o[2], 1, layout=(n, cp))
-        for k, kb in enumerate(kbufs):
-            lib.copy_probe(ext.ptr + 8 * alpha * k * n, o[2] + 8 * alpha * k * n, alpha * n)
-            lib.rns_mod_up_mul_pair(plans, acc.ptr, acc.ptr + 8 * ap, ext.ptr, alpha * k, alpha, kb.ptr, kb.ptr + 8 * ap, 1,
-                                    lib.MUL_B_BROADCAST | (lib.MUL_ACCUMULATE if k else 0), layout=(n, ap))
-        lib.rns_mod_down_bgv_add(plans, nl - nq, d.ptr, acc.ptr, pt, 2, T | A, layout=(n, cp, n, ap))
-        relin = d.download()
-        lib.rns_mod_down_bgv(plans[:nq], 1, d.ptr, pt, 2, T, layout=(n, cp))
-        switched = d.download()
-    finally:
-        for b in [din, d, ext, acc] + kbufs:
-            b.free()
-        for p in plans:
-            p.destroy()
-    cut = lambda img, limbs: [[img[j * cp + l * n:j * cp + (l + 1) * n] for l in range(limbs)] for j in range(2)]
-    return cut(relin, nq), cut(switched, nq - 1)
-
-
 @pytest.mark.gpu
 def test_bgv_multiplication_through_the_library_calls(lib, oracle):
     """N = 2^10, Q = 4 x 50 bits, P = 2 x 60 bits, two digits of two limbs, T = 65537, three ciphertext pairs of real encryptions under a
     ternary key: tensor, inverse of d2, the pair key products per digit, the BGV ModDown into (d0, d1), the BGV switch by q_3.  Every
     word equals the model, the relinearised product decrypts to m1 m2 and the switched one to m1 m2 q_3^-1 mod T"""
     n, nq, npp = 1 << 10, 4, 2
-    primes, roots = rm.chain(lib, n, [50] * nq + [60] * npp)
+    primes, roots = rs.chain(lib, n, [50] * nq + [60] * npp)
     rng = random.Random(10)
     bgv = bm.Bgv(oracle, primes, roots, nq, 2, n, PT, rng)
     keys = bgv.relin_keys()
@@ -243,7 +205,7 @@ def test_bgv_multiplication_through_the_library_calls(lib, oracle):
     for _ in range(3):
         m1, m2 = ([rng.randrange(PT) for _ in range(n)] for _ in range(2))
         ct1, ct2 = bgv.encrypt(m1), bgv.encrypt(m2)
-        relin, switched = _bgv_mul_on_device(lib, bgv, ct1, ct2, keys)
+        relin, switched = bm.mul_on_device(lib, bgv, ct1, ct2, keys)
         want_sw, want_relin, _ = bgv.multiply(ct1, ct2, keys)
         for j in range(2):
             for l in range(nq):
@@ -257,14 +219,9 @@ def test_bgv_multiplication_through_the_library_calls(lib, oracle):
 
 @pytest.mark.gpu
 def test_example_checksums_match_the_model(lib, oracle):
-    exe = os.path.join(ROOT, "build", "rns_bgv_mul")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "rns_bgv_mul.c"),
-                           "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x", "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-    r = subprocess.run(["timeout", "-k", "10", "120", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    out = children.run_example(lib, "rns_bgv_mul")
     got = {(int(m.group(1)), int(m.group(2))): int(m.group(3), 16)
-           for m in re.finditer(r"comp (\d+) limb (\d+) q \d+ checksum ([0-9a-f]+)", r.stdout)}
+           for m in re.finditer(r"comp (\d+) limb (\d+) q \d+ checksum ([0-9a-f]+)", out)}
     want = bm.example_model(lib, oracle)
     assert len(got) == 14 and got == want, sorted(k for k in want if got.get(k) != want[k])
 
@@ -275,8 +232,6 @@ def test_both_forms_captured_in_a_hip_graph():
     60-bit P limbs) captured one after the other on one stream into a HIP graph after ntt_plan_reserve (a linear capture) and replayed
     twice on fresh inputs (a process of its own: torch has to be imported before the library)"""
     code = """
-import sys
-sys.path.insert(0, %r); sys.path.insert(0, %r)
 import torch
 torch.cuda.set_device(0)
 import numpy as np
@@ -284,11 +239,11 @@ import ontt
 from oracle_binding import Oracle
 import bgv_model as bm
 import keyswitch_model as km
-import rescale_model as rm
+import rns_support as rs
 lib, orc = ontt.load(), Oracle()
 n, batch, np_, pt = 1 << 12, 3, 2, 65537
 T, A = bm.TRANSFORMED, bm.ACCUMULATE
-primes, roots = rm.chain(lib, n, [50] * 4 + [60] * np_)
+primes, roots = rs.chain(lib, n, [50] * 4 + [60] * np_)
 nq = len(primes) - np_
 plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
 words = len(primes) * batch * n
@@ -321,6 +276,5 @@ for seed in (1, 2):
     for l, w in enumerate(want):
         assert np.array_equal(got[l], w), ("add", seed, l)
 print("graph ok")
-""" % (ROOT, os.path.join(ROOT, "tests"))
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=ROOT)
-    assert out.returncode == 0 and "graph ok" in out.stdout, (out.stdout[-1000:], out.stderr[-3000:])
+"""
+    children.python_child(code, 300)

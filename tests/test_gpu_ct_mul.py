@@ -7,15 +7,14 @@ that write nothing; the plain-C example of a whole multiplication; and two kerne
 and the launch of all 38 new instances."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import children
 import ct_mul_model as cm
 import kernel_inventory
-import rescale_model as rm
-import test_gpu_rescale as tgr
+import rns_support as rs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODEL_PY = os.path.join(ROOT, "tests", "ct_mul_model.py")
@@ -31,7 +30,7 @@ MIXED = [60, 50, 30, 52]
 @pytest.mark.parametrize("logn", [1, 6, 12])
 def test_tensor_shapes(lib, oracle, logn, batch, nlimbs):
     n = 1 << logn
-    primes, _ = rm.chain(lib, n, [50] * nlimbs)
+    primes, _ = rs.chain(lib, n, [50] * nlimbs)
     cm.run_tensor(lib, oracle, primes, n, batch, cm.tensor_inputs(oracle, primes, n, batch, logn + batch))
 
 
@@ -41,7 +40,7 @@ def test_tensor_mixed_chain_and_extremes(lib, oracle, case):
     """60-, 50-, 30- and 52-bit limbs take the same integer kernel; all-zero and all-(q-1) words; with NTT_MUL_LAZY_IN all-(4q-1) words
     on the 60-bit and on the 30-bit limb"""
     n, batch = 1 << 12, 3
-    primes, _ = rm.chain(lib, n, MIXED)
+    primes, _ = rs.chain(lib, n, MIXED)
     lazy = {"lazy60": (0,), "lazy30": (2,)}.get(case, ())
     ops = cm.tensor_inputs(oracle, primes, n, batch, 9, fill=case if case in ("zero", "max") else None, lazy_limbs=lazy)
     cm.run_tensor(lib, oracle, primes, n, batch, ops, flags=cm.LAZY_IN if lazy else 0)
@@ -50,7 +49,7 @@ def test_tensor_mixed_chain_and_extremes(lib, oracle, case):
 @pytest.mark.gpu
 def test_tensor_squaring_and_in_place_by_aliasing(lib, oracle):
     n, batch = 1 << 10, 3
-    primes, _ = rm.chain(lib, n, MIXED)
+    primes, _ = rs.chain(lib, n, MIXED)
     ops = cm.tensor_inputs(oracle, primes, n, batch, 21)
     square = cm.run_tensor(lib, oracle, primes, n, batch, ops, mode="square")
     general = cm.run_tensor(lib, oracle, primes, n, batch, [ops[0], ops[1], [v.copy() for v in ops[0]], [v.copy() for v in ops[1]]])
@@ -64,7 +63,7 @@ def test_tensor_squaring_and_in_place_by_aliasing(lib, oracle):
 @pytest.mark.parametrize("layout", ["limb", "batch", "batch_padded", "limb_padded", "odd_limb_stride"])
 def test_tensor_layouts(lib, oracle, layout):
     n, batch = 1 << 11, 3
-    primes, _ = rm.chain(lib, n, [50, 50, 50, 52, 60, 60])
+    primes, _ = rs.chain(lib, n, [50, 50, 50, 52, 60, 60])
     if layout == "odd_limb_stride":
         ls = batch * n + 1
         layout = (ls, n, (len(primes) - 1) * ls + batch * n + 8)
@@ -76,13 +75,13 @@ def test_tensor_layouts(lib, oracle, layout):
 @pytest.mark.gpu
 @pytest.mark.parametrize("acc", [0, A], ids=["store", "accumulate"])
 @pytest.mark.parametrize("np_", [1, 3])
-@pytest.mark.parametrize("pol,k,logn", cm.launch_cases(), ids=["%s-k%d-logn%d" % c for c in cm.launch_cases()])
+@pytest.mark.parametrize("pol,k,logn", rs.fused_launch_cases(), ids=["%s-k%d-logn%d" % c for c in rs.fused_launch_cases()])
 def test_every_fused_instance(lib, oracle, pol, k, logn, np_, acc):
     """each ksfold_fwd_kernel<policy, LOGN, class>: three Q limbs of the class, np 60-bit P limbs, batch 3 (the tail of a workgroup
     that serves several blocks), round (even LOGN) / floor (odd); the accumulator's Q limbs unchanged, its P limbs in coefficients"""
     n = 1 << logn
-    b = rm.CLASS_BITS[(pol, k)]
-    primes, roots = rm.chain(lib, n, [b] * 3 + [60] * np_)
+    b = rs.CLASS_BITS[(pol, k)]
+    primes, roots = rs.chain(lib, n, [b] * 3 + [60] * np_)
     flags = T | acc | (F if logn % 2 else 0)
     cm.run_down_add(lib, oracle, primes, roots, np_, n, 3, flags, fused=1, seed=logn + np_, a_untouched=True)
 
@@ -95,7 +94,7 @@ def test_every_fused_instance(lib, oracle, pol, k, logn, np_, acc):
 @pytest.mark.parametrize("fused", [None, 0])
 def test_q_counts_across_the_run_boundary(lib, oracle, nq, flags, fused):
     n = 1 << 8
-    primes, roots = rm.chain(lib, n, [50] * nq + [60, 60, 60])
+    primes, roots = rs.chain(lib, n, [50] * nq + [60, 60, 60])
     cm.run_down_add(lib, oracle, primes, roots, 3, n, 2, flags, fused=fused, seed=nq)
 
 
@@ -108,7 +107,7 @@ def test_q_counts_across_the_run_boundary(lib, oracle, nq, flags, fused):
 def test_mixed_chains(lib, oracle, qbits, pbits, flags, acc):
     """integer-policy runs between FP64 runs; the coefficient domain (flags 0 and F)"""
     n = 1 << 12
-    primes, roots = rm.chain(lib, n, qbits + pbits)
+    primes, roots = rs.chain(lib, n, qbits + pbits)
     cm.run_down_add(lib, oracle, primes, roots, len(pbits), n, 3, flags | acc, seed=len(qbits))
 
 
@@ -118,7 +117,7 @@ def test_mixed_chains(lib, oracle, qbits, pbits, flags, acc):
 def test_integer_policy_limbs(lib, oracle, arith, flags):
     n = 1 << 12
     a = {"auto": lib.ARITH_AUTO, "u64": lib.ARITH_U64, "r4": lib.ARITH_U64_R4}[arith]
-    primes, roots = rm.chain(lib, n, [58] * 5 if arith != "auto" else [60] * 5)
+    primes, roots = rs.chain(lib, n, [58] * 5 if arith != "auto" else [60] * 5)
     plans = [lib.Plan(n, q, w, arith=a) for q, w in zip(primes, roots)]
     try:
         cm.run_down_add(lib, oracle, primes, roots, 2, n, 3, flags, plans=plans, seed=7)
@@ -131,7 +130,7 @@ def test_integer_policy_limbs(lib, oracle, arith, flags):
 @pytest.mark.parametrize("logn", [15, 16])
 def test_composition_at_large_sizes(lib, oracle, logn):
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50, 50, 60])
+    primes, roots = rs.chain(lib, n, [50, 50, 60])
     cm.run_down_add(lib, oracle, primes, roots, 1, n, 2, T | A, seed=logn)
 
 
@@ -139,7 +138,7 @@ def test_composition_at_large_sizes(lib, oracle, logn):
 @pytest.mark.parametrize("logn,nq,np_", [(14, 16, 2), (9, 5, 1), (12, 20, 3)])
 def test_fused_equals_composition_bit_for_bit(lib, oracle, logn, nq, np_):
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50] * nq + [60] * np_)
+    primes, roots = rs.chain(lib, n, [50] * nq + [60] * np_)
     fused = cm.run_down_add(lib, oracle, primes, roots, np_, n, 2, T | A, fused=1, seed=3, a_untouched=True)
     comp = cm.run_down_add(lib, oracle, primes, roots, np_, n, 2, T | A, fused=0, seed=3)
     sandwich = cm.run_down_add(lib, oracle, primes, roots, np_, n, 2, T | A, fused=0, rescale_fused=0, seed=3, cross_check=False)
@@ -153,7 +152,7 @@ def test_fused_equals_composition_bit_for_bit(lib, oracle, logn, nq, np_):
 @pytest.mark.parametrize("fused", [None, 0])
 def test_layouts(lib, oracle, c_layout, a_layout, flags, fused):
     n = 1 << 11
-    primes, roots = rm.chain(lib, n, [50, 50, 50, 52, 60, 60])
+    primes, roots = rs.chain(lib, n, [50, 50, 50, 52, 60, 60])
     cm.run_down_add(lib, oracle, primes, roots, 2, n, 3, flags, c_layout=c_layout, a_layout=a_layout, fused=fused, seed=11)
 
 
@@ -162,13 +161,13 @@ def test_layouts(lib, oracle, c_layout, a_layout, flags, fused):
 @pytest.mark.gpu
 def test_argument_errors_write_nothing(lib, oracle):
     n, batch = 1 << 10, 2
-    primes, roots = rm.chain(lib, n, [50] * 18)
+    primes, roots = rs.chain(lib, n, [50] * 18)
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     q2 = lib.find_prime(50, 2 * n)
     other = lib.Plan(2 * n, q2, lib.min_root(q2, 2 * n))
     same = lib.Plan(n, primes[0], roots[0])
-    fwd_only = tgr._forward_only_plan(lib, n, primes[3], roots[3])
-    fwd_only_q = tgr._forward_only_plan(lib, n, primes[1], roots[1])
+    fwd_only = rs.forward_only_plan(lib, n, primes[3], roots[3])
+    fwd_only_q = rs.forward_only_plan(lib, n, primes[1], roots[1])
     words = 18 * batch * n
     pat = oracle.fill_uniform(2 * words, primes[0], 5)
     buf = lib.DeviceBuffer(2 * words).upload(pat)
@@ -235,35 +234,20 @@ def test_argument_errors_write_nothing(lib, oracle):
 
 @pytest.mark.gpu
 def test_example_checksums_match_the_model(lib, oracle):
-    exe = os.path.join(ROOT, "build", "rns_ciphertext_mul")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "rns_ciphertext_mul.c"),
-                           "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x", "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-    r = subprocess.run(["timeout", "-k", "10", "120", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    out = children.run_example(lib, "rns_ciphertext_mul")
     got = {(int(m.group(1)), int(m.group(2))): int(m.group(3), 16)
-           for m in re.finditer(r"comp (\d+) limb (\d+) q \d+ checksum ([0-9a-f]+)", r.stdout)}
+           for m in re.finditer(r"comp (\d+) limb (\d+) q \d+ checksum ([0-9a-f]+)", out)}
     want = cm.example_model(lib, oracle)
     assert len(got) == 14 and got == want, sorted(k for k in want if got.get(k) != want[k])
 
 
 # ---------------------------------------------------------------- launch proofs
 
-def _traced(args, seconds):
-    """the kernels `python3 tests/ct_mul_model.py ARGS` launched in a fresh child process under a kernel trace"""
-    saved = tgr.MODEL_PY
-    tgr.MODEL_PY = MODEL_PY
-    try:
-        return tgr._traced(args, seconds)
-    finally:
-        tgr.MODEL_PY = saved
-
-
 @pytest.mark.gpu
 def test_route_proof_p_inverses_and_one_fused_launch():
     """2^14, 16 Q limbs of 50-bit primes and 2 P limbs of 60-bit primes, NTT domain, accumulating: the call launches the inverse
     transforms of the P limbs and exactly one ksfold_fwd_kernel, nothing else"""
-    launched = [k for k in _traced(["--route"], 300) if k.split("<")[0] not in rm.SETUP_KERNELS]
+    launched = [k for k in children.traced(MODEL_PY, ["--route"], 300) if k.split("<")[0] not in rs.SETUP_KERNELS]
     fused = [k for k in launched if k.startswith("ksfold_fwd_kernel")]
     assert fused == ["ksfold_fwd_kernel<ArithF64,14,1>"], launched
     others = [k for k in launched if not k.startswith("ksfold_fwd_kernel")]
@@ -273,7 +257,7 @@ def test_route_proof_p_inverses_and_one_fused_launch():
 
 @pytest.mark.gpu
 def test_launch_proof_every_new_instance():
-    launched = set(_traced([], 600))
-    want = {"ksfold_fwd_kernel<%s,%d,%d>" % (pol, logn, k) for pol, k, logn in cm.launch_cases()} | {"tensor_kernel", "ct_fold_kernel"}
+    launched = set(children.traced(MODEL_PY, [], 600))
+    want = rs.kernel_names("ksfold_fwd_kernel", rs.fused_launch_cases()) | {"tensor_kernel", "ct_fold_kernel"}
     assert len(want) == 38
     assert not sorted(want - launched), "instances never launched: %s" % sorted(want - launched)

@@ -3,33 +3,29 @@ forms).  Every output word against the model of tests/exact_bconv_model.py: ever
 primes, fused == sandwich, the sandwich at 2^15 and 2^16, integer-policy limbs, Q counts across the 16-limb run boundary, exact ModUp in
 both domains, the band words (B -+ 1) / 2 planted in the inputs, layouts with canaries, argument errors that write nothing, a BFV
 multiplication on real encryptions through the library calls, the plain-C example, and one call captured into a HIP graph."""
-import os
 import random
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import children
 import exact_bconv_model as xm
 import keyswitch_model as km
-import rescale_model as rm
-import test_gpu_rescale as tgr
+import rns_support as rs
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 T = xm.TRANSFORMED
 M = 65537
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("np_", [1, 2, 4])
-@pytest.mark.parametrize("pol,k,logn", km.launch_cases(), ids=["%s-k%d-logn%d" % c for c in km.launch_cases()])
+@pytest.mark.parametrize("pol,k,logn", rs.fused_launch_cases(), ids=["%s-k%d-logn%d" % c for c in rs.fused_launch_cases()])
 def test_every_fused_instance(lib, oracle, pol, k, logn, np_):
     """each moddown_exact_fwd_kernel<policy, LOGN, class>: three Q limbs of the class, np 60-bit P limbs, NTT domain, batch 3, m = 65537"""
     n = 1 << logn
-    b = rm.CLASS_BITS[(pol, k)]
-    primes, roots = rm.chain(lib, n, [b] * 3 + [60] * np_)
+    b = rs.CLASS_BITS[(pol, k)]
+    primes, roots = rs.chain(lib, n, [b] * 3 + [60] * np_)
     xm.run_down(lib, oracle, primes, roots, np_, n, 3, M, T, fused=1, seed=logn + np_)
 
 
@@ -37,7 +33,7 @@ def test_every_fused_instance(lib, oracle, pol, k, logn, np_):
 @pytest.mark.parametrize("logn,nq,np_", [(14, 16, 2), (9, 5, 1), (12, 20, 3), (13, 8, 8)])
 def test_fused_equals_sandwich_bit_for_bit(lib, oracle, logn, nq, np_):
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50] * nq + [60] * np_)
+    primes, roots = rs.chain(lib, n, [50] * nq + [60] * np_)
     fused = xm.run_down(lib, oracle, primes, roots, np_, n, 2, M, T, fused=1, seed=3)
     sandwich = xm.run_down(lib, oracle, primes, roots, np_, n, 2, M, T, fused=0, seed=3)
     for a, b in zip(fused, sandwich):
@@ -48,7 +44,7 @@ def test_fused_equals_sandwich_bit_for_bit(lib, oracle, logn, nq, np_):
 @pytest.mark.parametrize("logn", [15, 16])
 def test_sandwich_at_large_sizes(lib, oracle, logn):
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50, 50, 50, 60, 60])
+    primes, roots = rs.chain(lib, n, [50, 50, 50, 60, 60])
     xm.run_down(lib, oracle, primes, roots, 2, n, 2, M, T, seed=logn)
 
 
@@ -57,7 +53,7 @@ def test_sandwich_at_large_sizes(lib, oracle, logn):
 def test_integer_policy_limbs(lib, oracle, flags):
     """60-bit kept limbs (the wide integer policy): the coefficient kernel, or the sandwich around it; exact ModUp beside it"""
     n = 1 << 12
-    primes, roots = rm.chain(lib, n, [60] * 5)
+    primes, roots = rs.chain(lib, n, [60] * 5)
     xm.run_down(lib, oracle, primes, roots, 2, n, 3, M, flags, seed=7)
     xm.run_up(lib, oracle, primes, roots, 1, 2, n, 3, flags, seed=8)
 
@@ -68,7 +64,7 @@ def test_integer_policy_limbs(lib, oracle, flags):
 def test_mod_down_q_counts_across_the_run_boundary(lib, oracle, nq, flags):
     """several launches per call, band words in the P limbs: one v for all of them (mult = 1 keeps [m t]_P on the planted values)"""
     n = 1 << 10
-    primes, roots = rm.chain(lib, n, [50] * nq + [60, 60, 60])
+    primes, roots = rs.chain(lib, n, [50] * nq + [60, 60, 60])
     xm.run_down(lib, oracle, primes, roots, 3, n, 2, 1, flags, seed=nq, band=True)
     xm.run_down(lib, oracle, primes, roots, 3, n, 2, M, flags, seed=nq + 1)
 
@@ -79,7 +75,7 @@ def test_mod_down_q_counts_across_the_run_boundary(lib, oracle, nq, flags):
 @pytest.mark.parametrize("logn", [6, 12])
 def test_mod_up_exact(lib, oracle, nlimbs, first, count, flags, logn):
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [60] + [50] * (nlimbs - 3) + [60, 60])
+    primes, roots = rs.chain(lib, n, [60] + [50] * (nlimbs - 3) + [60, 60])
     xm.run_up(lib, oracle, primes, roots, first, count, n, 2, flags, seed=nlimbs + first)
 
 
@@ -90,9 +86,9 @@ def test_band_words_planted_in_the_inputs(lib, oracle, nb, bits, flags):
     """(B - 1) / 2 and (B + 1) / 2 in the digit of an exact ModUp to 18 limbs (two launches) and in the P limbs of an exact ModDown
     (coefficients; NTT domain: the fused kernel and the sandwich): the model's choice in every limb"""
     n = 1 << 8
-    primes, roots = rm.chain(lib, n, [bits] * nb + [52] * 18)
+    primes, roots = rs.chain(lib, n, [bits] * nb + [52] * 18)
     xm.run_up(lib, oracle, primes, roots, 0, nb, n, 2, flags, seed=nb, band=True)
-    primes, roots = rm.chain(lib, n, [52] * 18 + [bits] * nb)
+    primes, roots = rs.chain(lib, n, [52] * 18 + [bits] * nb)
     for fused in ((1, 0) if flags & T else (None,)):
         xm.run_down(lib, oracle, primes, roots, nb, n, 2, 1, flags, fused=fused, seed=nb, band=True)
 
@@ -102,7 +98,7 @@ def test_band_words_planted_in_the_inputs(lib, oracle, nb, bits, flags):
 @pytest.mark.parametrize("batch", [1, 3, 130])
 def test_layouts(lib, oracle, layout, batch):
     n = 1 << 8
-    primes, roots = rm.chain(lib, n, [50, 50, 50, 52, 60, 60])
+    primes, roots = rs.chain(lib, n, [50, 50, 50, 52, 60, 60])
     for flags in (0, T):
         xm.run_down(lib, oracle, primes, roots, 2, n, batch, M, flags, layout=layout, seed=11)
         xm.run_up(lib, oracle, primes, roots, 1, 2, n, batch, flags, layout=layout, seed=12)
@@ -111,11 +107,11 @@ def test_layouts(lib, oracle, layout, batch):
 @pytest.mark.gpu
 def test_argument_errors_write_nothing(lib, oracle):
     n, batch = 1 << 10, 2
-    primes, roots = rm.chain(lib, n, [50] * 18)
+    primes, roots = rs.chain(lib, n, [50] * 18)
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     other = lib.Plan(2 * n, lib.find_prime(50, 2 * n), lib.min_root(lib.find_prime(50, 2 * n), 2 * n))
     same = lib.Plan(n, primes[0], roots[0])
-    fwd_only = tgr._forward_only_plan(lib, n, primes[3], roots[3])
+    fwd_only = rs.forward_only_plan(lib, n, primes[3], roots[3])
     words = 18 * batch * n
     img = oracle.fill_uniform(words, primes[0], 5)
     buf = lib.DeviceBuffer(words).upload(img)
@@ -157,7 +153,7 @@ def test_argument_errors_write_nothing(lib, oracle):
             lib.rns_mod_up_exact(ps, ptr, first, count, batch, flags, layout=lay)
         assert np.array_equal(buf.download(), img), what
     # a Q limb without the inverse table: refused where the sandwich serves it, served by the fused route
-    fwd_only_q = tgr._forward_only_plan(lib, n, primes[1], roots[1])
+    fwd_only_q = rs.forward_only_plan(lib, n, primes[1], roots[1])
     ps = [plans[0], fwd_only_q, plans[2], plans[3]]
     plans[0].set_option(lib.OPT_RESCALE_FUSED, 0)
     with pytest.raises(lib.NttError):
@@ -172,39 +168,13 @@ def test_argument_errors_write_nothing(lib, oracle):
 
 # ---------------------------------------------------------------- BFV through the library calls
 
-def _bfv_on_device(lib, primes, roots, nr, t, ct_ntt, n):
-    """the example's four calls on [4][nr + nq][n] / [3][nr + nq][n] buffers; returns the three result polynomials' limbs"""
-    nl = len(primes)
-    plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
-    poly = nl * n
-    img = np.zeros(4 * poly, dtype=np.uint64)
-    for j, p in enumerate(ct_ntt):
-        for l, c in enumerate(p):
-            img[j * poly + (nr + l) * n:j * poly + (nr + l + 1) * n] = c
-    din, d = lib.DeviceBuffer(4 * poly).upload(img), lib.DeviceBuffer(3 * poly)
-    try:
-        lay = (n, poly)
-        lib.rns_mod_up_exact(plans, din.ptr, nr, nl - nr, 4, T, layout=lay)
-        o = [d.ptr + 8 * j * poly for j in range(3)]
-        i = [din.ptr + 8 * j * poly for j in range(4)]
-        lib.rns_tensor(plans, o[0], o[1], o[2], i[0], i[1], i[2], i[3], 1, 0, layout=lay)
-        lib.rns_mod_down_exact(plans, nl - nr, d.ptr, t, 3, T, layout=lay)
-        lib.rns_mod_up_exact(plans, d.ptr, 0, nr, 3, T, layout=lay)
-        out = d.download()
-    finally:
-        din.free(), d.free()
-        for p in plans:
-            p.destroy()
-    return [[out[j * poly + l * n:j * poly + (l + 1) * n] for l in range(nl)] for j in range(3)]
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("logn", [6, 10])
 def test_bfv_multiplication_through_the_library_calls(lib, oracle, logn):
     """real encryptions under a ternary key, Q = 2 x 50 bits, R = 3 x 50 bits, t = 65537: the sequence of examples/rns_bfv_mul.c
     decrypts to m1 m2 mod t, and every word of the result (R limbs included) equals the model"""
     n, nr, nq, t = 1 << logn, 3, 2, 65537
-    primes, roots = rm.chain(lib, n, [50] * (nr + nq))
+    primes, roots = rs.chain(lib, n, [50] * (nr + nq))
     qp, qr = primes[nr:], roots[nr:]
     Q = km.prod(qp)
     rng = random.Random(logn)
@@ -212,7 +182,7 @@ def test_bfv_multiplication_through_the_library_calls(lib, oracle, logn):
     m1, m2 = ([rng.randrange(t) for _ in range(n)] for _ in range(2))
     ct = [p for m in (m1, m2) for p in xm.bfv_encrypt(rng, s, m, n, Q, t)]
     ntt = [[oracle.ctx(n, q, w).fwd(c) for q, w, c in zip(qp, qr, km.residues(p, qp))] for p in ct]
-    got = _bfv_on_device(lib, primes, roots, nr, t, ntt, n)
+    got = xm.bfv_on_device(lib, primes, roots, nr, t, ntt, n)
     want, (_, _, _, back) = xm.bfv_mul(oracle, primes, roots, nr, t, *ntt, n)
     for j in range(3):
         for l in range(nr + nq):
@@ -223,14 +193,9 @@ def test_bfv_multiplication_through_the_library_calls(lib, oracle, logn):
 
 @pytest.mark.gpu
 def test_example_checksums_match_the_model(lib, oracle):
-    exe = os.path.join(ROOT, "build", "rns_bfv_mul")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "rns_bfv_mul.c"),
-                           "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x", "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-    r = subprocess.run(["timeout", "-k", "10", "120", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    out = children.run_example(lib, "rns_bfv_mul")
     got = {(int(m.group(1)), int(m.group(2))): int(m.group(3), 16)
-           for m in re.finditer(r"comp (\d+) limb (\d+) q \d+ checksum ([0-9a-f]+)", r.stdout)}
+           for m in re.finditer(r"comp (\d+) limb (\d+) q \d+ checksum ([0-9a-f]+)", out)}
     want = xm.example_model(lib, oracle)
     assert len(got) == 12 and got == want, sorted(k for k in want if got.get(k) != want[k])
 
@@ -240,18 +205,16 @@ def test_mod_down_exact_captured_in_a_hip_graph():
     """one ntt_rns_mod_down_exact_batch call (NTT domain, 2^12, four 50-bit Q limbs and two 60-bit P limbs) captured into a HIP graph
     after ntt_plan_reserve and replayed twice on fresh inputs (a process of its own: torch has to be imported before the library)"""
     code = """
-import sys
-sys.path.insert(0, %r); sys.path.insert(0, %r)
 import torch
 torch.cuda.set_device(0)
 import numpy as np
 import ontt
 from oracle_binding import Oracle
 import exact_bconv_model as xm
-import rescale_model as rm
+import rns_support as rs
 lib, orc = ontt.load(), Oracle()
 n, batch, np_, mult = 1 << 12, 3, 2, 65537
-primes, roots = rm.chain(lib, n, [50] * 4 + [60] * np_)
+primes, roots = rs.chain(lib, n, [50] * 4 + [60] * np_)
 plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
 words = len(primes) * batch * n
 buf = torch.zeros(words, dtype=torch.int64, device="cuda:0")
@@ -272,6 +235,5 @@ for seed in (1, 2):
     for l, w in enumerate(want + t):
         assert np.array_equal(got[l], w), (seed, l)
 print("graph ok")
-""" % (ROOT, os.path.join(ROOT, "tests"))
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=ROOT)
-    assert out.returncode == 0 and "graph ok" in out.stdout, (out.stdout[-1000:], out.stderr[-3000:])
+"""
+    children.python_child(code, 300)

@@ -7,15 +7,14 @@ write nothing, the plain-C example; and one kernel trace: 17 limbs are two galoi
 galois_dot_kernel."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import children
 import galois_model as gm
-import rescale_model as rm
+import rns_support as rs
 import keyswitch_model as km
-import test_gpu_rescale as tgr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODEL_PY = os.path.join(ROOT, "tests", "galois_model.py")
@@ -34,7 +33,7 @@ def test_sizes_and_galois_elements(lib, oracle, logn, flags):
     """every g of the list on a mixed chain, two polynomials (2^16: the first size where a polynomial exceeds any one workgroup's
     share)"""
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, MIXED if logn < 16 else [60, 30])
+    primes, roots = rs.chain(lib, n, MIXED if logn < 16 else [60, 30])
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     limbs = gm.operand(oracle, primes, n, 2, logn)
     try:
@@ -50,7 +49,7 @@ def test_sizes_and_galois_elements(lib, oracle, logn, flags):
 @pytest.mark.parametrize("flags", [0, T], ids=["coef", "ntt"])
 def test_batches(lib, oracle, batch, flags):
     n = 1 << 8
-    primes, roots = rm.chain(lib, n, MIXED)
+    primes, roots = rs.chain(lib, n, MIXED)
     for g in (5, n + 1, 2 * n - 1):
         gm.run_galois(lib, oracle, primes, roots, n, batch, g, flags, seed=batch)
 
@@ -60,7 +59,7 @@ def test_batches(lib, oracle, batch, flags):
 @pytest.mark.parametrize("flags", [0, T], ids=["coef", "ntt"])
 def test_limb_counts_across_the_launch_boundary(lib, oracle, nlimbs, flags):
     n = 1 << 10
-    primes, roots = rm.chain(lib, n, _bits(nlimbs))
+    primes, roots = rs.chain(lib, n, _bits(nlimbs))
     for g in (25, 2 * n - 1):
         gm.run_galois(lib, oracle, primes, roots, n, 2, g, flags, seed=nlimbs)
 
@@ -71,7 +70,7 @@ def test_integer_policy_plans_and_the_one_limb_form(lib, oracle, arith):
     """ARITH_U64 and ARITH_U64_R4 at 58 bits, AUTO at 60 bits; Plan.galois beside the RNS form"""
     n, batch = 1 << 12, 3
     a = {"auto": lib.ARITH_AUTO, "u64": lib.ARITH_U64, "r4": lib.ARITH_U64_R4}[arith]
-    primes, roots = rm.chain(lib, n, [58] * 3 if arith != "auto" else [60] * 3)
+    primes, roots = rs.chain(lib, n, [58] * 3 if arith != "auto" else [60] * 3)
     plans = [lib.Plan(n, q, w, arith=a) for q, w in zip(primes, roots)]
     try:
         g = gm.rotation(n, 7)
@@ -94,7 +93,7 @@ def test_integer_policy_plans_and_the_one_limb_form(lib, oracle, arith):
 def test_ntt_domain_passes_lazy_words_through(lib, oracle):
     """words >= q (a lazy forward output, a buffer of 2^64 - 1) come out bit-identical"""
     n, batch = 1 << 12, 2
-    primes, roots = rm.chain(lib, n, [50, 60])
+    primes, roots = rs.chain(lib, n, [50, 60])
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     try:
         lazy = [p.fwd_host(oracle.fill_uniform(batch * n, q, 9), lazy=True) for p, q in zip(plans, primes)]
@@ -112,7 +111,7 @@ def test_ntt_domain_passes_lazy_words_through(lib, oracle):
 @pytest.mark.parametrize("flags", [T, T | ACC, T | BC, T | ACC | BC], ids=["plain", "acc", "bcast", "acc-bcast"])
 def test_dot(lib, oracle, k, flags):
     n = 1 << 10
-    primes, roots = rm.chain(lib, n, _bits(5))
+    primes, roots = rs.chain(lib, n, _bits(5))
     gm.run_dot(lib, oracle, primes, roots, n, 2, k, gm.rotation(n, k), flags, seed=k)
 
 
@@ -121,7 +120,7 @@ def test_dot(lib, oracle, k, flags):
 @pytest.mark.parametrize("logn", [6, 12, 14, 16])
 def test_dot_sizes_and_limb_counts(lib, oracle, logn, nlimbs):
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, _bits(nlimbs))
+    primes, roots = rs.chain(lib, n, _bits(nlimbs))
     gm.run_dot(lib, oracle, primes, roots, n, 2, 3, gm.rotation(n, -5), T | ACC | (BC if logn % 4 else 0), seed=logn)
 
 
@@ -130,7 +129,7 @@ def test_dot_sizes_and_limb_counts(lib, oracle, logn, nlimbs):
 def test_dot_of_32_extreme_products(lib, oracle, flags):
     """every operand word q - 1, k = 32, 60-bit primes: the largest sum the 128-bit accumulator sees"""
     n = 1 << 8
-    primes, roots = rm.chain(lib, n, [60, 60, 60])
+    primes, roots = rs.chain(lib, n, [60, 60, 60])
     gm.run_dot(lib, oracle, primes, roots, n, 2, 32, 2 * n - 1, flags, extreme=True)
 
 
@@ -139,7 +138,7 @@ def test_both_domains_and_the_dot_agree_on_the_device(lib, oracle):
     """rns_inv(dot) == sum_i sigma_g(a_i) key_i with the coefficient automorphism's outputs and rns_negacyclic_mul (N = 2^12, k = 3,
     4 limbs)"""
     n, batch, k = 1 << 12, 2, 3
-    primes, roots = rm.chain(lib, n, MIXED)
+    primes, roots = rs.chain(lib, n, MIXED)
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     g = gm.rotation(n, 11)
     words = len(primes) * batch * n
@@ -179,7 +178,7 @@ def test_both_domains_and_the_dot_agree_on_the_device(lib, oracle):
 @pytest.mark.parametrize("layout", ["limb", "batch", "batch_padded", "limb_padded"])
 def test_layouts(lib, oracle, layout):
     n = 1 << 11
-    primes, roots = rm.chain(lib, n, MIXED + [50])
+    primes, roots = rs.chain(lib, n, MIXED + [50])
     g = gm.rotation(n, 3)
     gm.run_galois(lib, oracle, primes, roots, n, 3, g, 0, layout=layout, seed=11)
     gm.run_galois(lib, oracle, primes, roots, n, 3, g, T, layout=layout, seed=12)
@@ -191,18 +190,18 @@ def test_layouts(lib, oracle, layout):
 def test_ntt_domain_with_operands_off_the_16_byte_grid(lib, oracle):
     """buffers that start 8 bytes off a 16-byte boundary (the one-slot-per-lane kernel) give the same words"""
     n, batch = 1 << 10, 3
-    primes, roots = rm.chain(lib, n, [50, 60])
+    primes, roots = rs.chain(lib, n, [50, 60])
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     limbs = gm.operand(oracle, primes, n, batch, 21)
     img = np.concatenate(limbs)
     src, dst = lib.DeviceBuffer(img.size + 2), lib.DeviceBuffer(img.size + 2)
     try:
-        src.upload(np.concatenate([[rm.CANARY], img, [rm.CANARY]]).astype(np.uint64))
-        dst.upload(np.full(img.size + 2, rm.CANARY, dtype=np.uint64))
+        src.upload(np.concatenate([[rs.CANARY], img, [rs.CANARY]]).astype(np.uint64))
+        dst.upload(np.full(img.size + 2, rs.CANARY, dtype=np.uint64))
         g = gm.rotation(n, 9)
         lib.rns_galois(plans, dst.ptr + 8, src.ptr + 8, g, batch, T)
         got = dst.download()
-        assert got[0] == rm.CANARY and got[-1] == rm.CANARY
+        assert got[0] == rs.CANARY and got[-1] == rs.CANARY
         assert np.array_equal(got[1:-1], np.concatenate([gm.ntt_model(x, n, g) for x in limbs]))
     finally:
         src.free(), dst.free()
@@ -213,7 +212,7 @@ def test_ntt_domain_with_operands_off_the_16_byte_grid(lib, oracle):
 @pytest.mark.gpu
 def test_argument_errors_write_nothing(lib, oracle):
     n, batch, nl = 1 << 10, 2, 3
-    primes, roots = rm.chain(lib, n, [50] * nl)
+    primes, roots = rs.chain(lib, n, [50] * nl)
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     q2 = lib.find_prime(50, 2 * n)
     other = lib.Plan(2 * n, q2, lib.min_root(q2, 2 * n))
@@ -282,14 +281,9 @@ def test_argument_errors_write_nothing(lib, oracle):
 
 @pytest.mark.gpu
 def test_example_checksums_match_the_model(lib, oracle):
-    exe = os.path.join(ROOT, "build", "rns_rotate")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "rns_rotate.c"),
-                           "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x", "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-    r = subprocess.run(["timeout", "-k", "10", "120", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    out = children.run_example(lib, "rns_rotate")
     got = {(int(m.group(1)), m.group(2), int(m.group(3)), int(m.group(4))): int(m.group(5), 16)
-           for m in re.finditer(r"rotation (\d+) (\w+) poly (\d+) limb (\d+) q \d+ checksum ([0-9a-f]+)", r.stdout)}
+           for m in re.finditer(r"rotation (\d+) (\w+) poly (\d+) limb (\d+) q \d+ checksum ([0-9a-f]+)", out)}
     n, nq, np_, alpha, digits = 1 << 13, 8, 2, 2, 4
     primes = [lib.find_prime(60, n, 0)] + [lib.find_prime(50, n, k) for k in range(7)] + [lib.find_prime(60, n, k) for k in (1, 2)]
     roots = [lib.min_root(q, n) for q in primes]
@@ -316,19 +310,9 @@ def test_example_checksums_match_the_model(lib, oracle):
                 assert got[(r_, "c0", p, l)] == oracle.checksum(gm.ntt_model(c0, n, g)), (r_, p, l)
 
 
-def _traced(args, seconds):
-    """the kernels `python3 tests/galois_model.py ARGS` launched in a fresh child process under a kernel trace"""
-    saved = tgr.MODEL_PY
-    tgr.MODEL_PY = MODEL_PY
-    try:
-        return tgr._traced(args, seconds)
-    finally:
-        tgr.MODEL_PY = saved
-
-
 @pytest.mark.gpu
 def test_route_proof_two_launches_for_17_limbs_and_one_for_a_dot_over_16():
-    launched = [k for k in _traced(["--route"], 300) if k.split("<")[0] not in rm.SETUP_KERNELS]
+    launched = [k for k in children.traced(MODEL_PY, ["--route"], 300) if k.split("<")[0] not in rs.SETUP_KERNELS]
     assert len(launched) == 3, launched
     assert all(k.startswith("galois_ntt_kernel") for k in launched[:2]), launched
     assert launched[2] == "galois_dot_kernel", launched

@@ -3,15 +3,11 @@ column), the coefficient-domain product families (fused_product, fused_product_s
 families (dot_inv, fwd_mul, team_dot, team_mul, onepass_mul) and the pointwise kernels -- launched and checked word for word
 against the oracle; a kernel trace, one traced child per family, proves that the recipes launch every instance they claim; route
 precedence of explicit plan options over the automatic one-pass choice."""
-import csv
-import glob
 import os
-import subprocess
-import sys
-import tempfile
 
 import pytest
 
+import children
 import kernel_inventory
 import kernel_recipes
 
@@ -25,38 +21,6 @@ _CASES = kernel_recipes.cases()
 @pytest.mark.parametrize("case", _CASES, ids=[c.id for c in _CASES])
 def test_instance(lib, oracle, case):
     case.run(lib, oracle)
-
-
-def _rocprofv3():
-    for exe in ("/opt/rocm/bin/rocprofv3",):
-        if os.path.exists(exe):
-            return exe
-    import shutil
-    exe = shutil.which("rocprofv3")
-    if not exe:
-        pytest.fail("rocprofv3 is not on this machine: the launch proof needs its kernel trace")
-    return exe
-
-
-def _traced(args, seconds):
-    """run `python3 tests/kernel_recipes.py ARGS` in a fresh child process under a kernel trace; the set of normalised kernel
-    names it launched"""
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["timeout", "-k", "10", str(seconds), _rocprofv3(), "--kernel-trace", "--output-format", "csv", "-d", d, "--",
-               sys.executable, RECIPES_PY] + list(args)
-        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True)
-        assert r.returncode == 0, "traced run failed (exit %d):\n%s\n%s" % (r.returncode, r.stdout[-4000:], r.stderr[-4000:])
-        names = set()
-        files = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
-        assert files, "the kernel trace wrote no CSV:\n" + r.stderr[-2000:]
-        for f in files:
-            with open(f, newline="") as fh:
-                for row in csv.DictReader(fh):
-                    names.add(row["Kernel_Name"])
-    mangled = sorted(n for n in names if n.startswith("_Z"))
-    keys = {kernel_inventory.normalise(n) for n in names if not n.startswith("_Z")}
-    keys |= {kernel_inventory.normalise(n) for n in kernel_inventory.demangle(mangled)}
-    return keys
 
 
 # Limit of each family's traced child, seconds: 3 x the untraced wall time of `python3 tests/kernel_recipes.py --family NAME` on an
@@ -81,18 +45,12 @@ FAMILY_LIMITS = {
 
 
 _TRACES = {}   # family -> the kernels its traced child launched (one child per family and session)
-_BROKEN = []   # the family whose traced child did not end cleanly: no further child is started on the GPU after it
 
 
 def _family_trace(family):
+    """(after a child that did not end cleanly, tests/children.py starts no further one)"""
     if family not in _TRACES:
-        if _BROKEN:
-            pytest.fail("not started: the traced child of %s did not end cleanly" % _BROKEN[0])
-        try:
-            _TRACES[family] = _traced(["--family", family], FAMILY_LIMITS[family])
-        except BaseException:
-            _BROKEN.append(family)
-            raise
+        _TRACES[family] = set(children.traced(RECIPES_PY, ["--family", family], FAMILY_LIMITS[family]))
     return _TRACES[family]
 
 
@@ -137,6 +95,6 @@ def test_every_covered_instance_is_launched():
 def test_explicit_xcd_local_wins_over_the_automatic_one_pass_choice(route, want, unwanted):
     """N = 2^15, 50-bit prime, NTT_OPT_XCD_LOCAL 1, 131 polynomials (2 x 131 >= the CU count: the automatic one-pass choice
     would take it): the trace shows the XCD-local kernel and no one-pass kernel"""
-    fams = {kernel_inventory.parse(k).family for k in _traced(["--precedence", route], 300)}
+    fams = {kernel_inventory.parse(k).family for k in children.traced(RECIPES_PY, ["--precedence", route], 300)}
     assert want in fams, (route, sorted(f for f in fams if f))
     assert unwanted not in fams, (route, sorted(f for f in fams if f))

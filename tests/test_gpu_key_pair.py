@@ -6,26 +6,21 @@ words, the composition route (integer policies, N = 2^5, 2^15, 2^16, mixed chain
 pair, argument errors that write nothing, the plain-C example against the model, and one kernel trace."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import children
 import galois_model as gm
 import kernel_inventory
 import key_pair_model as kp
 import keyswitch_model as km
-import rescale_model as rm
-import test_gpu_rescale as tgr
+import rns_support as rs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODEL_PY = os.path.join(ROOT, "tests", "key_pair_model.py")
 L, B, A = kp.LAZY_IN, kp.BROADCAST, kp.ACCUMULATE
 T, GA, GB = gm.TRANSFORMED, gm.ACCUMULATE, gm.KEY_BROADCAST
-
-
-def _plans(lib, n, primes, roots, arith=None):
-    return [lib.Plan(n, q, w) if arith is None else lib.Plan(n, q, w, arith=arith) for q, w in zip(primes, roots)]
 
 
 def _destroy(plans):
@@ -34,16 +29,16 @@ def _destroy(plans):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("pol,k,logn", kp.launch_cases(), ids=["%s-k%d-logn%d" % c for c in kp.launch_cases()])
+@pytest.mark.parametrize("pol,k,logn", rs.fused_launch_cases(), ids=["%s-k%d-logn%d" % c for c in rs.fused_launch_cases()])
 def test_every_instance(lib, oracle, pol, k, logn):
     """each modup_mul2_kernel<policy, LOGN, class>: three limbs of the class and two 60-bit limbs; digits of one and of two FP64
     limbs, and the 60-bit digit feeding the FP64 run (its own run on the composition); accumulate and broadcast each way.  The same
     instance through ntt_rns_fwd_mul_pair_batch over the three FP64 limbs: d_a is left as it was"""
     n = 1 << logn
-    b = rm.CLASS_BITS[(pol, k)]
+    b = rs.CLASS_BITS[(pol, k)]
     batch = 3 if logn < 9 else 2
-    primes, roots = rm.chain(lib, n, [b, b, b, 60, 60])
-    plans = _plans(lib, n, primes, roots)
+    primes, roots = rs.chain(lib, n, [b, b, b, 60, 60])
+    plans = rs.plans(lib, n, primes, roots)
     try:
         for (first, count), flags in (((0, 1), 0), ((1, 2), A | B), ((3, 2), B)):
             _, ext, _ = kp.run(lib, oracle, primes, roots, first, count, n, batch, flags, fused=1, seed=logn + first, plans=plans)
@@ -63,8 +58,8 @@ def test_route_proof_by_the_sentinel(lib, oracle, logn, nlimbs, first, count):
     """an all-FP64 chain.  NTT_OPT_PAIR_FUSED 1: the sentinel in every non-digit slot of d_ext survives, the digit is unchanged;
     0: the same c0^, c1^ bit for bit, and no slot of d_ext holds the sentinel any more (the run was transformed in place)"""
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50] * nlimbs)
-    plans = _plans(lib, n, primes, roots)
+    primes, roots = rs.chain(lib, n, [50] * nlimbs)
+    plans = rs.plans(lib, n, primes, roots)
     digit = range(first, first + count)
     try:
         c1, ext1, up = kp.run(lib, oracle, primes, roots, first, count, n, 2, A | B, fused=1, seed=3, plans=plans)
@@ -87,8 +82,8 @@ def test_route_proof_by_the_sentinel(lib, oracle, logn, nlimbs, first, count):
 def test_fwd_mul_pair_routes(lib, oracle, logn):
     """NTT_OPT_PAIR_FUSED 1: d_a unchanged; 0: the same outputs and d_a holds fwd(a); both equal the two single calls"""
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50, 50, 52, 50])
-    plans = _plans(lib, n, primes, roots)
+    primes, roots = rs.chain(lib, n, [50, 50, 52, 50])
+    plans = rs.plans(lib, n, primes, roots)
     try:
         c1, after1, a, fa = kp.run_fwd(lib, oracle, primes, roots, n, 3, A | B, fused=1, seed=4, plans=plans, single=True)
         c0, after0, _, _ = kp.run_fwd(lib, oracle, primes, roots, n, 3, A | B, fused=0, seed=4, plans=plans, single=True)
@@ -106,7 +101,7 @@ def test_fwd_mul_pair_routes(lib, oracle, logn):
 def test_grid_stride_loop_wraps(lib, oracle, bits, first, count):
     """2^14, 5 polynomials, NTT_OPT_MAX_GRID 2: two workgroups for the one FP64 limb (rounds of 2, 2 and 1 blocks), or one per limb"""
     n = 1 << 14
-    primes, roots = rm.chain(lib, n, bits)
+    primes, roots = rs.chain(lib, n, bits)
     kp.run(lib, oracle, primes, roots, first, count, n, 5, A | B, fused=1, seed=14, max_grid=2)
 
 
@@ -115,7 +110,7 @@ def test_grid_stride_loop_wraps(lib, oracle, bits, first, count):
 def test_batches(lib, oracle, logn, batch):
     """several blocks per workgroup with the last group partly dead (2^8: 73), one polynomial, 130"""
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50, 50, 50, 60])
+    primes, roots = rs.chain(lib, n, [50, 50, 50, 60])
     kp.run(lib, oracle, primes, roots, 1, 2, n, batch, A, fused=1, seed=batch)
     kp.run(lib, oracle, primes, roots, 3, 1, n, batch, B, fused=1, seed=batch + 1)
     kp.run_fwd(lib, oracle, primes[:3], roots[:3], n, batch, A | B, fused=1, seed=batch + 2)
@@ -128,7 +123,7 @@ def test_batches(lib, oracle, logn, batch):
 def test_digit_positions(lib, oracle, nlimbs, first, count, fused):
     """digits at the start, in the middle and at the end (inside P), of 1 and of 16 limbs, chains of more than 16 limbs"""
     n = 1 << 10
-    primes, roots = rm.chain(lib, n, [60] + [50] * (nlimbs - 3) + [60, 60])
+    primes, roots = rs.chain(lib, n, [60] + [50] * (nlimbs - 3) + [60, 60])
     kp.run(lib, oracle, primes, roots, first, count, n, 2, A | B, fused=fused, seed=nlimbs + first)
 
 
@@ -136,9 +131,9 @@ def test_digit_positions(lib, oracle, nlimbs, first, count, fused):
 def test_digit_of_largest_words(lib, oracle):
     """every digit word b_i - 1 over 16 limbs: the largest 128-bit sum"""
     n = 1 << 10
-    primes, roots = rm.chain(lib, n, [50] * 18)
+    primes, roots = rs.chain(lib, n, [50] * 18)
     kp.run(lib, oracle, primes, roots, 1, 16, n, 2, A, fused=1, seed=5, digit_max=True)
-    primes, roots = rm.chain(lib, n, [60] * 16 + [50, 52])
+    primes, roots = rs.chain(lib, n, [60] * 16 + [50, 52])
     kp.run(lib, oracle, primes, roots, 0, 16, n, 2, B, fused=1, seed=6, digit_max=True)
 
 
@@ -147,7 +142,7 @@ def test_digit_of_largest_words(lib, oracle):
 @pytest.mark.parametrize("flags", [A, B, A | B])
 def test_layouts(lib, oracle, layout, flags):
     n = 1 << 11
-    primes, roots = rm.chain(lib, n, [50, 50, 50, 52, 60, 60])
+    primes, roots = rs.chain(lib, n, [50, 50, 50, 52, 60, 60])
     kp.run(lib, oracle, primes, roots, 1, 2, n, 3, flags, layout=layout, fused=1, seed=11)
     kp.run_fwd(lib, oracle, primes, roots, n, 3, flags, layout=layout, fused=1, seed=12)
 
@@ -158,7 +153,7 @@ def test_layouts(lib, oracle, layout, flags):
 def test_lazy_key_words(lib, oracle, flags, fused):
     """key words up to min(4q, 2^53) - 1"""
     n = 1 << 10
-    primes, roots = rm.chain(lib, n, [50, 51, 30, 52, 50])
+    primes, roots = rs.chain(lib, n, [50, 51, 30, 52, 50])
     kp.run(lib, oracle, primes, roots, 0, 1, n, 3, flags, fused=fused, seed=21, single=True)
     kp.run_fwd(lib, oracle, primes, roots, n, 3, flags, fused=fused, seed=22, single=True)
 
@@ -170,8 +165,8 @@ def test_composition_integer_policies(lib, oracle, arith, bits):
     says"""
     n = 1 << 12
     a = {"auto": lib.ARITH_AUTO, "u64": lib.ARITH_U64, "r4": lib.ARITH_U64_R4}[arith]
-    primes, roots = rm.chain(lib, n, [bits] * 5)
-    plans = _plans(lib, n, primes, roots, a)
+    primes, roots = rs.chain(lib, n, [bits] * 5)
+    plans = rs.plans(lib, n, primes, roots, a)
     try:
         _, ext, _ = kp.run(lib, oracle, primes, roots, 1, 2, n, 3, A | B, fused=1, seed=7, plans=plans, single=True)
         assert not kp.untouched(ext, 1, 2), "an integer-policy run cannot take the fused kernel"
@@ -189,7 +184,7 @@ def test_composition_outside_the_fused_sizes(lib, oracle, logn):
     """N = 2^5, and 2^15 / 2^16 at batch 2 where the single call uses the operand as scratch: the second component is formed from the
     one transform, not from a transform of overwritten data"""
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50, 50, 50, 60, 60])
+    primes, roots = rs.chain(lib, n, [50, 50, 50, 60, 60])
     _, ext, _ = kp.run(lib, oracle, primes, roots, 1, 2, n, 2, A | B, fused=1, seed=logn)
     assert not kp.untouched(ext, 1, 2)
     kp.run(lib, oracle, primes, roots, 3, 2, n, 2, 0, fused=1, seed=logn + 1)
@@ -202,7 +197,7 @@ def test_composition_outside_the_fused_sizes(lib, oracle, logn):
 def test_mixed_chains(lib, oracle, first, count, fused):
     """a 60-bit first prime, 50-bit (and 52-, 30-bit) primes behind it, a 60-bit P"""
     n = 1 << 12
-    primes, roots = rm.chain(lib, n, [60, 50, 50, 52, 50, 30] + [60, 60])
+    primes, roots = rs.chain(lib, n, [60, 50, 50, 52, 50, 30] + [60, 60])
     kp.run(lib, oracle, primes, roots, first, count, n, 3, A | B, fused=fused, seed=first, single=True)
 
 
@@ -212,8 +207,8 @@ def test_mixed_chains(lib, oracle, first, count, fused):
 def test_galois_pair(lib, oracle, k, flags):
     """k across the four-at-a-time loop and its tail; a rotation by 1, by -3, the conjugation and the identity; 57- and 60-bit primes"""
     n = 1 << 11
-    primes, roots = rm.chain(lib, n, [50, 57, 60])
-    plans = _plans(lib, n, primes, roots)
+    primes, roots = rs.chain(lib, n, [50, 57, 60])
+    plans = rs.plans(lib, n, primes, roots)
     try:
         for i, g in enumerate((gm.rotation(n, 1), gm.rotation(n, -3), 2 * n - 1, 1)):
             if k == 32 and i > 1:
@@ -227,20 +222,20 @@ def test_galois_pair(lib, oracle, k, flags):
 @pytest.mark.parametrize("layout", ["limb", "batch_padded"])
 def test_galois_pair_sizes_limb_counts_and_extremes(lib, oracle, layout):
     """N = 2^4; 17 limbs (two launches) at 2^11; 32 products of q - 1 words on top of c = q - 1"""
-    primes, roots = rm.chain(lib, 16, [60, 57, 50])
+    primes, roots = rs.chain(lib, 16, [60, 57, 50])
     kp.run_dot(lib, oracle, primes, roots, 16, 3, 3, gm.rotation(16, -3), T | GA, layout=layout, seed=2, single=True)
     n = 1 << 11
-    primes, roots = rm.chain(lib, n, [60] + [50] * 16)
+    primes, roots = rs.chain(lib, n, [60] + [50] * 16)
     kp.run_dot(lib, oracle, primes, roots, n, 2, 3, gm.rotation(n, 1), T | GA | GB, layout=layout, seed=3, single=True)
-    primes, roots = rm.chain(lib, n, [60, 57])
+    primes, roots = rs.chain(lib, n, [60, 57])
     kp.run_dot(lib, oracle, primes, roots, n, 2, 32, 2 * n - 1, T | GA, layout=layout, seed=4, extreme=True)
 
 
 @pytest.mark.gpu
 def test_argument_errors_write_nothing(lib, oracle):
     n, batch = 1 << 10, 2
-    primes, roots = rm.chain(lib, n, [50] * 18)
-    plans = _plans(lib, n, primes, roots)
+    primes, roots = rs.chain(lib, n, [50] * 18)
+    plans = rs.plans(lib, n, primes, roots)
     words = 18 * batch * n
     imgs = [oracle.fill_uniform(words, primes[0], 5 + i) for i in range(5)]
     dc0, dc1, dext, dk0, dk1 = bufs = [lib.DeviceBuffer(words).upload(i) for i in imgs]
@@ -303,14 +298,9 @@ def test_argument_errors_write_nothing(lib, oracle):
 
 @pytest.mark.gpu
 def test_pair_example_checksums_match_the_model(lib, oracle):
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    exe = os.path.join(ROOT, "build", "rns_key_switch_pair_for_test")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "rns_key_switch_pair.c"),
-                           "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x", "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-    r = subprocess.run(["timeout", "-k", "10", "120", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    out = children.run_example(lib, "rns_key_switch_pair")
     got = {(int(m.group(1)), int(m.group(2))): int(m.group(3), 16)
-           for m in (re.match(r"comp (\d+) limb (\d+) q \d+ checksum ([0-9a-f]+)", line) for line in r.stdout.splitlines()) if m}
+           for m in (re.match(r"comp (\d+) limb (\d+) q \d+ checksum ([0-9a-f]+)", line) for line in out.splitlines()) if m}
     assert len(got) == 16
     n, nq, np_, alpha = 1 << 13, 8, 2, 2
     primes = [lib.find_prime(60, n, 0)] + [lib.find_prime(50, n, k) for k in range(7)] + [lib.find_prime(60, n, k) for k in (1, 2)]
@@ -333,13 +323,8 @@ def test_launch_proof_every_instance_and_the_route_call():
     50-bit + 2 x 60-bit, digit (0, 2), NTT_OPT_PAIR_FUSED 1) is the only launch of modup_mul2_kernel<ArithF64,14,1> -- ONE fused launch
     for the FP64 run --, no single-component product kernel runs anywhere in the child, bconv_kernel only once (the route call's two
     60-bit limbs) and keypair_dot2_kernel only once (their products)"""
-    saved = tgr.MODEL_PY
-    tgr.MODEL_PY = MODEL_PY
-    try:
-        launched = tgr._traced([], 600)
-    finally:
-        tgr.MODEL_PY = saved
-    want = {"modup_mul2_kernel<%s,%d,%d>" % (pol, logn, k) for pol, k, logn in kp.launch_cases()}
+    launched = children.traced(MODEL_PY, [], 600)
+    want = rs.kernel_names("modup_mul2_kernel", rs.fused_launch_cases())
     assert len(want) == 36
     assert not sorted(want - set(launched)), "instances never launched: %s" % sorted(want - set(launched))
     assert launched.count("modup_mul2_kernel<ArithF64,14,1>") == 1, launched

@@ -7,15 +7,14 @@ moddown_fwd_kernel) and the launch of all 38 new instances."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import children
 import kernel_inventory
 import keyswitch_model as km
-import rescale_model as rm
-import test_gpu_rescale as tgr
+import rns_support as rs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODEL_PY = os.path.join(ROOT, "tests", "keyswitch_model.py")
@@ -24,13 +23,13 @@ T, F = km.TRANSFORMED, km.FLOOR
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("np_", [1, 2, 4])
-@pytest.mark.parametrize("pol,k,logn", km.launch_cases(), ids=["%s-k%d-logn%d" % c for c in km.launch_cases()])
+@pytest.mark.parametrize("pol,k,logn", rs.fused_launch_cases(), ids=["%s-k%d-logn%d" % c for c in rs.fused_launch_cases()])
 def test_every_fused_instance(lib, oracle, pol, k, logn, np_):
     """each moddown_fwd_kernel<policy, LOGN, class>: three Q limbs of the class, np 60-bit P limbs, NTT domain, round (even LOGN) /
     floor (odd)"""
     n = 1 << logn
-    b = rm.CLASS_BITS[(pol, k)]
-    primes, roots = rm.chain(lib, n, [b] * 3 + [60] * np_)
+    b = rs.CLASS_BITS[(pol, k)]
+    primes, roots = rs.chain(lib, n, [b] * 3 + [60] * np_)
     flags = T | (F if logn % 2 else 0)
     km.run_down(lib, oracle, primes, roots, np_, n, 3 if logn < 9 else 2, flags, seed=logn + np_)
 
@@ -40,7 +39,7 @@ def test_every_fused_instance(lib, oracle, pol, k, logn, np_):
 @pytest.mark.parametrize("flags", [T, T | F])
 def test_sandwich_at_large_sizes(lib, oracle, logn, flags):
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50, 50, 50, 60, 60])
+    primes, roots = rs.chain(lib, n, [50, 50, 50, 60, 60])
     km.run_down(lib, oracle, primes, roots, 2, n, 2, flags, seed=logn)
 
 
@@ -52,7 +51,7 @@ def test_integer_policy_limbs(lib, oracle, arith, flags):
     coefficient kernel; ModUp beside it"""
     n = 1 << 12
     a = {"auto": lib.ARITH_AUTO, "u64": lib.ARITH_U64, "r4": lib.ARITH_U64_R4}[arith]
-    primes, roots = rm.chain(lib, n, [58] * 5 if arith != "auto" else [60] * 5)
+    primes, roots = rs.chain(lib, n, [58] * 5 if arith != "auto" else [60] * 5)
     plans = [lib.Plan(n, q, w, arith=a) for q, w in zip(primes, roots)]
     try:
         km.run_down(lib, oracle, primes, roots, 2, n, 3, flags, plans=plans, seed=7)
@@ -68,7 +67,7 @@ def test_integer_policy_limbs(lib, oracle, arith, flags):
 @pytest.mark.parametrize("flags", [0, T])
 def test_mod_up(lib, oracle, nlimbs, first, count, flags):
     n = 1 << 10
-    primes, roots = rm.chain(lib, n, [60] + [50] * (nlimbs - 3) + [60, 60])
+    primes, roots = rs.chain(lib, n, [60] + [50] * (nlimbs - 3) + [60, 60])
     km.run_up(lib, oracle, primes, roots, first, count, n, 2, flags, seed=nlimbs + first)
 
 
@@ -77,7 +76,7 @@ def test_mod_up(lib, oracle, nlimbs, first, count, flags):
 @pytest.mark.parametrize("flags", [0, T])
 def test_mod_down_q_counts_across_the_run_boundary(lib, oracle, nq, flags):
     n = 1 << 10
-    primes, roots = rm.chain(lib, n, [50] * nq + [60, 60, 60])
+    primes, roots = rs.chain(lib, n, [50] * nq + [60, 60, 60])
     km.run_down(lib, oracle, primes, roots, 3, n, 2, flags, seed=nq)
 
 
@@ -88,7 +87,7 @@ def test_mod_down_q_counts_across_the_run_boundary(lib, oracle, nq, flags):
 @pytest.mark.parametrize("flags", [0, F, T, T | F])
 def test_mixed_chains(lib, oracle, qbits, pbits, flags):
     n = 1 << 12
-    primes, roots = rm.chain(lib, n, qbits + pbits)
+    primes, roots = rs.chain(lib, n, qbits + pbits)
     km.run_down(lib, oracle, primes, roots, len(pbits), n, 3, flags, seed=len(qbits))
     if len(pbits) <= 3:
         km.run_up(lib, oracle, primes, roots, 0, 2, n, 3, flags & T, seed=len(qbits))
@@ -99,7 +98,7 @@ def test_mixed_chains(lib, oracle, qbits, pbits, flags):
 @pytest.mark.parametrize("flags", [0, T])
 def test_batches(lib, oracle, batch, flags):
     n = 1 << 8
-    primes, roots = rm.chain(lib, n, [50, 50, 50, 50, 60, 60])
+    primes, roots = rs.chain(lib, n, [50, 50, 50, 50, 60, 60])
     km.run_down(lib, oracle, primes, roots, 2, n, batch, flags, seed=batch)
     km.run_up(lib, oracle, primes, roots, 2, 2, n, batch, flags, seed=batch)
 
@@ -109,7 +108,7 @@ def test_batches(lib, oracle, batch, flags):
 @pytest.mark.parametrize("flags", [0, T, T | F])
 def test_layouts(lib, oracle, layout, flags):
     n = 1 << 11
-    primes, roots = rm.chain(lib, n, [50, 50, 50, 52, 60, 60])
+    primes, roots = rs.chain(lib, n, [50, 50, 50, 52, 60, 60])
     km.run_down(lib, oracle, primes, roots, 2, n, 3, flags, layout=layout, seed=11)
     km.run_up(lib, oracle, primes, roots, 1, 2, n, 3, flags & T, layout=layout, seed=12)
 
@@ -121,7 +120,7 @@ def test_layouts(lib, oracle, layout, flags):
 def test_mod_down_with_one_p_prime_equals_the_rescale(lib, oracle, logn, bits, flags):
     """ntt_rns_mod_down_batch(nq = L, np = 1) and ntt_rns_rescale_batch(L + 1) on the same operand: the same words"""
     n, batch = 1 << logn, 2
-    primes, roots = rm.chain(lib, n, bits)
+    primes, roots = rs.chain(lib, n, bits)
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     coef = [oracle.fill_uniform(batch * n, q, 40 + l) for l, q in enumerate(primes)]
     limbs = [oracle.ctx(n, q, w).fwd(c) for q, w, c in zip(primes, roots, coef)] if flags & T else coef
@@ -141,7 +140,7 @@ def test_mod_down_with_one_p_prime_equals_the_rescale(lib, oracle, logn, bits, f
 @pytest.mark.parametrize("logn,nq,np_", [(14, 16, 2), (9, 5, 1), (12, 20, 3), (13, 8, 4)])
 def test_fused_equals_sandwich_bit_for_bit(lib, oracle, logn, nq, np_):
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50] * nq + [60] * np_)
+    primes, roots = rs.chain(lib, n, [50] * nq + [60] * np_)
     fused = km.run_down(lib, oracle, primes, roots, np_, n, 2, T, fused=1, seed=3)
     sandwich = km.run_down(lib, oracle, primes, roots, np_, n, 2, T, fused=0, seed=3)
     for a, b in zip(fused, sandwich):
@@ -151,11 +150,11 @@ def test_fused_equals_sandwich_bit_for_bit(lib, oracle, logn, nq, np_):
 @pytest.mark.gpu
 def test_argument_errors_write_nothing(lib, oracle):
     n, batch = 1 << 10, 2
-    primes, roots = rm.chain(lib, n, [50] * 18)
+    primes, roots = rs.chain(lib, n, [50] * 18)
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     other = lib.Plan(2 * n, lib.find_prime(50, 2 * n), lib.min_root(lib.find_prime(50, 2 * n), 2 * n))
     same = lib.Plan(n, primes[0], roots[0])
-    fwd_only = tgr._forward_only_plan(lib, n, primes[3], roots[3])
+    fwd_only = rs.forward_only_plan(lib, n, primes[3], roots[3])
     words = 18 * batch * n
     img = oracle.fill_uniform(words, primes[0], 5)
     buf = lib.DeviceBuffer(words).upload(img)
@@ -194,7 +193,7 @@ def test_argument_errors_write_nothing(lib, oracle):
             lib.rns_mod_up(ps, buf.ptr, first, count, batch, flags, layout=lay)
         assert np.array_equal(buf.download(), img), what
     # a Q limb without the inverse table: refused where the sandwich serves it, served by the fused route
-    fwd_only_q = tgr._forward_only_plan(lib, n, primes[1], roots[1])
+    fwd_only_q = rs.forward_only_plan(lib, n, primes[1], roots[1])
     ps = [plans[0], fwd_only_q, plans[2], plans[3]]
     plans[0].set_option(lib.OPT_RESCALE_FUSED, 0)
     with pytest.raises(lib.NttError):
@@ -209,14 +208,9 @@ def test_argument_errors_write_nothing(lib, oracle):
 
 @pytest.mark.gpu
 def test_example_checksums_match_the_model(lib, oracle):
-    exe = os.path.join(ROOT, "build", "rns_key_switch")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "rns_key_switch.c"),
-                           "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x", "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-    r = subprocess.run(["timeout", "-k", "10", "120", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    out = children.run_example(lib, "rns_key_switch")
     got = {(int(m.group(1)), int(m.group(2))): int(m.group(3), 16)
-           for m in re.finditer(r"poly (\d+) limb (\d+) q \d+ checksum ([0-9a-f]+)", r.stdout)}
+           for m in re.finditer(r"poly (\d+) limb (\d+) q \d+ checksum ([0-9a-f]+)", out)}
     n, nq, np_, alpha = 1 << 13, 8, 2, 2
     primes = [lib.find_prime(60, n, 0)] + [lib.find_prime(50, n, k) for k in range(7)] + [lib.find_prime(60, n, k) for k in (1, 2)]
     roots = [lib.min_root(q, n) for q in primes]
@@ -236,21 +230,11 @@ def test_example_checksums_match_the_model(lib, oracle):
             assert got[(p, l)] == oracle.checksum(out[l]), (p, l)
 
 
-def _traced(args, seconds):
-    """the kernels `python3 tests/keyswitch_model.py ARGS` launched in a fresh child process under a kernel trace"""
-    saved = tgr.MODEL_PY
-    tgr.MODEL_PY = MODEL_PY
-    try:
-        return tgr._traced(args, seconds)
-    finally:
-        tgr.MODEL_PY = saved
-
-
 @pytest.mark.gpu
 def test_route_proof_p_inverses_and_one_fused_launch():
     """2^14, 16 Q limbs of 50-bit primes and 2 P limbs of 60-bit primes, NTT domain: the call launches the inverse transforms of the
     P limbs and exactly one moddown_fwd_kernel, nothing else"""
-    launched = [k for k in _traced(["--route"], 300) if k.split("<")[0] not in rm.SETUP_KERNELS]
+    launched = [k for k in children.traced(MODEL_PY, ["--route"], 300) if k.split("<")[0] not in rs.SETUP_KERNELS]
     fused = [k for k in launched if k.startswith("moddown_fwd_kernel")]
     assert fused == ["moddown_fwd_kernel<ArithF64,14,1>"], launched
     others = [k for k in launched if not k.startswith("moddown_fwd_kernel")]
@@ -260,7 +244,7 @@ def test_route_proof_p_inverses_and_one_fused_launch():
 
 @pytest.mark.gpu
 def test_launch_proof_every_new_instance():
-    launched = set(_traced([], 600))
-    want = {"moddown_fwd_kernel<%s,%d,%d>" % (pol, logn, k) for pol, k, logn in km.launch_cases()} | {"moddown_coef_kernel", "bconv_kernel"}
+    launched = set(children.traced(MODEL_PY, [], 600))
+    want = rs.kernel_names("moddown_fwd_kernel", rs.fused_launch_cases()) | {"moddown_coef_kernel", "bconv_kernel"}
     assert len(want) == 38
     assert not sorted(want - launched), "instances never launched: %s" % sorted(want - launched)

@@ -4,20 +4,15 @@ accumulation; every lift_fwd_kernel instance; the persistent loop's wrap; mixed 
 integer policies; layouts with canaries; a broadcast lifted plaintext fed to rns_lincomb; corner words; fused == composition;
 argument errors that write nothing; round trips through rns_to_plain / rns_to_double; the plain-C example; and two kernel traces: the
 route at 2^14 over 17 FP64 limbs (two lift_fwd_kernel launches, nothing else) and the launch of all 37 new kernels."""
-import csv
-import glob
 import os
-import subprocess
-import sys
-import tempfile
 from math import prod
 
 import numpy as np
 import pytest
 
-import kernel_inventory
+import children
 import lift_model as lm
-import rescale_model as rm
+import rns_support as rs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODEL_PY = os.path.join(ROOT, "tests", "lift_model.py")
@@ -39,7 +34,7 @@ def _arg(kind, t=65537, scale=2.0 ** 40):
 @pytest.mark.parametrize("acc", [0, A], ids=["store", "accumulate"])
 def test_coefficient_shapes(lib, oracle, logn, batch, mode, acc):
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50, 60, 30])
+    primes, roots = rs.chain(lib, n, [50, 60, 30])
     lm.check_lift(lib, oracle, primes, roots, n, batch, mode[0], mode[1] | acc, seed=logn + batch, **_arg(mode[0]))
 
 
@@ -49,7 +44,7 @@ def test_coefficient_shapes(lib, oracle, logn, batch, mode, acc):
 @pytest.mark.parametrize("acc", [0, A], ids=["store", "accumulate"])
 def test_coefficient_limb_counts_across_the_chunk(lib, oracle, nlimbs, mode, acc):
     n = 1 << 8
-    primes, roots = rm.chain(lib, n, [50] * nlimbs)
+    primes, roots = rs.chain(lib, n, [50] * nlimbs)
     lm.check_lift(lib, oracle, primes, roots, n, 2, mode[0], mode[1] | acc, seed=nlimbs, **_arg(mode[0]))
 
 
@@ -60,7 +55,7 @@ def test_coefficient_plaintext_moduli_with_their_corner_words(lib, oracle, t, fl
     """every t with m in {0, 1, ceil(t/2) - 1, ceil(t/2), t - 1} and, scaled, the constructed ties and boundaries (the generator's
     own test is in test_lift_cpu.py)"""
     n = 1 << 7
-    primes, roots = rm.chain(lib, n, [50, 60, 30, 52])
+    primes, roots = rs.chain(lib, n, [50, 60, 30, 52])
     corners = lm.plain_corners(t, primes if flags & S else None)
     assert {0, 1 % t, t - 1, t - t // 2, (t - t // 2 - 1) % t} <= set(corners)
     lm.check_lift(lib, oracle, primes, roots, n, 2, "plain", flags, t=t, seed=t % 1000)
@@ -72,7 +67,7 @@ def test_coefficient_plaintext_moduli_with_their_corner_words(lib, oracle, t, fl
 def test_double_corner_words(lib, oracle, scale, flags):
     """+-0.0, +-0.5, 1.5, 2.5, 2^53 + 2, just below 2^127 and 2^127, NaN, +-inf, the smallest subnormal, products that round"""
     n = 1 << 6
-    primes, roots = rm.chain(lib, n, [50, 60, 30])
+    primes, roots = rs.chain(lib, n, [50, 60, 30])
     words = lm.with_corners(lm.DOUBLE, 2 * n, 0, 9, flags, primes)
     assert lm.double_corners().size <= words.size
     lm.check_lift(lib, oracle, primes, roots, n, 2, lm.DOUBLE, flags, scale=scale, plain=words)
@@ -82,14 +77,14 @@ def test_double_corner_words(lib, oracle, scale, flags):
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_coefficient_max_grid(lib, oracle, mode):
     n = 1 << 10
-    primes, roots = rm.chain(lib, n, [50, 50, 50])
+    primes, roots = rs.chain(lib, n, [50, 50, 50])
     lm.check_lift(lib, oracle, primes, roots, n, 5, mode[0], mode[1], max_grid=3, seed=5, **_arg(mode[0]))
 
 
 # ---------------------------------------------------------------- the fused route
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("pol,k,logn", lm.launch_cases(), ids=["%s-k%d-logn%d" % c for c in lm.launch_cases()])
+@pytest.mark.parametrize("pol,k,logn", rs.fused_launch_cases(), ids=["%s-k%d-logn%d" % c for c in rs.fused_launch_cases()])
 def test_every_fused_instance(lib, oracle, pol, k, logn):
     """each lift_fwd_kernel<policy, LOGN, class>: three limbs of the class, batch 3 below 2^9 (a partly dead group of sub-blocks), mode
     and accumulation rotating with LOGN"""
@@ -104,7 +99,7 @@ def test_persistent_loop_wrap(lib, oracle, logn, batch, flags):
     """the smallest grid (8 workgroups per limb: the x extent is a multiple of 8): batch 5 leaves workgroups without a block, batch 13
     wraps five of them, the last block served by a wrapped iteration"""
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50, 50, 50])
+    primes, roots = rs.chain(lib, n, [50, 50, 50])
     lm.check_lift(lib, oracle, primes, roots, n, batch, "plain", flags, max_grid=3, fused=1, seed=logn)
 
 
@@ -115,7 +110,7 @@ def test_persistent_loop_wrap(lib, oracle, logn, batch, flags):
 def test_mixed_chains(lib, oracle, bits, mode, acc):
     """fused and composed runs in one call"""
     n = 1 << 12
-    primes, roots = rm.chain(lib, n, bits)
+    primes, roots = rs.chain(lib, n, bits)
     lm.check_lift(lib, oracle, primes, roots, n, 3, mode[0], T | mode[1] | acc, seed=len(bits), **_arg(mode[0]))
 
 
@@ -124,7 +119,7 @@ def test_mixed_chains(lib, oracle, bits, mode, acc):
 @pytest.mark.parametrize("flags", [T, T | S | A])
 def test_composition_at_large_sizes(lib, oracle, logn, flags):
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50, 50, 50, 50])
+    primes, roots = rs.chain(lib, n, [50, 50, 50, 50])
     lm.check_lift(lib, oracle, primes, roots, n, 2, "plain", flags, seed=logn)
 
 
@@ -135,7 +130,7 @@ def test_composition_at_large_sizes(lib, oracle, logn, flags):
 def test_integer_policy_limbs(lib, oracle, arith, mode, flags):
     n = 1 << 12
     a = {"u64": lib.ARITH_U64, "r4": lib.ARITH_U64_R4}[arith]
-    primes, roots = rm.chain(lib, n, [58, 58, 58])
+    primes, roots = rs.chain(lib, n, [58, 58, 58])
     lm.check_lift(lib, oracle, primes, roots, n, 3, mode[0], flags | mode[1], arith=a, seed=7, **_arg(mode[0]))
 
 
@@ -144,7 +139,7 @@ def test_integer_policy_limbs(lib, oracle, arith, mode, flags):
 @pytest.mark.parametrize("flags", [0, A, T, T | S | A])
 def test_layouts_and_plaintext_stride(lib, oracle, layout, flags):
     n = 1 << 11
-    primes, roots = rm.chain(lib, n, [50, 50, 50, 50, 52])
+    primes, roots = rs.chain(lib, n, [50, 50, 50, 50, 52])
     lm.check_lift(lib, oracle, primes, roots, n, 3, "plain", flags, layout=layout, m_stride=n + 24, seed=11)
     lm.check_lift(lib, oracle, primes, roots, n, 3, lm.DOUBLE, flags & ~S, layout=layout, m_stride=n + 24, seed=12, scale=2.0 ** 45)
 
@@ -153,7 +148,7 @@ def test_layouts_and_plaintext_stride(lib, oracle, layout, flags):
 def test_broadcast_lifted_plaintext_multiplies_through_lincomb(lib, oracle):
     """ct (.) pt: pt^ = from_plain(batch = 1, TRANSFORMED) is the [limb][N] multiplier LINCOMB_M_BROADCAST reads"""
     n, batch, t = 1 << 10, 3, 65537
-    primes, roots = rm.chain(lib, n, [50, 50, 52])
+    primes, roots = rs.chain(lib, n, [50, 50, 52])
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     m = lm.with_corners("plain", n, t, 3, 0, primes)
     ct = [oracle.fill_uniform(batch * n, q, 40 + l) for l, q in enumerate(primes)]
@@ -178,7 +173,7 @@ def test_broadcast_lifted_plaintext_multiplies_through_lincomb(lib, oracle):
 @pytest.mark.parametrize("acc", [0, A], ids=["store", "accumulate"])
 def test_fused_equals_composition_bit_for_bit(lib, oracle, logn, nlimbs, mode, acc):
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50] * nlimbs)
+    primes, roots = rs.chain(lib, n, [50] * nlimbs)
     kw = dict(seed=3, **_arg(mode[0]))
     fused = lm.check_lift(lib, oracle, primes, roots, n, 2, mode[0], T | mode[1] | acc, fused=1, **kw)
     composed = lm.check_lift(lib, oracle, primes, roots, n, 2, mode[0], T | mode[1] | acc, fused=0, **kw)
@@ -203,7 +198,7 @@ def test_option_defaults_and_round_trips(lib):
 @pytest.mark.gpu
 def test_argument_errors_write_nothing(lib, oracle):
     n, batch, t = 1 << 10, 2, 65537
-    primes, roots = rm.chain(lib, n, [50, 50, 50])
+    primes, roots = rs.chain(lib, n, [50, 50, 50])
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     other = lib.Plan(2 * n, lib.find_prime(50, 2 * n), lib.min_root(lib.find_prime(50, 2 * n), 2 * n))
     words = 3 * batch * n
@@ -245,7 +240,7 @@ def test_round_trip_through_to_plain(lib, oracle, t, flags_in, flags_out):
     """rns_to_plain(rns_from_plain(m)) == m.  Q >= 2^20 t: centred, |m_c| <= t / 2 <= 2^-21 Q is far from Q / 2; scaled, t x mod Q for
     x = round(Q m / t) is within t / 2 of 0 or Q -- no word lies in to_plain's band, the definitions alone give the identity"""
     n, batch = 1 << 8, 2
-    primes, roots = rm.chain(lib, n, [50, 50])
+    primes, roots = rs.chain(lib, n, [50, 50])
     assert prod(primes) >= (t << 20) and flags_out == lib.PLAIN_SCALE * (flags_in == S)
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     m = lm.with_corners("plain", batch * n, t, 21, flags_in, primes)
@@ -263,7 +258,7 @@ def test_round_trip_through_to_plain(lib, oracle, t, flags_in, flags_out):
 def test_round_trip_through_to_double(lib, oracle):
     """rns_to_double(rns_from_double(y, Delta), 1 / Delta) == rint(y Delta) / Delta for |y Delta| < 2^53 (Delta a power of two)"""
     n, batch, delta = 1 << 8, 2, 2.0 ** 30
-    primes, roots = rm.chain(lib, n, [60, 60])
+    primes, roots = rs.chain(lib, n, [60, 60])
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     rng = np.random.default_rng(8)
     y = rng.standard_normal(batch * n) * np.exp2(rng.integers(-30, 22, size=batch * n))
@@ -284,55 +279,23 @@ def test_round_trip_through_to_double(lib, oracle):
 
 @pytest.mark.gpu
 def test_example_checksums_match_the_model(lib, oracle):
-    exe = os.path.join(ROOT, "build", "rns_encrypt")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "rns_encrypt.c"),
-                           "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x", "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-    r = subprocess.run(["timeout", "-k", "10", "120", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.splitlines() == lm.example_model(lib, oracle)
+    out = children.run_example(lib, "rns_encrypt")
+    assert out.splitlines() == lm.example_model(lib, oracle)
 
 
 # ---------------------------------------------------------------- kernel traces
-
-def _rocprofv3():
-    import shutil
-    exe = "/opt/rocm/bin/rocprofv3" if os.path.exists("/opt/rocm/bin/rocprofv3") else shutil.which("rocprofv3")
-    if not exe:
-        pytest.fail("rocprofv3 is not on this machine: the launch proofs need its kernel trace")
-    return exe
-
-
-def _traced(args, seconds):
-    """run `python3 tests/lift_model.py ARGS` in a fresh child process under a kernel trace: the normalised kernel names it launched,
-    one entry per dispatch"""
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["timeout", "-k", "10", str(seconds), _rocprofv3(), "--kernel-trace", "--output-format", "csv", "-d", d, "--",
-               sys.executable, MODEL_PY] + list(args)
-        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True)
-        assert r.returncode == 0, "traced run failed (exit %d):\n%s\n%s" % (r.returncode, r.stdout[-4000:], r.stderr[-4000:])
-        names = []
-        files = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
-        assert files, "the kernel trace wrote no CSV:\n" + r.stderr[-2000:]
-        for f in files:
-            with open(f, newline="") as fh:
-                names += [row["Kernel_Name"] for row in csv.DictReader(fh)]
-    mangled = sorted({n for n in names if n.startswith("_Z")})
-    dem = dict(zip(mangled, kernel_inventory.demangle(mangled)))
-    return [kernel_inventory.normalise(dem.get(n, n)) for n in names]
-
 
 @pytest.mark.gpu
 def test_route_proof_two_fused_launches():
     """2^14, 17 FP64 limbs, NTT domain, the fused kernel selected (the measured default composes a storing centred lift at 2^14): the
     call launches exactly two lift_fwd_kernels, one per run of at most 16 limbs, and nothing else"""
-    launched = [k for k in _traced(["--route"], 300) if k.split("<")[0] not in rm.SETUP_KERNELS]
+    launched = [k for k in children.traced(MODEL_PY, ["--route"], 300) if k.split("<")[0] not in rs.SETUP_KERNELS]
     assert launched == ["lift_fwd_kernel<ArithF64,14,1>"] * 2, launched
 
 
 @pytest.mark.gpu
 def test_launch_proof_every_new_kernel():
-    launched = set(_traced([], 600))
-    want = {"lift_fwd_kernel<%s,%d,%d>" % (pol, logn, k) for pol, k, logn in lm.launch_cases()} | {"lift_coef_kernel"}
+    launched = set(children.traced(MODEL_PY, [], 600))
+    want = rs.kernel_names("lift_fwd_kernel", rs.fused_launch_cases()) | {"lift_coef_kernel"}
     assert len(want) == 37
     assert not sorted(want - launched), "kernels never launched: %s" % sorted(want - launched)

@@ -2,16 +2,14 @@
 model of tests/lincomb_model.py (the definition in Python integers; through the oracle's modular product for the large shapes),
 exactly; the operands sit among canaries, which stay untouched, as the inputs do."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import children
 import galois_model as gm
 import lincomb_model as lm
-import rescale_model as rm
-import test_gpu_rescale as tgr
+import rns_support as rs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODEL_PY = os.path.join(ROOT, "tests", "lincomb_model.py")
@@ -34,7 +32,7 @@ def test_shapes(lib, oracle, logn, batch, nlimbs):
     """k = 3: a scalar term, a term with a polynomial multiplier read through sigma_5, a scalar term through the conjugation; a
     different scalar per term and limb and a different bias per limb (17 limbs: two launches -- a wrong limb index shows)"""
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [60] + [50] * (nlimbs - 1))
+    primes, roots = rs.chain(lib, n, [60] + [50] * (nlimbs - 1))
     lm.run_case(lib, oracle, primes, roots, n, batch, [1, 5 % (2 * n), 2 * n - 1], poly=(1,), seed=logn + batch)
 
 
@@ -42,7 +40,7 @@ def test_shapes(lib, oracle, logn, batch, nlimbs):
 def test_grid_wrap(lib, oracle):
     """NTT_OPT_MAX_GRID = 3 on plans[0] at 2^10, 5 polynomials: every thread walks several iterations and polynomials"""
     n = 1 << 10
-    primes, roots = rm.chain(lib, n, [50, 50])
+    primes, roots = rs.chain(lib, n, [50, 50])
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     plans[0].set_option(lib.OPT_MAX_GRID, 3)
     lm.run_case(lib, oracle, primes, roots, n, 5, _gs(n, 3), poly=(0, 2), flags=A, plans=plans, seed=4)
@@ -58,7 +56,7 @@ def test_grid_wrap(lib, oracle):
 def test_term_counts(lib, oracle, k, mix):
     """the load groups of four and their tail; scalar and polynomial terms in one call (d_m NULL, NULL entries inside d_m)"""
     n = 64
-    primes, roots = rm.chain(lib, n, [60, 30])
+    primes, roots = rs.chain(lib, n, [60, 30])
     poly = {"scalars_null_m": (), "scalars": (), "every_third_poly": tuple(range(0, k, 3)), "all_poly": tuple(range(k))}[mix]
     lm.run_case(lib, oracle, primes, roots, n, 3, _gs(n, k), poly=poly, null_m=mix == "scalars_null_m", seed=k)
 
@@ -68,7 +66,7 @@ def test_term_counts(lib, oracle, k, mix):
 def test_a_galois_element_per_term(lib, oracle, logn):
     """k = 5, g_i = 1, 5, 25, 2N - 1, 5^-1 mod 2N in one call (N = 2 and 4: what they reduce to), scalars and multipliers mixed"""
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [60, 50, 30])
+    primes, roots = rs.chain(lib, n, [60, 50, 30])
     lm.run_case(lib, oracle, primes, roots, n, 3, _gs(n), poly=(1, 4), flags=A, seed=logn)
     lm.run_case(lib, oracle, primes, roots, n, 3, _gs(n)[::-1], poly=(0,), flags=B, seed=logn + 1)
 
@@ -78,7 +76,7 @@ def test_a_galois_element_per_term(lib, oracle, logn):
 def test_one_unit_term_is_the_automorphism_word_for_word(lib, oracle, logn):
     """k = 1, scalar 1 (h_s NULL), no bias: ntt_rns_galois_batch's output"""
     n, batch = 1 << logn, 3
-    primes, roots = rm.chain(lib, n, [60, 50, 52])
+    primes, roots = rs.chain(lib, n, [60, 50, 52])
     for g in sorted(set(_gs(n))):
         got = lm.run_case(lib, oracle, primes, roots, n, batch, [g], scalars=None, bias=None, seed=3)
         a = [oracle.fill_uniform(batch * n, q, 3 * 1000 + l) for l, q in enumerate(primes)]
@@ -95,7 +93,7 @@ def test_one_unit_term_is_the_automorphism_word_for_word(lib, oracle, logn):
 def test_equal_g_and_multipliers_is_the_rotation_key_product_word_for_word(lib, oracle, flags):
     """every g_i equal, every term with a polynomial multiplier: ntt_rns_galois_dot_batch's output on the same operands"""
     n, batch, k = 1 << 8, 3, 5
-    primes, roots = rm.chain(lib, n, [60, 50])
+    primes, roots = rs.chain(lib, n, [60, 50])
     g = pow(5, 3, 2 * n)
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     a = [[oracle.fill_uniform(batch * n, q, 50 * i + l) for l, q in enumerate(primes)] for i in range(k)]
@@ -126,7 +124,7 @@ CHAIN = [60, 50, 30, 52]
 @pytest.mark.parametrize("case", ["zero", "top", "k16_top_accumulate", "lazy_top_k8", "lazy_random_k8", "k9_lazy_refused"])
 def test_mixed_chain_and_extremes(lib, oracle, case):
     n = 64
-    primes, roots = rm.chain(lib, n, CHAIN)
+    primes, roots = rs.chain(lib, n, CHAIN)
     top = [[q - 1 for q in primes]] * 16
     if case == "zero":
         lm.run_case(lib, oracle, primes, roots, n, 3, _gs(n, 4), poly=(1,), flags=A, fill=lambda q: 0, scalars=[[0] * 4] * 4, bias=[0] * 4)
@@ -151,7 +149,7 @@ def test_mixed_chain_and_extremes(lib, oracle, case):
 @pytest.mark.parametrize("flags", [0, A, B, A | B])
 def test_flags(lib, oracle, flags):
     n = 1 << 7
-    primes, roots = rm.chain(lib, n, CHAIN)
+    primes, roots = rs.chain(lib, n, CHAIN)
     lm.run_case(lib, oracle, primes, roots, n, 5, _gs(n, 4), poly=(0, 3), flags=flags, seed=flags)
 
 
@@ -160,7 +158,7 @@ def test_flags(lib, oracle, flags):
 def test_bias_with_one_term(lib, oracle, flags):
     """k = 1, h_s NULL: c (+)= a + bias_l"""
     n = 1 << 7
-    primes, roots = rm.chain(lib, n, CHAIN)
+    primes, roots = rs.chain(lib, n, CHAIN)
     lm.run_case(lib, oracle, primes, roots, n, 2, [1], scalars=None, flags=flags, seed=6)
 
 
@@ -168,7 +166,7 @@ def test_bias_with_one_term(lib, oracle, flags):
 def test_add_sub_neg(lib, oracle):
     """the convenience calls, in place and out of place"""
     n, batch = 1 << 6, 3
-    primes, roots = rm.chain(lib, n, CHAIN)
+    primes, roots = rs.chain(lib, n, CHAIN)
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     a = [oracle.fill_uniform(batch * n, q, l) for l, q in enumerate(primes)]
     b = [oracle.fill_uniform(batch * n, q, 10 + l) for l, q in enumerate(primes)]
@@ -199,7 +197,7 @@ def test_add_sub_neg(lib, oracle):
 def test_in_place_equals_out_of_place(lib, oracle, alias):
     """c == a_0 (g_0 = 1) and c == m_1: the result of the out-of-place call on the same operands"""
     n = 1 << 10
-    primes, roots = rm.chain(lib, n, CHAIN)
+    primes, roots = rs.chain(lib, n, CHAIN)
     gs = [1, 5, 2 * n - 1]
     out = lm.run_case(lib, oracle, primes, roots, n, 3, gs, poly=(1, 2), seed=12)
     inp = lm.run_case(lib, oracle, primes, roots, n, 3, gs, poly=(1, 2), seed=12, alias=alias)
@@ -213,7 +211,7 @@ def test_in_place_equals_out_of_place(lib, oracle, alias):
 def test_layouts(lib, oracle, layout, flags):
     """[limb][batch][N], [batch][limb][N], padded strides, an odd limb stride; 17 limbs: the second launch's offsets too"""
     n, batch, nl = 1 << 6, 3, 17
-    primes, roots = rm.chain(lib, n, [60] + [50] * (nl - 1))
+    primes, roots = rs.chain(lib, n, [60] + [50] * (nl - 1))
     if layout == "odd_limb_stride":
         ls, ps = n + 1, nl * (n + 1) + 3
         layout = (ls, ps, (batch - 1) * ps + (nl - 1) * ls + n + 5)
@@ -225,7 +223,7 @@ def test_layouts(lib, oracle, layout, flags):
 @pytest.mark.gpu
 def test_argument_errors_write_nothing(lib, oracle):
     n, batch = 1 << 8, 2
-    primes, roots = rm.chain(lib, n, [50] * 3)
+    primes, roots = rs.chain(lib, n, [50] * 3)
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     q2 = lib.find_prime(50, 2 * n)
     other = lib.Plan(2 * n, q2, lib.min_root(q2, 2 * n))
@@ -279,18 +277,16 @@ def test_captured_in_a_hip_graph():
     a HIP graph and replayed twice: the model applied twice (a process of its own: torch has to be imported before the library).  The
     host arrays are released before the replay: the launch carries its own copy."""
     code = """
-import sys
-sys.path.insert(0, %r); sys.path.insert(0, %r)
 import torch
 torch.cuda.set_device(0)
 import numpy as np
 import ontt
 from oracle_binding import Oracle
 import lincomb_model as lm
-import rescale_model as rm
+import rns_support as rs
 lib, orc = ontt.load(), Oracle()
 n, batch, k = 1 << 10, 3, 3
-primes, roots = rm.chain(lib, n, [60] + [50] * 16)
+primes, roots = rs.chain(lib, n, [60] + [50] * 16)
 nl = len(primes)
 plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
 gs = [1, 5, 2 * n - 1]
@@ -315,29 +311,18 @@ for rep in (1, 2):
     for l in range(nl):
         assert np.array_equal(got[l], want[l]), (rep, l)
 print("graph ok")
-""" % (ROOT, os.path.join(ROOT, "tests"))
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=ROOT)
-    assert out.returncode == 0 and "graph ok" in out.stdout, (out.stdout[-1000:], out.stderr[-3000:])
-
-
-def _traced(args, seconds):
-    """the kernels `python3 tests/lincomb_model.py ARGS` launched in a fresh child process under a kernel trace"""
-    saved = tgr.MODEL_PY
-    tgr.MODEL_PY = MODEL_PY
-    try:
-        return tgr._traced(args, seconds)
-    finally:
-        tgr.MODEL_PY = saved
+"""
+    children.python_child(code, 300)
 
 
 @pytest.mark.gpu
 def test_route_proof_one_launch_per_16_limbs():
     """one traced process: the call over 16 limbs launches lincomb_kernel once, the call over 17 limbs twice, and neither anything
     else (the calls are told apart by the table kernels of the plans each creates first)"""
-    launched = _traced(["--route"], 300)
+    launched = children.traced(MODEL_PY, ["--route"], 300)
     calls, setup = [], True
     for k in launched:
-        if k.split("<")[0] in rm.SETUP_KERNELS:
+        if k.split("<")[0] in rs.SETUP_KERNELS:
             setup = True
             continue
         if setup:
@@ -349,11 +334,6 @@ def test_route_proof_one_launch_per_16_limbs():
 
 @pytest.mark.gpu
 def test_example_prints_ok_for_every_limb(lib):
-    exe = os.path.join(ROOT, "build", "rns_lincomb")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "rns_lincomb.c"),
-                           "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x", "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-    r = subprocess.run(["timeout", "-k", "10", "120", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    lines = [line for line in r.stdout.splitlines() if line.startswith("limb ")]
-    assert len(lines) == 8 and all(line.endswith(" OK") for line in lines), r.stdout
+    out = children.run_example(lib, "rns_lincomb")
+    lines = [line for line in out.splitlines() if line.startswith("limb ")]
+    assert len(lines) == 8 and all(line.endswith(" OK") for line in lines), out

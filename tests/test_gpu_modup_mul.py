@@ -7,24 +7,19 @@ and the model, and one kernel trace: all 36 instances launched, the route call's
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import children
 import kernel_inventory
 import keyswitch_model as km
 import modup_mul_model as mm
-import rescale_model as rm
-import test_gpu_rescale as tgr
+import rns_support as rs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODEL_PY = os.path.join(ROOT, "tests", "modup_mul_model.py")
 L, B, A = mm.LAZY_IN, mm.BROADCAST, mm.ACCUMULATE
-
-
-def _plans(lib, n, primes, roots, arith=None):
-    return [lib.Plan(n, q, w) if arith is None else lib.Plan(n, q, w, arith=arith) for q, w in zip(primes, roots)]
 
 
 def _destroy(plans):
@@ -33,14 +28,14 @@ def _destroy(plans):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("pol,k,logn", mm.launch_cases(), ids=["%s-k%d-logn%d" % c for c in mm.launch_cases()])
+@pytest.mark.parametrize("pol,k,logn", rs.fused_launch_cases(), ids=["%s-k%d-logn%d" % c for c in rs.fused_launch_cases()])
 def test_every_instance(lib, oracle, pol, k, logn):
     """each modup_mul_kernel<policy, LOGN, class>: three limbs of the class and two 60-bit limbs; digits of one and of two FP64
     limbs, and the 60-bit digit feeding the FP64 run (its own run on the composition); accumulate and broadcast each way"""
     n = 1 << logn
-    b = rm.CLASS_BITS[(pol, k)]
-    primes, roots = rm.chain(lib, n, [b, b, b, 60, 60])
-    plans = _plans(lib, n, primes, roots)
+    b = rs.CLASS_BITS[(pol, k)]
+    primes, roots = rs.chain(lib, n, [b, b, b, 60, 60])
+    plans = rs.plans(lib, n, primes, roots)
     try:
         for (first, count), flags in (((0, 1), 0), ((1, 2), A | B), ((3, 2), B)):
             _, ext, _ = mm.run(lib, oracle, primes, roots, first, count, n, 3 if logn < 9 else 2, flags, fused=1, seed=logn + first, plans=plans)
@@ -56,8 +51,8 @@ def test_route_proof_by_the_sentinel(lib, oracle, logn, nlimbs, first, count):
     """an all-FP64 chain.  NTT_OPT_MODUP_FUSED 1: the sentinel in every non-digit slot of d_ext survives, the digit is unchanged;
     0: the same c^ bit for bit, the slots hold ntt_rns_mod_up_batch's words"""
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50] * nlimbs)
-    plans = _plans(lib, n, primes, roots)
+    primes, roots = rs.chain(lib, n, [50] * nlimbs)
+    plans = rs.plans(lib, n, primes, roots)
     digit = range(first, first + count)
     try:
         c1, ext1, up = mm.run(lib, oracle, primes, roots, first, count, n, 2, A | B, fused=1, seed=3, plans=plans)
@@ -77,7 +72,7 @@ def test_route_proof_by_the_sentinel(lib, oracle, logn, nlimbs, first, count):
 def test_grid_stride_loop_wraps(lib, oracle, bits, first, count):
     """2^14, 5 polynomials, NTT_OPT_MAX_GRID 2: two workgroups for the one FP64 limb (rounds of 2, 2 and 1 blocks), or one per limb"""
     n = 1 << 14
-    primes, roots = rm.chain(lib, n, bits)
+    primes, roots = rs.chain(lib, n, bits)
     mm.run(lib, oracle, primes, roots, first, count, n, 5, A | B, fused=1, seed=14, max_grid=2)
 
 
@@ -86,7 +81,7 @@ def test_grid_stride_loop_wraps(lib, oracle, bits, first, count):
 def test_batches(lib, oracle, logn, batch):
     """several blocks per workgroup with the last group partly dead (2^8: 73), one polynomial, 130"""
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50, 50, 50, 60])
+    primes, roots = rs.chain(lib, n, [50, 50, 50, 60])
     mm.run(lib, oracle, primes, roots, 1, 2, n, batch, A, fused=1, seed=batch)
     mm.run(lib, oracle, primes, roots, 3, 1, n, batch, B, fused=1, seed=batch + 1)
 
@@ -98,7 +93,7 @@ def test_batches(lib, oracle, logn, batch):
 def test_digit_positions(lib, oracle, nlimbs, first, count, fused):
     """digits at the start, in the middle and at the end (inside P), of 1 and of 16 limbs, chains of more than 16 limbs"""
     n = 1 << 10
-    primes, roots = rm.chain(lib, n, [60] + [50] * (nlimbs - 3) + [60, 60])
+    primes, roots = rs.chain(lib, n, [60] + [50] * (nlimbs - 3) + [60, 60])
     mm.run(lib, oracle, primes, roots, first, count, n, 2, A | B, fused=fused, seed=nlimbs + first)
 
 
@@ -106,9 +101,9 @@ def test_digit_positions(lib, oracle, nlimbs, first, count, fused):
 def test_digit_of_largest_words(lib, oracle):
     """every digit word b_i - 1 over 16 limbs: the largest 128-bit sum"""
     n = 1 << 10
-    primes, roots = rm.chain(lib, n, [50] * 18)
+    primes, roots = rs.chain(lib, n, [50] * 18)
     mm.run(lib, oracle, primes, roots, 1, 16, n, 2, A, fused=1, seed=5, digit_max=True)
-    primes, roots = rm.chain(lib, n, [60] * 16 + [50, 52])
+    primes, roots = rs.chain(lib, n, [60] * 16 + [50, 52])
     mm.run(lib, oracle, primes, roots, 0, 16, n, 2, B, fused=1, seed=6, digit_max=True)
 
 
@@ -117,7 +112,7 @@ def test_digit_of_largest_words(lib, oracle):
 @pytest.mark.parametrize("flags", [A, B, A | B])
 def test_layouts(lib, oracle, layout, flags):
     n = 1 << 11
-    primes, roots = rm.chain(lib, n, [50, 50, 50, 52, 60, 60])
+    primes, roots = rs.chain(lib, n, [50, 50, 50, 52, 60, 60])
     mm.run(lib, oracle, primes, roots, 1, 2, n, 3, flags, layout=layout, fused=1, seed=11)
 
 
@@ -127,7 +122,7 @@ def test_layouts(lib, oracle, layout, flags):
 def test_lazy_key_words(lib, oracle, flags, fused):
     """key words up to min(4q, 2^53) - 1"""
     n = 1 << 10
-    primes, roots = rm.chain(lib, n, [50, 51, 30, 52, 50])
+    primes, roots = rs.chain(lib, n, [50, 51, 30, 52, 50])
     mm.run(lib, oracle, primes, roots, 0, 1, n, 3, flags, fused=fused, seed=21)
 
 
@@ -139,8 +134,8 @@ def test_composition_integer_policies(lib, oracle, arith, bits):
     run on the composition, whatever NTT_OPT_MODUP_FUSED says"""
     n = 1 << 12
     a = {"auto": lib.ARITH_AUTO, "u64": lib.ARITH_U64, "r4": lib.ARITH_U64_R4}[arith]
-    primes, roots = rm.chain(lib, n, [bits] * 5)
-    plans = _plans(lib, n, primes, roots, a)
+    primes, roots = rs.chain(lib, n, [bits] * 5)
+    plans = rs.plans(lib, n, primes, roots, a)
     try:
         _, ext, up = mm.run(lib, oracle, primes, roots, 1, 2, n, 3, A | B, fused=1, seed=7, plans=plans)
         assert not mm.untouched(ext, 1, 2), "an integer-policy run cannot take the fused kernel"
@@ -153,7 +148,7 @@ def test_composition_integer_policies(lib, oracle, arith, bits):
 @pytest.mark.parametrize("logn", [5, 15])
 def test_composition_outside_the_fused_sizes(lib, oracle, logn):
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50, 50, 50, 60, 60])
+    primes, roots = rs.chain(lib, n, [50, 50, 50, 60, 60])
     _, ext, _ = mm.run(lib, oracle, primes, roots, 1, 2, n, 2, A | B, fused=1, seed=logn)
     assert not mm.untouched(ext, 1, 2)
     mm.run(lib, oracle, primes, roots, 3, 2, n, 2, 0, fused=1, seed=logn + 1)
@@ -164,7 +159,7 @@ def test_composition_outside_the_fused_sizes(lib, oracle, logn):
 @pytest.mark.parametrize("first,count", [(0, 2), (2, 3), (6, 2)])
 def test_mixed_chains(lib, oracle, first, count, fused):
     n = 1 << 12
-    primes, roots = rm.chain(lib, n, [60, 50, 50, 52, 50, 30] + [60, 60])
+    primes, roots = rs.chain(lib, n, [60, 50, 50, 52, 50, 30] + [60, 60])
     mm.run(lib, oracle, primes, roots, first, count, n, 3, A | B, fused=fused, seed=first)
 
 
@@ -185,8 +180,8 @@ def _inverse_only_plan(lib, n, q, w):
 @pytest.mark.gpu
 def test_argument_errors_write_nothing(lib, oracle):
     n, batch = 1 << 10, 2
-    primes, roots = rm.chain(lib, n, [50] * 18)
-    plans = _plans(lib, n, primes, roots)
+    primes, roots = rs.chain(lib, n, [50] * 18)
+    plans = rs.plans(lib, n, primes, roots)
     q2 = lib.find_prime(50, 2 * n)
     other = lib.Plan(2 * n, q2, lib.min_root(q2, 2 * n))
     same = lib.Plan(n, primes[0], roots[0])
@@ -230,24 +225,15 @@ def test_argument_errors_write_nothing(lib, oracle):
         _destroy(plans + [other, same, inv_only])
 
 
-def _checksums(exe):
-    r = subprocess.run(["timeout", "-k", "10", "120", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return [line for line in r.stdout.splitlines() if line.startswith("poly ")]
+def _checksums(lib, name):
+    return [line for line in children.run_example(lib, name).splitlines() if line.startswith("poly ")]
 
 
 @pytest.mark.gpu
 def test_fused_example_prints_the_lines_of_the_two_call_example(lib, oracle):
-    exes = []
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    for name in ("rns_key_switch_fused", "rns_key_switch"):
-        exe = os.path.join(ROOT, "build", name + "_for_modup_mul")
-        subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", name + ".c"),
-                               "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x", "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-        exes.append(exe)
-    fused = _checksums(exes[0])
+    fused = _checksums(lib, "rns_key_switch_fused")
     assert len(fused) == 16
-    assert fused == _checksums(exes[1])  # (started only after the first exited 0)
+    assert fused == _checksums(lib, "rns_key_switch")  # (started only after the first exited 0)
     got = {(int(m.group(1)), int(m.group(2))): int(m.group(3), 16)
            for m in (re.match(r"poly (\d+) limb (\d+) q \d+ checksum ([0-9a-f]+)", line) for line in fused)}
     n, nq, np_, alpha = 1 << 13, 8, 2, 2
@@ -270,13 +256,8 @@ def test_launch_proof_every_instance_and_the_route_call():
     (0, 2), NTT_OPT_MODUP_FUSED 1) is the only launch of modup_mul_kernel<ArithF64,14,1>, no FP64 fwd_mul_kernel runs anywhere in
     the child and bconv_kernel only once, for the route call's two 60-bit limbs (the child itself checks that the FP64 run's slots of
     d_ext keep the sentinel)"""
-    saved = tgr.MODEL_PY
-    tgr.MODEL_PY = MODEL_PY
-    try:
-        launched = tgr._traced([], 600)
-    finally:
-        tgr.MODEL_PY = saved
-    want = {"modup_mul_kernel<%s,%d,%d>" % (pol, logn, k) for pol, k, logn in mm.launch_cases()}
+    launched = children.traced(MODEL_PY, [], 600)
+    want = rs.kernel_names("modup_mul_kernel", rs.fused_launch_cases())
     assert len(want) == 36
     assert not sorted(want - set(launched)), "instances never launched: %s" % sorted(want - set(launched))
     assert launched.count("modup_mul_kernel<ArithF64,14,1>") == 1, launched

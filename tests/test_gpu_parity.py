@@ -9,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import children
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 UNI_SEED = 0x5EED5EED
@@ -1434,79 +1436,45 @@ def test_compat_device_selection_env():
     assert bad.returncode != 0 and "libntt_mi355x" in bad.stderr and "ok" not in bad.stdout
 
 
-def test_c_example_runs():
+def test_c_example_runs(lib):
     """the plain-C caller of the batched API (examples/batched_product.c): built here if it did not travel, run on the
     GPU, exit code 0 = its product coefficient equals the schoolbook value"""
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    exe = os.path.join(ROOT, "build", "batched_product")
-    libdir = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_amd")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "batched_product.c"), "-L" + libdir, "-lntt_mi355x",
-                           "-Wl,-rpath," + libdir, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "schoolbook" in out.stdout
+    out = children.run_example(lib, "batched_product", 300)
+    assert "schoolbook" in out
 
 
-def test_c_example_pointer_batch_runs():
+def test_c_example_pointer_batch_runs(lib):
     """examples/pointer_batch.c: 96 polynomials allocated ONE BY ONE (ntt_dev_malloc each), transformed in one launch through
     ntt_transform_ptrs and ntt_transform_dev_ptrs, multiplied through ntt_negacyclic_mul_dev_ptrs -- from plain C; exit code 0 =
     equal to the contiguous slab word for word, product coefficient equal to the schoolbook value"""
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    exe = os.path.join(ROOT, "build", "pointer_batch")
-    libdir = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_amd")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "pointer_batch.c"), "-L" + libdir, "-lntt_mi355x", "-Wl,-rpath," + libdir, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert out.stdout.count("equal to the slab") == 2 and "schoolbook" in out.stdout
+    out = children.run_example(lib, "pointer_batch", 300, extra=children.STRICT)
+    assert out.count("equal to the slab") == 2 and "schoolbook" in out
 
 
-def test_c_example_rns_ciphertext_tensor_runs():
+def test_c_example_rns_ciphertext_tensor_runs(lib):
     """examples/rns_ciphertext_tensor.c: the tensor step of a ciphertext multiplication over four SEPARATELY ALLOCATED RNS polynomials
     (eight 50-bit primes, N = 2^14) from plain C -- ntt_rns_transform_dev_ptrs, ntt_rns_inv_dot_dev_ptrs (k = 1 over two pairs, k = 2),
     ntt_rns_negacyclic_mul_dev_ptrs, every call one launch over all limbs; one coefficient of every limb of e0, e1, e2 against the
     schoolbook value"""
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    exe = os.path.join(ROOT, "build", "rns_ciphertext_tensor")
-    libdir = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_amd")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "rns_ciphertext_tensor.c"), "-L" + libdir, "-lntt_mi355x", "-Wl,-rpath," + libdir, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert out.stdout.count("equal to the schoolbook value") == 3 and "word for word" in out.stdout
+    out = children.run_example(lib, "rns_ciphertext_tensor", 300, extra=children.STRICT)
+    assert out.count("equal to the schoolbook value") == 3 and "word for word" in out
 
 
-def test_c_example_rns_modulus_chain_runs():
+def test_c_example_rns_modulus_chain_runs(lib):
     """examples/rns_chain_product.c: the RNS entry points from plain C over a chain of a 60-bit, three 50-bit and two 57-bit
     primes (runs of compatible limbs), every limb's product coefficient against the schoolbook value"""
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    exe = os.path.join(ROOT, "build", "rns_chain_product")
-    libdir = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_amd")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "rns_chain_product.c"), "-L" + libdir, "-lntt_mi355x",
-                           "-Wl,-rpath," + libdir, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert out.stdout.count("schoolbook") == 6 and out.stdout.count("same coefficients") == 2 and "round trip exact" in out.stdout
-    assert "MISMATCH" not in out.stdout
+    out = children.run_example(lib, "rns_chain_product", 300)
+    assert out.count("schoolbook") == 6 and out.count("same coefficients") == 2 and "round trip exact" in out
+    assert "MISMATCH" not in out
 
 
-def test_c_example_graph_replay_runs():
+def test_c_example_graph_replay_runs(lib):
     """examples/graph_replay.c: a key-switching step (three forward-side multiply-accumulates with a broadcast key, one NTT-domain
     product: four XCD-local launches at N = 2^16) captured into a HIP graph from plain C after ntt_plan_reserve, replayed four times
     on new inputs, each replay equal to the direct calls on every polynomial; the capture and the replays allocate nothing"""
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    exe = os.path.join(ROOT, "build", "graph_replay")
-    libdir = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_amd")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROOT, "include"), "-I/opt/rocm/include",
-                           os.path.join(ROOT, "examples", "graph_replay.c"), "-L" + libdir, "-lntt_mi355x", "-L/opt/rocm/lib", "-lamdhip64",
-                           "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert out.stdout.count("graph == direct calls") == 4 and "MISMATCH" not in out.stdout
+    out = children.run_example(lib, "graph_replay", 600,
+                               extra=("-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib"))
+    assert out.count("graph == direct calls") == 4 and "MISMATCH" not in out
 
 
 def test_torch_tensors_and_streams_interoperate():
@@ -1515,10 +1483,7 @@ def test_torch_tensors_and_streams_interoperate():
     the torch wheel bundles its own HIP runtime under the same SONAME, and the library must bind to the copy torch
     loaded (loaded the other way round the process holds two runtimes and the second one finds no device --
     profiles/r02/torch_runtime_coexistence.txt).  This is also the order of bench.py's torch.distributed path."""
-    import sys
     code = """
-import sys
-sys.path.insert(0, %r); sys.path.insert(0, %r)
 import torch
 assert torch.cuda.is_available()
 torch.cuda.set_device(0)
@@ -1540,9 +1505,8 @@ assert torch.cuda.current_device() == 0
 assert np.array_equal(y.cpu().numpy().view(np.uint64), orc.ctx(n, q, w).fwd(a))
 assert np.array_equal(t.cpu().numpy().view(np.uint64), a)
 print("interop ok")
-""" % (ROOT, os.path.join(ROOT, "tests"))
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and "interop ok" in out.stdout, out.stderr[-3000:]
+"""
+    children.python_child(code, 600, marker="interop ok")
 
 
 def test_bench_rccl_control_plane_single_rank():
@@ -1612,10 +1576,7 @@ def test_product_pipeline_captured_in_a_hip_graph():
     is captured ONCE into a HIP graph (torch.cuda.graph on a side stream; the library only enqueues kernels on the
     stream it is given -- no allocation, synchronisation or device query inside the batched entry points) and replayed
     on new inputs; every replay equals the oracle's schoolbook-free product (fwd, pointwise, inv)."""
-    import sys
     code = """
-import sys
-sys.path.insert(0, %r); sys.path.insert(0, %r)
 import torch
 torch.cuda.set_device(0)
 import numpy as np
@@ -1646,9 +1607,8 @@ for seed in (1, 2, 3):
         want = cx.inv(orc.pointwise(cx.fwd(a[sl]), cx.fwd(b[sl]), q))
         assert np.array_equal(got[sl], want), (seed, i)
 print("graph ok")
-""" % (ROOT, os.path.join(ROOT, "tests"))
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and "graph ok" in out.stdout, (out.stdout[-1000:], out.stderr[-3000:])
+"""
+    children.python_child(code, 600)
 
 
 def test_single_launch_two_pass_transform_captured_in_a_hip_graph():
@@ -1657,10 +1617,7 @@ def test_single_launch_two_pass_transform_captured_in_a_hip_graph():
     the plan has not seen takes the per-pass launches, and (warm) a capture on a stream that already owns a buffer records
     the clearing kernel + the one launch; so does one on a stream ntt_plan_reserve prepared.  All three graphs, replayed on fresh inputs,
     equal the oracle on sampled polynomials and each other on all of them; so does the product chain."""
-    import sys
     code = """
-import sys
-sys.path.insert(0, %r); sys.path.insert(0, %r)
 import torch
 torch.cuda.set_device(0)
 import numpy as np
@@ -1707,9 +1664,8 @@ for seed in (1, 2):
     assert np.array_equal(outs[("cold", seed)], outs[("warm", seed)]), seed
     assert np.array_equal(outs[("cold", seed)], outs[("reserved", seed)]), seed
 print("graph ok")
-""" % (ROOT, os.path.join(ROOT, "tests"))
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0 and "graph ok" in out.stdout, (out.stdout[-1000:], out.stderr[-3000:])
+"""
+    children.python_child(code, 900)
 
 
 def test_captured_xcd_local_launches_replayed_between_other_work():
@@ -1718,10 +1674,7 @@ def test_captured_xcd_local_launches_replayed_between_other_work():
     96 of 96 wrong polynomials here from the second replay on: profiles/r05/graph_replay_control_block_clear.txt); the block is now
     cleared by a kernel.  A graph that BEGINS with the XCD-local launches (forward transform, product), six replays with 2 GiB of
     unrelated traffic between them, every polynomial against the oracle."""
-    import sys
     code = """
-import sys
-sys.path.insert(0, %r); sys.path.insert(0, %r)
 import torch
 torch.cuda.set_device(0)
 import numpy as np
@@ -1754,9 +1707,8 @@ for seed in (1, 2, 3, 1, 2, 3):
         assert np.array_equal(got_p[sl], cx.inv(orc.pointwise(fb, fb, q))), ("product", seed, j)
     big = torch.empty(1 << 28, dtype=torch.int64, device="cuda:0"); big.fill_(1); torch.cuda.synchronize(); del big
 print("graph ok")
-""" % (ROOT, os.path.join(ROOT, "tests"))
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0 and "graph ok" in out.stdout, (out.stdout[-1000:], out.stderr[-3000:])
+"""
+    children.python_child(code, 900)
 
 
 def test_rns_xcd_local_launches_over_limbs_captured_in_a_hip_graph():
@@ -1764,10 +1716,7 @@ def test_rns_xcd_local_launches_over_limbs_captured_in_a_hip_graph():
     queue entry, control block of the run's first plan): product, NTT-domain inner product and forward-side product captured after
     ntt_plan_reserve on the first plan, replayed between unrelated traffic, every word against the uncaptured per-limb per-chunk
     calls, samples against the oracle"""
-    import sys
     code = """
-import sys
-sys.path.insert(0, %r); sys.path.insert(0, %r)
 import torch
 torch.cuda.set_device(0)
 import numpy as np
@@ -1818,19 +1767,15 @@ for rep in range(3):
     for x in (da, db, dc): x.free()
     big = torch.empty(1 << 27, dtype=torch.int64, device="cuda:0"); big.fill_(1); torch.cuda.synchronize(); del big
 print("graph ok")
-""" % (ROOT, os.path.join(ROOT, "tests"))
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0 and "graph ok" in out.stdout, (out.stdout[-1000:], out.stderr[-3000:])
+"""
+    children.python_child(code, 900)
 
 
 def test_one_launch_ntt_domain_products_captured_in_a_hip_graph():
     """round 5's one-launch kernels (team_dot_kernel, team_mul_kernel) inside a HIP graph: control blocks from ntt_plan_reserve, the
     capture records the clearing kernel + one launch per call; two replays on fresh inputs with direct (uncaptured, per-chunk) calls
     between them -- the interleaving that exposed the unreliable captured memset -- every word, and one polynomial against the oracle"""
-    import sys
     code = """
-import sys
-sys.path.insert(0, %r); sys.path.insert(0, %r)
 import torch
 torch.cuda.set_device(0)
 import numpy as np
@@ -1869,9 +1814,8 @@ for seed in (1, 2):
     assert np.array_equal(got_c[sl], cx.inv(orc.pointwise(a[sl], b[sl], q))) and np.array_equal(got_d[sl], orc.pointwise(cx.fwd(a[sl]), b[sl], q))
     for x in (da, db, dc): x.free()
 print("graph ok")
-""" % (ROOT, os.path.join(ROOT, "tests"))
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0 and "graph ok" in out.stdout, (out.stdout[-1000:], out.stderr[-3000:])
+"""
+    children.python_child(code, 900)
 
 
 def test_concurrent_host_threads_on_their_own_streams(lib, oracle, kat):
@@ -2409,10 +2353,7 @@ def test_captured_xcd_local_launch_survives_regrowth_and_concurrent_direct_calls
     direct block only -- the graph, replayed afterwards, still runs on live memory and equals the oracle; (ii) the graph
     replayed on ANOTHER stream while direct calls of the same plan run on the capture stream: both results right (separate
     counters).  The NTT-domain products (no workspace at all) are captured beside the transform."""
-    import sys
     code = """
-import sys
-sys.path.insert(0, %r); sys.path.insert(0, %r)
 import torch
 torch.cuda.set_device(0)
 import numpy as np
@@ -2474,9 +2415,8 @@ got = tbig.cpu().numpy().view(np.uint64)
 for j in (0, 700, 1535):
     assert np.array_equal(got[j * n:(j + 1) * n], cx.fwd(bigv[j * n:(j + 1) * n])), ("concurrent direct", j)
 print("graph ok")
-""" % (ROOT, os.path.join(ROOT, "tests"))
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0 and "graph ok" in out.stdout, (out.stdout[-1000:], out.stderr[-3000:])
+"""
+    children.python_child(code, 900)
 
 
 @pytest.mark.parametrize("cls", sorted(_DOT_MODULI))

@@ -2,23 +2,19 @@
 tests/plain_model.py (to_double: with the correctly rounded conversion of the CRT integer) bit for bit; the operands and the output sit
 among canaries, which stay untouched, as the inputs do.  The corner words are also compared with the big-integer definitions wherever
 they lie outside the band, and the toy BFV and BGV of the earlier rounds decrypt through the two calls."""
-import os
 import random
-import subprocess
 from math import prod
 
 import numpy as np
 import pytest
 
 import bgv_model as bm
+import children
 import exact_bconv_model as xm
 import keyswitch_model as km
 import plain_model as pm
-import rescale_model as rm
-import test_gpu_bgv as tgb
-import test_gpu_exact_bconv as tgx
+import rns_support as rs
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TS = [2, 256, 65537, 1 << 32, (1 << 61) - 1]
 MODES = [0, pm.SCALE]
 MODE_IDS = ["centred", "scale"]
@@ -39,7 +35,7 @@ def _bits(nlimbs):
 def test_shapes(lib, logn, batch, nlimbs, t, flags):
     """one limb, the tail groups of one and two, one full group of four loads, four of them; N = 2, one and several workgroups"""
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, _bits(nlimbs))
+    primes, roots = rs.chain(lib, n, _bits(nlimbs))
     pm.check_plain(lib, primes, roots, n, batch, t, flags, pm.random_limbs(primes, batch * n, logn + batch + nlimbs))
 
 
@@ -49,7 +45,7 @@ def test_shapes(lib, logn, batch, nlimbs, t, flags):
 def test_load_groups_and_tails(lib, nlimbs, flags):
     """every remainder of the groups of four beside the counts of test_shapes"""
     n = 64
-    primes, roots = rm.chain(lib, n, _bits(nlimbs))
+    primes, roots = rs.chain(lib, n, _bits(nlimbs))
     pm.check_plain(lib, primes, roots, n, 3, 65537, flags, pm.random_limbs(primes, 3 * n, nlimbs))
 
 
@@ -58,7 +54,7 @@ def test_load_groups_and_tails(lib, nlimbs, flags):
 def test_grid_wrap(lib, flags):
     """NTT_OPT_MAX_GRID = 3 on plans[0] at 2^10, 5 polynomials: every thread walks several iterations and polynomials"""
     n, batch = 1 << 10, 5
-    primes, roots = rm.chain(lib, n, _bits(5))
+    primes, roots = rs.chain(lib, n, _bits(5))
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     plans[0].set_option(lib.OPT_MAX_GRID, 3)
     try:
@@ -76,8 +72,8 @@ def test_grid_wrap(lib, flags):
 def test_strided(lib, kind, flags):
     """[batch][limb][N] and [limb][batch][N] with padded strides, the output's polynomials N + 24 words apart"""
     n, batch, nl = 64, 5, 6
-    primes, roots = rm.chain(lib, n, _bits(nl))
-    ls, ps, _ = rm.layout_strides(kind, n, nl, batch)
+    primes, roots = rs.chain(lib, n, _bits(nl))
+    ls, ps, _ = rs.layout_strides(kind, n, nl, batch)
     pm.check_plain(lib, primes, roots, n, batch, 1 << 32, flags, pm.random_limbs(primes, batch * n, 11), layout=(ls, ps, n + 24))
 
 
@@ -87,8 +83,8 @@ def test_strided(lib, kind, flags):
 def test_output_in_place_of_limb_0(lib, kind, flags):
     """d_m == d_a: the plaintext lands in limb 0's slots, every other limb and every gap untouched"""
     n, batch, nl = 256, 3, 5
-    primes, roots = rm.chain(lib, n, _bits(nl))
-    ls, ps, _ = rm.layout_strides(kind, n, nl, batch)
+    primes, roots = rs.chain(lib, n, _bits(nl))
+    ls, ps, _ = rs.layout_strides(kind, n, nl, batch)
     pm.check_plain(lib, primes, roots, n, batch, 65537, flags, pm.random_limbs(primes, batch * n, 13), layout=(ls, ps, ps), alias=True)
 
 
@@ -101,7 +97,7 @@ def test_corner_words(lib, nlimbs, flags):
     """x in {0, 1, Q - 1, (Q -+ 1) / 2}; SCALE: t x mod Q = (Q -+ 1) / 2 and the x either side of k Q / t, k = 1 and t - 1 -- bit for
     bit against the model, and against the definition wherever they lie outside the band (inside: one of the two neighbours)"""
     n = 16
-    primes, roots = rm.chain(lib, n, _bits(nlimbs))
+    primes, roots = rs.chain(lib, n, _bits(nlimbs))
     Q = prod(primes)
     for t in TS:
         xs = pm.corner_values(Q, t, flags)
@@ -119,7 +115,7 @@ def test_corner_words(lib, nlimbs, flags):
 def test_largest_sums(lib, flags):
     """16 limbs of 60-bit primes, every digit z_i = q_i - 1, t = 2^61 - 1: the largest 128-bit sum and the largest FP64 sum"""
     n, t = 16, (1 << 61) - 1
-    primes, roots = rm.chain(lib, n, [60] * 16)
+    primes, roots = rs.chain(lib, n, [60] * 16)
     c, _, _, _ = pm.constants(primes, t, flags)
     top = [(q - 1) * pow(ci, -1, q) % q for q, ci in zip(primes, c)]
     limbs = pm.random_limbs(primes, n, 3)
@@ -138,7 +134,7 @@ def test_to_double(lib, logn, batch, bits, scale):
     """ties to even at 2^53, a tie and a sticky bit at 2^100, zero (+0.0), -+(Q - 1) / 2 and random words: the bit pattern of
     fl(x_c) * scale, x_c by big-integer CRT, fl Python's correctly rounded conversion"""
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, bits)
+    primes, roots = rs.chain(lib, n, bits)
     Q = prod(primes)
     rng = random.Random(logn)
     xs = (pm.double_values(Q) + [rng.randrange(Q) for _ in range(batch * n)])[:batch * n] if n > 2 else pm.double_values(Q)[3:5]
@@ -161,8 +157,8 @@ def test_to_double(lib, logn, batch, bits, scale):
 @pytest.mark.parametrize("alias", [False, True])
 def test_to_double_strided(lib, alias):
     n, batch = 64, 3
-    primes, roots = rm.chain(lib, n, [60, 50])
-    ls, ps, _ = rm.layout_strides("batch_padded", n, 2, batch)
+    primes, roots = rs.chain(lib, n, [60, 50])
+    ls, ps, _ = rs.layout_strides("batch_padded", n, 2, batch)
     limbs = pm.random_limbs(primes, batch * n, 5)
     got = pm.run_plain(lib, primes, roots, n, batch, None, 0, limbs, layout=(ls, ps, ps if alias else n + 8), alias=alias, double_scale=0.125)
     assert np.array_equal(got, pm.double_model(limbs, primes, 0.125))
@@ -175,9 +171,9 @@ def test_refusals_leave_the_buffers_alone(lib):
     """every refusal of the header: NTT_ERR_ARG (-1), nothing written.  (A prime >= 2^61 cannot reach the call: no plan is created for
     one, which is asserted instead.)"""
     n, batch = 64, 2
-    primes, roots = rm.chain(lib, n, [50] * 17)
+    primes, roots = rs.chain(lib, n, [50] * 17)
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
-    other_n = lib.Plan(2 * n, *[v[0] for v in rm.chain(lib, 2 * n, [50])])
+    other_n = lib.Plan(2 * n, *[v[0] for v in rs.chain(lib, 2 * n, [50])])
     t_div = primes[1] * 3  # SCALE: a prime divides t
     img = np.arange(17 * batch * n, dtype=np.uint64)
     da, dm = lib.DeviceBuffer(img.size).upload(img), lib.DeviceBuffer(img.size).upload(img)
@@ -251,7 +247,7 @@ def test_bfv_product_decrypts_through_the_two_calls(lib, oracle):
     """the toy BFV of exact_bconv_model at N = 64: encrypt, the multiplication of examples/rns_bfv_mul.c on the device, then
     ntt_rns_inv_dot_batch + ntt_rns_to_plain_batch(NTT_PLAIN_SCALE) on (d0, d1, d2): the product of the messages"""
     n, nr, nq, t = 64, 3, 2, 65537
-    primes, roots = rm.chain(lib, n, [50] * (nr + nq))
+    primes, roots = rs.chain(lib, n, [50] * (nr + nq))
     qp, qr = primes[nr:], roots[nr:]
     Q = prod(qp)
     rng = random.Random(64)
@@ -260,7 +256,7 @@ def test_bfv_product_decrypts_through_the_two_calls(lib, oracle):
     ct = [p for m in (m1, m2) for p in xm.bfv_encrypt(rng, s, m, n, Q, t)]
     ntt = [[oracle.ctx(n, q, w).fwd(c) for q, w, c in zip(qp, qr, km.residues(p, qp))] for p in ct]
     assert _decrypt_on_device(lib, oracle, qp, qr, n, ntt[:2], s, t, lib.PLAIN_SCALE) == m1
-    d = tgx._bfv_on_device(lib, primes, roots, nr, t, ntt, n)
+    d = xm.bfv_on_device(lib, primes, roots, nr, t, ntt, n)
     assert _decrypt_on_device(lib, oracle, qp, qr, n, [dj[nr:] for dj in d], s, t, lib.PLAIN_SCALE) == xm.negacyclic(m1, m2, n, t)
 
 
@@ -268,15 +264,15 @@ def test_bfv_product_decrypts_through_the_two_calls(lib, oracle):
 def test_bgv_product_decrypts_through_the_two_calls(lib, oracle):
     """the toy BGV of bgv_model at N = 64: encrypt, multiply and relinearise on the device, then ntt_rns_inv_dot_batch +
     ntt_rns_to_plain_batch (default mode): the product of the messages; after the modulus switch, that times q_3^-1 mod T"""
-    n, nq, npp, T = 64, 4, 2, tgb.PT
-    primes, roots = rm.chain(lib, n, [50] * nq + [60] * npp)
+    n, nq, npp, T = 64, 4, 2, bm.PT
+    primes, roots = rs.chain(lib, n, [50] * nq + [60] * npp)
     rng = random.Random(65)
     bgv = bm.Bgv(oracle, primes, roots, nq, 2, n, T, rng)
     keys = bgv.relin_keys()
     m1, m2 = ([rng.randrange(T) for _ in range(n)] for _ in range(2))
     ct1, ct2 = bgv.encrypt(m1), bgv.encrypt(m2)
     assert _decrypt_on_device(lib, oracle, primes[:nq], roots[:nq], n, list(ct1), bgv.s, T, 0) == m1
-    relin, switched = tgb._bgv_mul_on_device(lib, bgv, ct1, ct2, keys)
+    relin, switched = bm.mul_on_device(lib, bgv, ct1, ct2, keys)
     want = bgv.plain_product(m1, m2)
     assert _decrypt_on_device(lib, oracle, primes[:nq], roots[:nq], n, relin, bgv.s, T, 0) == want
     f = pow(primes[nq - 1], -1, T)
@@ -285,10 +281,5 @@ def test_bgv_product_decrypts_through_the_two_calls(lib, oracle):
 
 @pytest.mark.gpu
 def test_example_checksums_match_the_model(lib, oracle):
-    exe = os.path.join(ROOT, "build", "rns_decrypt")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "rns_decrypt.c"),
-                           "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x", "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-    r = subprocess.run(["timeout", "-k", "10", "120", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.splitlines() == pm.example_model(lib, oracle)
+    out = children.run_example(lib, "rns_decrypt")
+    assert out.splitlines() == pm.example_model(lib, oracle)

@@ -4,15 +4,14 @@ device-resident polynomials at irregular, shuffled places go through ntt_transfo
 uploaded) and ntt_transform_dev_ptrs (device array: as given, capturable), the kernels reading every polynomial's address from a
 device table (csrc/ntt_core.h poly_offset).  Every polynomial against the oracle, every word between them untouched."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
+import children
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GUARD = np.uint64(0xA5A5A5A5A5A5A5A5)
 
 
@@ -163,10 +162,7 @@ def test_shuffled_rns_pointer_batch(lib, oracle, m, nl, bits, count, launch):
 def test_device_pointer_table_captured_in_a_hip_graph():
     """ntt_transform_dev_ptrs allocates nothing and copies nothing: a forward transform over a shuffled pointer batch captured into
     a HIP graph (torch.cuda.CUDAGraph; a process of its own: torch has to be imported before the library), replayed on fresh data"""
-    import subprocess
     code = """
-import sys
-sys.path.insert(0, %r); sys.path.insert(0, %r)
 import torch
 torch.cuda.set_device(0)
 import numpy as np
@@ -178,7 +174,7 @@ q = lib.find_prime(51, n, 0)
 w = lib.min_root(q, n)
 plan, cx = lib.Plan(n, q, w), orc.ctx(n, q, w)
 rng = np.random.default_rng(5)
-gaps = rng.integers(1, 64, size=count) + np.arange(count) %% 7
+gaps = rng.integers(1, 64, size=count) + np.arange(count) % 7
 starts = np.cumsum(gaps + n) - n
 offs = [int(starts[i]) for i in rng.permutation(count)]
 words = int(starts[-1] + n + 8)
@@ -206,19 +202,15 @@ for seed in (1, 2, 3):
     for i in range(count):
         assert np.array_equal(got[offs[i]:offs[i] + n], cx.fwd(polys[i].copy())), (seed, i)
 print("graph ok")
-""" % (ROOT, os.path.join(ROOT, "tests"))
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert out.returncode == 0 and "graph ok" in out.stdout, out.stderr[-3000:]
+"""
+    children.python_child(code, 600)
 
 
 def test_products_over_device_tables_captured_in_a_hip_graph():
     """the fused kernels' table forms allocate nothing and copy nothing either: c = a * b, d^ = fwd(c) . key^ and e = inv(a^' . k0^ + b^' . k1^)
     over shuffled device tables, three launches captured into ONE HIP graph and replayed on fresh data (a process of its own: torch
     has to be imported before the library)"""
-    import subprocess
     code = """
-import sys
-sys.path.insert(0, %r); sys.path.insert(0, %r)
 import torch
 torch.cuda.set_device(0)
 import numpy as np
@@ -231,7 +223,7 @@ w = lib.min_root(q, n)
 plan, cx = lib.Plan(n, q, w), orc.ctx(n, q, w)
 rng = np.random.default_rng(11)
 total = ops * count
-gaps = rng.integers(1, 64, size=total) + np.arange(total) %% 7
+gaps = rng.integers(1, 64, size=total) + np.arange(total) % 7
 starts = np.cumsum(gaps + n) - n
 order = rng.permutation(total)
 offs = [[int(starts[i]) for i in order[o * count:(o + 1) * count]] for o in range(ops)]
@@ -270,13 +262,12 @@ for seed in (1, 2):
         c = cx.inv(orc.pointwise(cx.fwd(A[i].copy()), cx.fwd(B[i].copy()), q))
         assert np.array_equal(got[offs[2][i]:offs[2][i] + n], c), (seed, i, "c")
         assert np.array_equal(got[offs[3][i]:offs[3][i] + n], orc.pointwise(cx.fwd(c.copy()), keys_h[0].copy(), q)), (seed, i, "d")
-        e = (orc.pointwise(A[i].copy(), keys_h[0].copy(), q) + orc.pointwise(B[i].copy(), keys_h[1].copy(), q)) %% np.uint64(q)
+        e = (orc.pointwise(A[i].copy(), keys_h[0].copy(), q) + orc.pointwise(B[i].copy(), keys_h[1].copy(), q)) % np.uint64(q)
         assert np.array_equal(got[offs[4][i]:offs[4][i] + n], cx.inv(e)), (seed, i, "e")
         assert np.array_equal(got[offs[0][i]:offs[0][i] + n], A[i]) and np.array_equal(got[offs[1][i]:offs[1][i] + n], B[i]), (seed, i, "operands")
 print("graph ok")
-""" % (ROOT, os.path.join(ROOT, "tests"))
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert out.returncode == 0 and "graph ok" in out.stdout, out.stderr[-3000:]
+"""
+    children.python_child(code, 600)
 
 
 @pytest.mark.parametrize("m", [14, 16])
@@ -284,10 +275,7 @@ def test_rns_products_over_device_tables_captured_in_a_hip_graph(m):
     """the RNS twins on a few polynomials x several primes -- one launch (2^14: the fused kernels' MULTI table forms) or one chain (2^16:
     element-wise kernel and transforms over the tables) over the whole run of limbs -- allocate and copy nothing: both operands into the
     NTT domain, e = inv(a^ . b^ + b^ . a^) and c = a' * b' over shuffled device tables captured into ONE HIP graph, replayed on fresh data"""
-    import subprocess
     code = """
-import sys
-sys.path.insert(0, %r); sys.path.insert(0, %r)
 import torch
 torch.cuda.set_device(0)
 import numpy as np
@@ -344,9 +332,8 @@ for seed in (1, 2):
             assert np.array_equal(got[offs[2][p] + l * n:offs[2][p] + (l + 1) * n], ctx[l].inv((prod + prod) %% np.uint64(qs[l]))), (seed, p, l, "e")
             assert np.array_equal(got[offs[3][p] + l * n:offs[3][p] + (l + 1) * n], ctx[l].inv(prod)), (seed, p, l, "c")
 print("graph ok")
-""" % (ROOT, os.path.join(ROOT, "tests"), m)
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert out.returncode == 0 and "graph ok" in out.stdout, (out.stdout[-1000:], out.stderr[-3000:])
+""" % m
+    children.python_child(code, 600)
 
 
 def test_pointer_batch_arguments(lib, oracle):

@@ -3,20 +3,15 @@ cases also against round / floor(x / q_L) over the CRT): both domains, round and
 sandwich route (N >= 2^15, integer-policy limbs), runs across the 16-limb boundary, mixed chains, batches, layouts with canaries,
 the dropped limb's slot, argument errors that write nothing, fused == sandwich bit for bit, the plain-C example; and two kernel
 traces: the route at 2^14 over 17 FP64 limbs (one inverse, one rescale_fwd_kernel) and the launch of all 37 new instances."""
-import csv
-import ctypes as C
-import glob
 import os
 import re
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
-import kernel_inventory
+import children
 import rescale_model as rm
+import rns_support as rs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODEL_PY = os.path.join(ROOT, "tests", "rescale_model.py")
@@ -24,11 +19,11 @@ T, F = rm.TRANSFORMED, rm.FLOOR
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("pol,k,logn", rm.launch_cases(), ids=["%s-k%d-logn%d" % c for c in rm.launch_cases()])
+@pytest.mark.parametrize("pol,k,logn", rs.fused_launch_cases(), ids=["%s-k%d-logn%d" % c for c in rs.fused_launch_cases()])
 def test_every_fused_instance(lib, oracle, pol, k, logn):
     """each rescale_fwd_kernel<policy, LOGN, class>: three limbs of the class, NTT domain, round (even LOGN) / floor (odd)"""
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [rm.CLASS_BITS[(pol, k)]] * 3)
+    primes, roots = rs.chain(lib, n, [rs.CLASS_BITS[(pol, k)]] * 3)
     flags = T | (F if logn % 2 else 0)
     rm.run_case(lib, oracle, primes, roots, n, 3 if logn < 9 else 2, flags, seed=logn, crt=logn <= 7)
 
@@ -38,7 +33,7 @@ def test_every_fused_instance(lib, oracle, pol, k, logn):
 @pytest.mark.parametrize("flags", [T, T | F])
 def test_sandwich_at_large_sizes(lib, oracle, logn, flags):
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50, 50, 50, 50])
+    primes, roots = rs.chain(lib, n, [50, 50, 50, 50])
     rm.run_case(lib, oracle, primes, roots, n, 2, flags, seed=logn)
 
 
@@ -50,7 +45,7 @@ def test_integer_policy_limbs(lib, oracle, arith, flags):
     coefficient kernel"""
     n = 1 << 12
     a = {"auto": lib.ARITH_AUTO, "u64": lib.ARITH_U64, "r4": lib.ARITH_U64_R4}[arith]
-    primes, roots = rm.chain(lib, n, [58, 58, 58] if arith != "auto" else [60, 60, 60])
+    primes, roots = rs.chain(lib, n, [58, 58, 58] if arith != "auto" else [60, 60, 60])
     plans = [lib.Plan(n, q, w, arith=a) for q, w in zip(primes, roots)]
     rm.run_case(lib, oracle, primes, roots, n, 3, flags, plans=plans, seed=7)
 
@@ -60,7 +55,7 @@ def test_integer_policy_limbs(lib, oracle, arith, flags):
 @pytest.mark.parametrize("flags", [0, T])
 def test_limb_counts_across_the_run_boundary(lib, oracle, nlimbs, flags):
     n = 1 << 10
-    primes, roots = rm.chain(lib, n, [50] * nlimbs)
+    primes, roots = rs.chain(lib, n, [50] * nlimbs)
     rm.run_case(lib, oracle, primes, roots, n, 2, flags, seed=nlimbs, crt=nlimbs <= 5)
 
 
@@ -70,7 +65,7 @@ def test_limb_counts_across_the_run_boundary(lib, oracle, nlimbs, flags):
 @pytest.mark.parametrize("flags", [0, F, T, T | F])
 def test_mixed_chains(lib, oracle, bits, flags):
     n = 1 << 12
-    primes, roots = rm.chain(lib, n, bits)
+    primes, roots = rs.chain(lib, n, bits)
     rm.run_case(lib, oracle, primes, roots, n, 3, flags, seed=len(bits), crt=False)
 
 
@@ -79,7 +74,7 @@ def test_mixed_chains(lib, oracle, bits, flags):
 @pytest.mark.parametrize("flags", [0, T])
 def test_batches(lib, oracle, batch, flags):
     n = 1 << 8
-    primes, roots = rm.chain(lib, n, [50, 50, 50, 50, 50])
+    primes, roots = rs.chain(lib, n, [50, 50, 50, 50, 50])
     rm.run_case(lib, oracle, primes, roots, n, batch, flags, seed=batch, crt=batch <= 3)
 
 
@@ -88,7 +83,7 @@ def test_batches(lib, oracle, batch, flags):
 @pytest.mark.parametrize("flags", [0, T, T | F])
 def test_layouts(lib, oracle, layout, flags):
     n = 1 << 11
-    primes, roots = rm.chain(lib, n, [50, 50, 50, 50, 52])
+    primes, roots = rs.chain(lib, n, [50, 50, 50, 50, 52])
     rm.run_case(lib, oracle, primes, roots, n, 3, flags, layout=layout, seed=11)
 
 
@@ -96,35 +91,22 @@ def test_layouts(lib, oracle, layout, flags):
 @pytest.mark.parametrize("logn,nlimbs", [(14, 17), (9, 5), (12, 20)])
 def test_fused_equals_sandwich_bit_for_bit(lib, oracle, logn, nlimbs):
     n = 1 << logn
-    primes, roots = rm.chain(lib, n, [50] * nlimbs)
+    primes, roots = rs.chain(lib, n, [50] * nlimbs)
     fused = rm.run_case(lib, oracle, primes, roots, n, 2, T, fused=1, seed=3)
     sandwich = rm.run_case(lib, oracle, primes, roots, n, 2, T, fused=0, seed=3)
     for a, b in zip(fused, sandwich):
         assert np.array_equal(a, b)
 
 
-def _forward_only_plan(lib, n, q, w):
-    """a plan built from the forward table alone (no inverse): ntt_plan_create_from_tables with w_inv_powers = NULL"""
-    logn = n.bit_length() - 1
-    rev = [int(format(i, "0%db" % logn)[::-1], 2) if logn else 0 for i in range(n)]
-    powers = np.array([pow(w, r, q) for r in rev], dtype=np.uint64)
-    h = C.c_void_p()
-    rc = lib._lib.ntt_plan_create_from_tables(C.byref(h), 0, n, q, powers.ctypes.data_as(lib.U64P), None, lib.ARITH_AUTO)
-    assert rc == 0, lib._lib.ntt_last_error()
-    p = object.__new__(lib.Plan)
-    p.h, p.N, p.q, p.root, p.device = h.value, n, q, w, 0
-    return p
-
-
 @pytest.mark.gpu
 def test_argument_errors_write_nothing(lib, oracle):
     n, batch = 1 << 10, 2
-    primes, roots = rm.chain(lib, n, [50, 50, 50])
+    primes, roots = rs.chain(lib, n, [50, 50, 50])
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     other = lib.Plan(2 * n, lib.find_prime(50, 2 * n), lib.min_root(lib.find_prime(50, 2 * n), 2 * n))
     same = lib.Plan(n, primes[0], roots[0])
-    fwd_only = _forward_only_plan(lib, n, primes[2], roots[2])
-    fwd_only_kept = _forward_only_plan(lib, n, primes[1], roots[1])
+    fwd_only = rs.forward_only_plan(lib, n, primes[2], roots[2])
+    fwd_only_kept = rs.forward_only_plan(lib, n, primes[1], roots[1])
     words = 3 * batch * n
     img = oracle.fill_uniform(words, primes[0], 5)
     buf = lib.DeviceBuffer(words).upload(img)
@@ -155,14 +137,9 @@ def test_argument_errors_write_nothing(lib, oracle):
 
 @pytest.mark.gpu
 def test_example_checksums_match_the_model(lib, oracle):
-    exe = os.path.join(ROOT, "build", "rns_rescale")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "rns_rescale.c"),
-                           "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x", "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-    r = subprocess.run(["timeout", "-k", "10", "120", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    out = children.run_example(lib, "rns_rescale")
     got = {(int(m.group(1)), int(m.group(2))): int(m.group(3), 16)
-           for m in re.finditer(r"poly (\d+) limb (\d+) q \d+ checksum ([0-9a-f]+)", r.stdout)}
+           for m in re.finditer(r"poly (\d+) limb (\d+) q \d+ checksum ([0-9a-f]+)", out)}
     n = 1 << 13
     primes = [lib.find_prime(60, n, 0)] + [lib.find_prime(50, n, k) for k in range(5)]
     roots = [lib.min_root(q, n) for q in primes]
@@ -175,37 +152,10 @@ def test_example_checksums_match_the_model(lib, oracle):
             assert got[(p, l)] == oracle.checksum(twice[l]), (p, l)
 
 
-def _rocprofv3():
-    import shutil
-    exe = "/opt/rocm/bin/rocprofv3" if os.path.exists("/opt/rocm/bin/rocprofv3") else shutil.which("rocprofv3")
-    if not exe:
-        pytest.fail("rocprofv3 is not on this machine: the launch proofs need its kernel trace")
-    return exe
-
-
-def _traced(args, seconds):
-    """run `python3 tests/rescale_model.py ARGS` in a fresh child process under a kernel trace: the normalised kernel names it
-    launched, one entry per dispatch"""
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["timeout", "-k", "10", str(seconds), _rocprofv3(), "--kernel-trace", "--output-format", "csv", "-d", d, "--",
-               sys.executable, MODEL_PY] + list(args)
-        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True)
-        assert r.returncode == 0, "traced run failed (exit %d):\n%s\n%s" % (r.returncode, r.stdout[-4000:], r.stderr[-4000:])
-        names = []
-        files = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
-        assert files, "the kernel trace wrote no CSV:\n" + r.stderr[-2000:]
-        for f in files:
-            with open(f, newline="") as fh:
-                names += [row["Kernel_Name"] for row in csv.DictReader(fh)]
-    mangled = sorted({n for n in names if n.startswith("_Z")})
-    dem = dict(zip(mangled, kernel_inventory.demangle(mangled)))
-    return [kernel_inventory.normalise(dem.get(n, n)) for n in names]
-
-
 @pytest.mark.gpu
 def test_route_proof_one_inverse_and_one_fused_launch():
     """2^14, 17 FP64 limbs (16 kept: one run), NTT domain: the call launches one inverse transform and one rescale_fwd_kernel"""
-    launched = [k for k in _traced(["--route"], 300) if k.split("<")[0] not in rm.SETUP_KERNELS]
+    launched = [k for k in children.traced(MODEL_PY, ["--route"], 300) if k.split("<")[0] not in rs.SETUP_KERNELS]
     assert len(launched) == 2, launched
     assert launched[0].startswith("fused_kernel<ArithF64,14,true"), launched
     assert launched[1] == "rescale_fwd_kernel<ArithF64,14,1>", launched
@@ -213,7 +163,7 @@ def test_route_proof_one_inverse_and_one_fused_launch():
 
 @pytest.mark.gpu
 def test_launch_proof_every_new_instance():
-    launched = set(_traced([], 600))
-    want = {"rescale_fwd_kernel<%s,%d,%d>" % (pol, logn, k) for pol, k, logn in rm.launch_cases()} | {"rescale_coef_kernel"}
+    launched = set(children.traced(MODEL_PY, [], 600))
+    want = rs.kernel_names("rescale_fwd_kernel", rs.fused_launch_cases()) | {"rescale_coef_kernel"}
     assert len(want) == 37
     assert not sorted(want - launched), "instances never launched: %s" % sorted(want - launched)

@@ -3,20 +3,15 @@ output word against the model of tests/slots_model.py, bit for bit: the device t
 persistent loop's wrap and every built instance; the composition at the sizes and policies the fused kernels do not serve; fused ==
 composition; corner words; padded layouts among canaries; the rotation, row-swap and product statements through the shipped Galois and
 product calls; a round trip through the RNS; argument errors that write nothing; the plain-C example; and two kernel traces."""
-import csv
 import ctypes as C
-import glob
 import os
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
+import children
 import galois_model as gm
-import kernel_inventory
-import rescale_model as rm
+import rns_support as rs
 import slots_model as sm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -78,7 +73,7 @@ def test_persistent_loop_wrap(lib, oracle, logn, grid, batch, direction):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("pol,k,logn", sm.launch_cases(), ids=["%s-k%d-logn%d" % c for c in sm.launch_cases()])
+@pytest.mark.parametrize("pol,k,logn", rs.fused_launch_cases(), ids=["%s-k%d-logn%d" % c for c in rs.fused_launch_cases()])
 def test_every_fused_instance(lib, oracle, pol, k, logn):
     """slots_inv_kernel and slots_fwd_kernel<policy, LOGN, class> through moduli of 30, 50, 51 and 52 bits"""
     sm.run_instance(lib, oracle, pol, k, logn)
@@ -220,7 +215,7 @@ def test_round_trip_through_the_rns(lib, oracle, fused):
     """the example's pipeline at 2^8 with three primes: encode x 2, centred lifts, product and rotation in the NTT domain, out of the
     RNS (BGV form), decode.  |coefficients of the product| <= N (t / 2)^2 < 2^39, far inside Q / 2"""
     n, batch, steps = 1 << 8, 2, 3
-    primes, roots = rm.chain(lib, n, [50, 50, 50])
+    primes, roots = rs.chain(lib, n, [50, 50, 50])
     plans = [lib.Plan(n, q, w) for q, w in zip(primes, roots)]
     pt = sm.plan_for(lib, n, T17, fused=fused)
     v1, v2 = sm.words(oracle, n, T17, batch, 11), sm.words(oracle, n, T17, batch, 12)
@@ -309,54 +304,22 @@ def test_argument_errors_write_nothing(lib, oracle, fused):
 
 @pytest.mark.gpu
 def test_example_lines_match_the_model(lib, oracle):
-    exe = os.path.join(ROOT, "build", "rns_slots")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "rns_slots.c"),
-                           "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x", "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-    r = subprocess.run(["timeout", "-k", "10", "120", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.splitlines() == sm.example_model(lib, oracle)
+    out = children.run_example(lib, "rns_slots")
+    assert out.splitlines() == sm.example_model(lib, oracle)
 
 
 # ---------------------------------------------------------------- kernel traces
 
-def _rocprofv3():
-    import shutil
-    exe = "/opt/rocm/bin/rocprofv3" if os.path.exists("/opt/rocm/bin/rocprofv3") else shutil.which("rocprofv3")
-    if not exe:
-        pytest.fail("rocprofv3 is not on this machine: the launch proofs need its kernel trace")
-    return exe
-
-
-def _traced(args, seconds):
-    """run `python3 tests/slots_model.py ARGS` in a fresh child process under a kernel trace: the normalised kernel names it launched,
-    one entry per dispatch"""
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["timeout", "-k", "10", str(seconds), _rocprofv3(), "--kernel-trace", "--output-format", "csv", "-d", d, "--",
-               sys.executable, MODEL_PY] + list(args)
-        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True)
-        assert r.returncode == 0, "traced run failed (exit %d):\n%s\n%s" % (r.returncode, r.stdout[-4000:], r.stderr[-4000:])
-        names = []
-        files = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
-        assert files, "the kernel trace wrote no CSV:\n" + r.stderr[-2000:]
-        for f in files:
-            with open(f, newline="") as fh:
-                names += [row["Kernel_Name"] for row in csv.DictReader(fh)]
-    mangled = sorted({n for n in names if n.startswith("_Z")})
-    dem = dict(zip(mangled, kernel_inventory.demangle(mangled)))
-    return [kernel_inventory.normalise(dem.get(n, n)) for n in names]
-
-
 @pytest.mark.gpu
 def test_route_proof_one_launch_per_call():
     """fused encode + decode at 2^14 x 4: exactly one slots_inv_kernel and one slots_fwd_kernel (t = 65537: class 18), nothing else"""
-    launched = [k for k in _traced(["--route"], 300) if k.split("<")[0] not in sm.SETUP_KERNELS]
+    launched = [k for k in children.traced(MODEL_PY, ["--route"], 300) if k.split("<")[0] not in sm.SETUP_KERNELS]
     assert launched == ["slots_inv_kernel<ArithF64,14,18>", "slots_fwd_kernel<ArithF64,14,18>"], launched
 
 
 @pytest.mark.gpu
 def test_launch_proof_every_new_kernel():
-    launched = set(_traced([], 600))
+    launched = set(children.traced(MODEL_PY, [], 600))
     want = sm.kernel_names()
     assert len(want) == 74
     assert not sorted(want - launched), "kernels never launched: %s" % sorted(want - launched)

@@ -14,10 +14,11 @@ import sys
 import numpy as np
 import pytest
 
+import children
 import galois_model as gm
 import key_pair_model as kp
 import keyswitch_model as km
-import test_keyswitch_cpu as tkc
+import rns_support as rs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_amd", "csrc")
@@ -34,11 +35,11 @@ def _want(f, key, acc, q, batch, flags):
     return [(int(f[i]) * kq[i % N if flags & B else i] + (int(acc[i]) if flags & A else 0)) % q for i in range(batch * N)]
 
 
-@pytest.mark.parametrize("bits,first,count", tkc.UP_CHAINS, ids=["start", "middle", "end", "one-limb", "count16"])
+@pytest.mark.parametrize("bits,first,count", km.UP_CHAINS, ids=["start", "middle", "end", "one-limb", "count16"])
 @pytest.mark.parametrize("flags", [0, A, B, B | A | L])
 def test_mod_up_mul_pair_model_equals_the_definition(oracle, bits, first, count, flags):
     batch = 2
-    primes, roots = tkc._chain(oracle, N, bits)
+    primes, roots = rs.chain(oracle, N, bits)
     basis = primes[first:first + count]
     Bp = km.prod(basis)
     rng = random.Random(len(bits) * 41 + first + flags)
@@ -62,7 +63,7 @@ def test_mod_up_mul_pair_model_equals_the_definition(oracle, bits, first, count,
 @pytest.mark.parametrize("flags", [0, A, B, B | A | L])
 def test_fwd_mul_pair_model_equals_the_definition(oracle, flags):
     batch = 3
-    primes, roots = tkc._chain(oracle, N, [50, 52, 60, 30])
+    primes, roots = rs.chain(oracle, N, [50, 52, 60, 30])
     a, keys, accs = kp.operands(oracle, primes, N, batch, 0, len(primes), flags, seed=9)
     got, fa = kp.fwd_model(oracle, primes, roots, a, keys, accs, N, batch, flags)
     for l, (q, w) in enumerate(zip(primes, roots)):
@@ -113,12 +114,7 @@ def test_python_wrappers_exist(lib):
 
 
 def test_pair_example_builds_against_the_public_header(lib):
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    exe = os.path.join(ROOT, "build", "rns_key_switch_pair")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "rns_key_switch_pair.c"), "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x",
-                           "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-    assert os.path.exists(exe)
+    assert os.path.exists(children.build_example(lib, "rns_key_switch_pair", *children.STRICT))
 
 
 def pair_kernels():
@@ -135,7 +131,7 @@ def pair_kernels():
 
 def test_pair_objects_hold_exactly_the_expected_instances_without_spills():
     ks = pair_kernels()
-    want = {"modup_mul2_kernel<%s,%d,%d>" % (pol, logn, k) for pol, k, logn in kp.launch_cases()} | {"keypair_dot2_kernel"}
+    want = rs.kernel_names("modup_mul2_kernel", rs.fused_launch_cases()) | {"keypair_dot2_kernel"}
     assert len(want) == 37
     assert set(ks) == want, ("missing %s, unexpected %s" % (sorted(want - set(ks))[:8], sorted(set(ks) - want)[:8]))
     bad = {n: (k.get("vgpr_spill_count"), k.get("private_segment_fixed_size"), k.get("group_segment_fixed_size"))

@@ -12,8 +12,10 @@ import sys
 import numpy as np
 import pytest
 
+import children
 import keyswitch_model as km
 import rescale_model as rm
+import rns_support as rs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_amd", "csrc")
@@ -21,15 +23,6 @@ LIB = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_a
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 T, F = km.TRANSFORMED, km.FLOOR
 N = 64
-
-
-def _chain(orc, n, bits_list):
-    seen, primes = {}, []
-    for b in bits_list:
-        k = seen.get(b, 0)
-        primes.append(orc.find_prime(b, n, k))
-        seen[b] = k + 1
-    return primes, [orc.min_root(q, n) for q in primes]
 
 
 # (Q bits, P bits): the chains the issue checked with Python integers
@@ -51,7 +44,7 @@ def _down_values(Q, P, count, rng):
 @pytest.mark.parametrize("qbits,pbits", DOWN_CHAINS, ids=DOWN_IDS)
 @pytest.mark.parametrize("flags", [0, F, T, T | F])
 def test_mod_down_model_equals_the_definition(oracle, qbits, pbits, flags):
-    primes, roots = _chain(oracle, N, qbits + pbits)
+    primes, roots = rs.chain(oracle, N, qbits + pbits)
     np_, nq = len(pbits), len(qbits)
     Q, P = km.prod(primes[:nq]), km.prod(primes[nq:])
     rng = random.Random(hash((tuple(qbits), tuple(pbits), flags)) & 0xFFFF)
@@ -74,14 +67,10 @@ def test_mod_down_model_equals_the_definition(oracle, qbits, pbits, flags):
             assert int(got[l][i]) == y % q, "limb %d, x = %d" % (l, x)
 
 
-UP_CHAINS = [([50, 50, 50, 50, 60, 60], 0, 2), ([60, 50, 50, 50, 50, 60, 60], 1, 3), ([50] * 6 + [60, 60], 6, 2), ([30, 52, 50, 60], 1, 1),
-             ([50] * 18, 1, 16)]
-
-
-@pytest.mark.parametrize("bits,first,count", UP_CHAINS, ids=["start", "middle", "end", "one-limb", "count16"])
+@pytest.mark.parametrize("bits,first,count", km.UP_CHAINS, ids=["start", "middle", "end", "one-limb", "count16"])
 @pytest.mark.parametrize("flags", [0, T])
 def test_mod_up_model_equals_the_definition(oracle, bits, first, count, flags):
-    primes, roots = _chain(oracle, N, bits)
+    primes, roots = rs.chain(oracle, N, bits)
     basis = primes[first:first + count]
     B = km.prod(basis)
     rng = random.Random(len(bits) * 31 + first + flags)
@@ -107,7 +96,7 @@ def test_mod_up_model_equals_the_definition(oracle, bits, first, count, flags):
 @pytest.mark.parametrize("bits", [[50, 50, 50, 52], [50, 50, 30], [50, 30, 60], [60, 50, 50, 50], [30, 50]])
 @pytest.mark.parametrize("flags", [0, F, T, T | F])
 def test_mod_down_with_one_p_prime_is_the_rescale(oracle, bits, flags):
-    primes, roots = _chain(oracle, N, bits)
+    primes, roots = rs.chain(oracle, N, bits)
     coef = [oracle.fill_uniform(2 * N, q, 70 + l) for l, q in enumerate(primes)]
     limbs = [oracle.ctx(N, q, w).fwd(c) for q, w, c in zip(primes, roots, coef)] if flags & T else coef
     got, t = km.mod_down(oracle, primes, roots, 1, limbs, N, flags)
@@ -124,16 +113,11 @@ def test_exports_the_four_symbols(lib):
 
 
 def test_key_switch_example_builds_against_the_public_header(lib):
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    exe = os.path.join(ROOT, "build", "rns_key_switch")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "rns_key_switch.c"), "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x",
-                           "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-    assert os.path.exists(exe)
+    assert os.path.exists(children.build_example(lib, "rns_key_switch", *children.STRICT))
 
 
 def expected_instances():
-    fwd = {"moddown_fwd_kernel<%s,%d,%d>" % (pol, logn, k) for pol, k, logn in km.launch_cases()}
+    fwd = rs.kernel_names("moddown_fwd_kernel", rs.fused_launch_cases())
     return fwd | {"moddown_coef_kernel", "bconv_kernel"}
 
 

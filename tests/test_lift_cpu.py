@@ -14,8 +14,9 @@ from math import prod
 import numpy as np
 import pytest
 
+import children
 import lift_model as lm
-import rescale_model as rm
+import rns_support as rs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_amd")
@@ -42,7 +43,7 @@ def test_delta_identity_of_the_host_constants(lib, chain):
     """floor((Q m + floor(t/2)) / t) = Delta m + floor((r m + floor(t/2)) / t) with Delta = floor(Q / t), r = Q mod t, and
     [Delta]_q = -r t^-1 mod q for every prime coprime to t: what host_lift.inc and lift_scaled compute, against the definition, the ties
     of even t included"""
-    primes, _ = rm.chain(lib, 16, CHAINS[chain])
+    primes, _ = rs.chain(lib, 16, CHAINS[chain])
     Q = prod(primes)
     rng = random.Random(len(primes))
     for t in lm.TS:
@@ -57,7 +58,7 @@ def test_delta_identity_of_the_host_constants(lib, chain):
 
 
 def test_corner_generator_builds_ties_and_boundaries(lib):
-    primes, _ = rm.chain(lib, 16, [50] * 3)
+    primes, _ = rs.chain(lib, 16, [50] * 3)
     Q = prod(primes)
     for t in (256, 1 << 32, 65537, 10 ** 18 + 9):
         r = Q % t
@@ -73,13 +74,7 @@ def test_corner_generator_builds_ties_and_boundaries(lib):
 
 @pytest.fixture(scope="module")
 def host_check():
-    exe = os.path.join(ROOT, "build", "lift_host_check")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    # host code only, every sanitizer flag bound to the host side: nothing is built for the GPU
-    flags = "--cuda-host-only -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=all"
-    subprocess.check_call([hipcc] + flags.split() + ["-I" + CSRC, os.path.join(ROOT, "tests", "lift_host_check.cpp"), "-o", exe])
-    return exe
+    return children.build_host_check("lift_host_check")
 
 
 def _run(host_check, tmp_path, mode, primes, t, scale, words):
@@ -98,7 +93,7 @@ def _run(host_check, tmp_path, mode, primes, t, scale, words):
 def test_host_statement_equals_the_definition(lib, host_check, tmp_path, chain, mode):
     """lift_word and lift_digit, compiled for the host with the sanitizers, for every t: the corner words and random draws, word for
     word the big-integer definition; the program itself compares the 128-by-64-bit quotient with the compiler's division"""
-    primes, _ = rm.chain(lib, 16, CHAINS[chain])
+    primes, _ = rs.chain(lib, 16, CHAINS[chain])
     rng = random.Random(len(primes) * 3 + (mode == lm.SCALED))
     for t in lm.TS:
         if mode == lm.SCALED and any(t % q == 0 for q in primes):
@@ -113,7 +108,7 @@ def test_host_statement_equals_the_definition(lib, host_check, tmp_path, chain, 
 
 def test_host_statement_stays_canonical_for_words_above_t(lib, host_check, tmp_path):
     """m >= t is the caller's error: the word is unspecified, but below q"""
-    primes, _ = rm.chain(lib, 16, [60, 30, 50])
+    primes, _ = rs.chain(lib, 16, [60, 30, 50])
     words = [(1 << 64) - 1, 1 << 63, (1 << 61) + 5, 65537, 65538]
     for mode in (0, 1):
         for t in (2, 65537, (1 << 61) - 1):
@@ -125,7 +120,7 @@ def test_host_statement_stays_canonical_for_words_above_t(lib, host_check, tmp_p
 @pytest.mark.parametrize("scale", [1.0, 2.0 ** 40, 1.0 / 3.0, 3.0, 2.0 ** -1074, -7.5])
 @pytest.mark.parametrize("chain", ["L1_30", "L3_mixed", "L16_60"])
 def test_host_double_equals_the_definition(lib, host_check, tmp_path, chain, scale):
-    primes, _ = rm.chain(lib, 16, CHAINS[chain])
+    primes, _ = rs.chain(lib, 16, CHAINS[chain])
     words = np.concatenate([lm.double_corners(), lm.random_plain(lm.DOUBLE, 200, 0, 5),
                             (np.random.default_rng(6).standard_normal(64) * 2.0 ** 120).view(np.uint64)])
     got = _run(host_check, tmp_path, 2, primes, 0, scale, words)
@@ -150,25 +145,18 @@ def test_header_declares_the_flags_and_the_option_as_c_and_cxx(lib):
                             ("NTT_LIFT_ACCUMULATE", 4, lib.LIFT_ACCUMULATE), ("NTT_OPT_LIFT_FUSED", 22, lib.OPT_LIFT_FUSED)):
         assert re.search(r"%s\s*=\s*%d\b" % (name, val), header) and mine == val, name
     assert (lm.SCALE, lm.TRANSFORMED, lm.ACCUMULATE) == (1, 2, 4)
-    for comp, std, lang in (("gcc", "-std=gnu11", "c"), ("g++", "-std=c++17", "c++")):
-        src = ('#include "ntt_mi355x.h"\nint main(void){return (NTT_LIFT_SCALE == 1 && NTT_LIFT_TRANSFORMED == 2 && NTT_LIFT_ACCUMULATE == 4 && '
-               "NTT_OPT_LIFT_FUSED == 22 && ntt_rns_from_plain_batch && ntt_rns_from_plain_batch_strided && "
-               "ntt_rns_from_double_batch && ntt_rns_from_double_batch_strided) ? 0 : 1;}\n")
-        subprocess.run([comp, std, "-Wall", "-Wextra", "-Werror", "-Wno-address", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), "-x", lang, "-"],
-                       input=src, text=True, check=True)
+    src = ('#include "ntt_mi355x.h"\nint main(void){return (NTT_LIFT_SCALE == 1 && NTT_LIFT_TRANSFORMED == 2 && NTT_LIFT_ACCUMULATE == 4 && '
+           "NTT_OPT_LIFT_FUSED == 22 && ntt_rns_from_plain_batch && ntt_rns_from_plain_batch_strided && "
+           "ntt_rns_from_double_batch && ntt_rns_from_double_batch_strided) ? 0 : 1;}\n")
+    children.syntax_check(src)
 
 
 def test_example_builds_against_the_public_header(lib):
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    exe = os.path.join(ROOT, "build", "rns_encrypt")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "rns_encrypt.c"), "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x",
-                           "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-    assert os.path.exists(exe)
+    assert os.path.exists(children.build_example(lib, "rns_encrypt", *children.STRICT))
 
 
 def expected_instances():
-    return {"lift_fwd_kernel<%s,%d,%d>" % (pol, logn, k) for pol, k, logn in lm.launch_cases()} | {"lift_coef_kernel"}
+    return rs.kernel_names("lift_fwd_kernel", rs.fused_launch_cases()) | {"lift_coef_kernel"}
 
 
 def lift_kernels():

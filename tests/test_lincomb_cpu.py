@@ -13,6 +13,7 @@ import sys
 import numpy as np
 import pytest
 
+import children
 import galois_model as gm
 import lincomb_model as lm
 
@@ -109,13 +110,7 @@ def test_the_two_routes_of_the_model_agree(oracle, flags):
 
 @pytest.fixture(scope="module")
 def host_check():
-    exe = os.path.join(ROOT, "build", "lincomb_host_check")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    # host code only, every sanitizer flag bound to the host side: nothing is built for the GPU
-    flags = "--cuda-host-only -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=all"
-    subprocess.check_call([hipcc] + flags.split() + ["-I" + CSRC, os.path.join(ROOT, "tests", "lincomb_host_check.cpp"), "-o", exe])
-    return exe
+    return children.build_host_check("lincomb_host_check")
 
 
 def _host_rows(host_check, tmp_path, primes, k, rows):
@@ -187,20 +182,13 @@ def test_header_declares_the_flags_as_c_and_cxx(lib):
     for name, val in (("NTT_LINCOMB_ACCUMULATE", 1), ("NTT_LINCOMB_M_BROADCAST", 2), ("NTT_LINCOMB_LAZY_IN", 4)):
         assert re.search(r"%s\s*=\s*%d\b" % (name, val), header)
     assert (lib.LINCOMB_ACCUMULATE, lib.LINCOMB_M_BROADCAST, lib.LINCOMB_LAZY_IN) == (1, 2, 4)
-    for comp, std, lang in (("gcc", "-std=gnu11", "c"), ("g++", "-std=c++17", "c++")):
-        src = ('#include "ntt_mi355x.h"\nint main(void){return (NTT_LINCOMB_ACCUMULATE == 1 && NTT_LINCOMB_M_BROADCAST == 2 && NTT_LINCOMB_LAZY_IN == 4 && '
-               "ntt_rns_lincomb_batch && ntt_rns_lincomb_batch_strided) ? 0 : 1;}\n")
-        subprocess.run([comp, std, "-Wall", "-Wextra", "-Werror", "-Wno-address", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), "-x", lang, "-"],
-                       input=src, text=True, check=True)
+    src = ('#include "ntt_mi355x.h"\nint main(void){return (NTT_LINCOMB_ACCUMULATE == 1 && NTT_LINCOMB_M_BROADCAST == 2 && NTT_LINCOMB_LAZY_IN == 4 && '
+           "ntt_rns_lincomb_batch && ntt_rns_lincomb_batch_strided) ? 0 : 1;}\n")
+    children.syntax_check(src)
 
 
 def test_example_builds_against_the_public_header(lib):
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    exe = os.path.join(ROOT, "build", "rns_lincomb")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "rns_lincomb.c"), "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x",
-                           "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-    assert os.path.exists(exe)
+    assert os.path.exists(children.build_example(lib, "rns_lincomb", *children.STRICT))
 
 
 def test_new_object_holds_one_kernel_without_spills():

@@ -1,6 +1,6 @@
 """CPU: ntt_rns_mod_up_mul_batch without a GPU -- the model of tests/modup_mul_model.py against the definition over the CRT (lift the
 digit to x in [0, B), extend as x + u B with 0 <= u < count, reduce mod every prime, forward transform, times the key, plus the
-accumulator) on the chains of test_keyswitch_cpu.UP_CHAINS; the exported symbols; the plain-C example against the public header
+accumulator) on the chains of keyswitch_model.UP_CHAINS; the exported symbols; the plain-C example against the public header
 alone; and the kernels of the new translation units (modup_mul_*.o): exactly the 36 expected instances, none spilling vector
 registers or using scratch."""
 import glob
@@ -12,9 +12,10 @@ import sys
 import numpy as np
 import pytest
 
+import children
 import keyswitch_model as km
 import modup_mul_model as mm
-import test_keyswitch_cpu as tkc
+import rns_support as rs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_amd", "csrc")
@@ -23,11 +24,11 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 N = 64
 
 
-@pytest.mark.parametrize("bits,first,count", tkc.UP_CHAINS, ids=["start", "middle", "end", "one-limb", "count16"])
+@pytest.mark.parametrize("bits,first,count", km.UP_CHAINS, ids=["start", "middle", "end", "one-limb", "count16"])
 @pytest.mark.parametrize("flags", [0, mm.ACCUMULATE, mm.BROADCAST, mm.BROADCAST | mm.ACCUMULATE | mm.LAZY_IN])
 def test_model_equals_the_definition(oracle, bits, first, count, flags):
     batch = 2
-    primes, roots = tkc._chain(oracle, N, bits)
+    primes, roots = rs.chain(oracle, N, bits)
     basis = primes[first:first + count]
     B = km.prod(basis)
     rng = random.Random(len(bits) * 37 + first + flags)
@@ -56,7 +57,7 @@ def test_model_equals_the_definition(oracle, bits, first, count, flags):
 def test_digit_of_largest_words_is_the_largest_sum(oracle):
     """every digit word b_i - 1: z_i = [(b_i - 1) b^_i^-1]_{b_i}; the model still agrees with the integers"""
     bits, first, count = [50] * 18, 1, 16
-    primes, roots = tkc._chain(oracle, N, bits)
+    primes, roots = rs.chain(oracle, N, bits)
     digit, key, acc = mm.operands(oracle, primes, N, 1, first, count, 0, seed=3, digit_max=True)
     basis = primes[first:first + count]
     assert all(int(d[0]) == b - 1 and int(d[-1]) == b - 1 for d, b in zip(digit, basis))
@@ -74,16 +75,11 @@ def test_exports_the_two_symbols(lib):
 
 
 def test_fused_example_builds_against_the_public_header(lib):
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    exe = os.path.join(ROOT, "build", "rns_key_switch_fused")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "rns_key_switch_fused.c"), "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x",
-                           "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-    assert os.path.exists(exe)
+    assert os.path.exists(children.build_example(lib, "rns_key_switch_fused", *children.STRICT))
 
 
 def expected_instances():
-    return {"modup_mul_kernel<%s,%d,%d>" % (pol, logn, k) for pol, k, logn in mm.launch_cases()}
+    return rs.kernel_names("modup_mul_kernel", rs.fused_launch_cases())
 
 
 def modup_mul_kernels():

@@ -10,21 +10,14 @@ import sys
 import numpy as np
 import pytest
 
+import children
 import rescale_model as rm
+import rns_support as rs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_amd", "csrc")
 LIB = os.path.join(ROOT, "optimized-number-theoretic-transform-implementations_amd", "libntt_mi355x.so")
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-
-def _chain(orc, n, bits_list):
-    seen, primes = {}, []
-    for b in bits_list:
-        k = seen.get(b, 0)
-        primes.append(orc.find_prime(b, n, k))
-        seen[b] = k + 1
-    return primes, [orc.min_root(q, n) for q in primes]
 
 
 def _edge_values(primes, count, rng):
@@ -48,7 +41,7 @@ CHAINS = [([50, 50, 50], 52), ([50, 50], 30), ([50, 30], 60), ([60, 50, 50], 50)
 @pytest.mark.parametrize("flags", [0, rm.FLOOR, rm.TRANSFORMED, rm.TRANSFORMED | rm.FLOOR])
 def test_model_equals_the_crt_definition(oracle, kept, dropped, flags):
     n = 64
-    primes, roots = _chain(oracle, n, kept + [dropped])
+    primes, roots = rs.chain(oracle, n, kept + [dropped])
     rng = random.Random(hash((tuple(kept), dropped, flags)) & 0xFFFF)
     xs = _edge_values(primes, 2 * n, rng)
     coef = rm.residues(xs, primes)
@@ -72,7 +65,7 @@ def test_model_equals_the_crt_definition(oracle, kept, dropped, flags):
 def test_two_rescales_in_a_row(oracle):
     """rescale by q_L, then by q_{L-1}: round(round(x / q_L) / q_{L-1})"""
     n = 64
-    primes, roots = _chain(oracle, n, [60, 50, 50, 50])
+    primes, roots = rs.chain(oracle, n, [60, 50, 50, 50])
     rng = random.Random(7)
     Q = 1
     for q in primes:
@@ -97,16 +90,11 @@ def test_exports_both_symbols(lib):
 
 
 def test_rescale_example_builds_against_the_public_header(lib):
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    exe = os.path.join(ROOT, "build", "rns_rescale")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "rns_rescale.c"), "-L" + os.path.dirname(lib.LIB_PATH), "-lntt_mi355x",
-                           "-Wl,-rpath," + os.path.dirname(lib.LIB_PATH), "-o", exe])
-    assert os.path.exists(exe)
+    assert os.path.exists(children.build_example(lib, "rns_rescale", *children.STRICT))
 
 
 def expected_instances():
-    fwd = {"rescale_fwd_kernel<%s,%d,%d>" % (pol, logn, k) for pol, k, logn in rm.launch_cases()}
+    fwd = rs.kernel_names("rescale_fwd_kernel", rs.fused_launch_cases())
     return fwd | {"rescale_coef_kernel"}
 
 
