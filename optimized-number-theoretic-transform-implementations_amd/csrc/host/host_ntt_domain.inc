@@ -6,20 +6,42 @@
 /* ------------------------------------------------------------------ */
 static hipError_t dispatch_dot(const ntt_plan *p, const DotArgs &da)
 {
-  if(p->arith == NTT_ARITH_U64) {
-    switch(eff_int_cls(p)) { /* (same tables; the wide policy's stages around its Barrett products) */
-      case 3: return launch_dot<ArithU64X<3>, 3>(da);
-      case 1: return launch_dot<ArithU64X<1>, 1>(da);
-      case 0: return launch_dot<ArithU64X<0>, 0>(da);
-      default: return launch_dot<ArithU64, 0>(da);
-    }
-  }
-  switch(eff_kcls(p)) {
-    case kWideClass: return launch_dot<ArithF64W, 0>(da);
-    case 18: return launch_dot<ArithF64, 18>(da);
-    case 1: return launch_dot<ArithF64, 1>(da);
-    default: return launch_dot<ArithF64, 0>(da);
-  }
+  return with_class(p, [&](auto k) { return launch_dot<typename decltype(k)::A, decltype(k)::KSH>(da); });
+}
+static hipError_t dispatch_mul(const ntt_plan *p, const MulArgs &ma)
+{
+  return with_class(p, [&](auto k) { return launch_fwd_mul<typename decltype(k)::A, decltype(k)::KSH>(ma); });
+}
+
+/* The two records of the NTT-domain products over ls, operands and operand flags (NTT_MUL_*) in place; b_limb_stride: words
+ * between the limbs of a b operand (0: one limb).  What a route adds: block_log and oversub, set_team, set_ptrs. */
+static DotArgs dot_args(const ntt_plan *p, const LimbSet &ls, uint64_t *out, int k, const uint64_t *const *a, const uint64_t *const *b, uint64_t batch,
+                        unsigned flags, uint64_t b_limb_stride, void *stream)
+{
+  DotArgs da{};
+  launch_common(da, p, ls, batch, stream);
+  da.out           = out;
+  da.a             = a;
+  da.b             = b;
+  da.npairs        = k;
+  da.lazy_in       = (flags & NTT_MUL_LAZY_IN) != 0;
+  da.b_bcast       = (flags & NTT_MUL_B_BROADCAST) != 0;
+  da.b_limb_stride = b_limb_stride;
+  return da;
+}
+static MulArgs mul_args(const ntt_plan *p, const LimbSet &ls, uint64_t *out, uint64_t *a, const uint64_t *b, uint64_t batch, unsigned flags,
+                        uint64_t b_limb_stride, void *stream)
+{
+  MulArgs ma{};
+  launch_common(ma, p, ls, batch, stream);
+  ma.a             = a;
+  ma.b             = b;
+  ma.out           = out;
+  ma.lazy_in       = (flags & NTT_MUL_LAZY_IN) != 0;
+  ma.b_bcast       = (flags & NTT_MUL_B_BROADCAST) != 0;
+  ma.accumulate    = (flags & NTT_MUL_ACCUMULATE) != 0;
+  ma.b_limb_stride = b_limb_stride;
+  return ma;
 }
 
 /* plans the fused kernel serves: the radix-2 policies on blocks of 2^6 points and more */
@@ -78,118 +100,49 @@ static int inv_dot(const ntt_plan *p, uint64_t *d_c, int k, const uint64_t *cons
   USE_DEVICE(p->device);
   if(!dot_kernel_applies(p) || (ls.n > 1 && !multi_limb_plan(p))) {
     if(ls.n != 1) return fail(NTT_ERR_UNSUPPORTED, "one launch over several limbs needs the FP64 policies or the wide integer policy");
-    const uint64_t n  = batch * p->N;
-    const dim3     g(grid_pw(n, p->max_grid)), t(256);
-    hipStream_t    st = (hipStream_t)stream;
-    const PwLayout lay{(uint32_t)p->m, poly_words(p, ls), bcast ? 0 : poly_words(p, ls)};
     for(int i = 0; i < k; i++) {
-#define NTT_PW_ACC(A, CONSTS)                                                                                              \
-  do {                                                                                                                     \
-    if(lazy) {                                                                                                             \
-      if(i) hipLaunchKernelGGL((pointwise_acc_kernel<A, true, true>), g, t, 0, st, d_c, a[i], b[i], n, lay, p->q, CONSTS);  \
-      else hipLaunchKernelGGL((pointwise_acc_kernel<A, true, false>), g, t, 0, st, d_c, a[i], b[i], n, lay, p->q, CONSTS);  \
-    } else {                                                                                                               \
-      if(i) hipLaunchKernelGGL((pointwise_acc_kernel<A, false, true>), g, t, 0, st, d_c, a[i], b[i], n, lay, p->q, CONSTS); \
-      else hipLaunchKernelGGL((pointwise_acc_kernel<A, false, false>), g, t, 0, st, d_c, a[i], b[i], n, lay, p->q, CONSTS); \
-    }                                                                                                                      \
-  } while(0)
-      if(p->arith == NTT_ARITH_F64) NTT_PW_ACC(ArithF64, p->cf);
-      else NTT_PW_ACC(ArithU64, p->cu);
-#undef NTT_PW_ACC
-      HIP_TRY(hipGetLastError());
+      int rc = pointwise_acc(p, d_c, a[i], b[i], batch, ls, lazy, i > 0, bcast, stream);
+      if(rc) return rc;
     }
     return run_transform(p, d_c, batch, true, false, stream, false, &ls);
   }
+  const uint64_t bls = ls.n > 1 ? b_limb_stride : 0;
   /* N = 2^15..2^17, batches that keep the eight queues busy: the blocks with the products AND the inverse's column stages as
    * the items of ONE launch (team_dot_kernel) instead of two launches per 128 / 256 MiB chunk.  NTT_OPT_XCD_LOCAL 1 / 0 forces
    * either form; while a stream is being captured without a control block of its own the per-chunk launches serve (team_buffer). */
-  {
-    const bool int_wide = p->arith == NTT_ARITH_U64 && p->int_cls >= 0;
-    const uint64_t polys = batch * (uint64_t)ls.n;
-    bool team = (p->arith == NTT_ARITH_F64 || int_wide) && p->m >= kTeamBlock + 3 && p->m <= kTeamBlock + 5 && !p->block_log && polys >= 64 &&
-                polys < (1ull << 29) && ls.n <= kMaxLimbs;
-    if(team && p->xcd_local >= 0) team = p->xcd_local == 1;
-    else if(team) team = dot_team_pays(p, polys, k, bcast);
-    void *ctl = nullptr;
-    if(team) {
-      int rc = team_buffer(p, stream, polys, &ctl);
-      if(rc) return rc;
-    }
-    if(ctl) {
-      DotArgs da{};
-      da.out           = d_c;
-      da.a             = a;
-      da.b             = b;
-      da.npairs        = k;
-      da.lazy_in       = lazy;
-      da.b_bcast       = bcast;
-      da.limbs         = ls.d;
-      da.nlimbs        = ls.n;
-      da.limb_stride   = ls.stride;
-      da.poly_stride   = ls.pstride;
-      da.b_limb_stride = ls.n > 1 ? b_limb_stride : 0;
-      da.batch         = batch;
-      da.logn          = (uint32_t)p->m;
-      da.block_log     = (uint32_t)kTeamBlock;
-      da.max_grid      = p->max_grid;
-      da.num_cus       = p->num_cus;
-      da.team_ctl      = ctl;
-      da.team_lag      = p->team_lag ? p->team_lag : dot_team_lag(p, k, bcast);
-      da.team_wpc      = p->team_wpc;
-      da.stream        = (hipStream_t)stream;
-      hipError_t e = dispatch_dot(p, da);
-      if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-      return NTT_OK;
-    }
+  const uint64_t polys = batch * (uint64_t)ls.n;
+  void *         ctl   = nullptr;
+  if(team_pays(p, polys, ls.n, [&] { return dot_team_pays(p, polys, k, bcast); })) {
+    int rc = team_buffer(p, stream, polys, &ctl);
+    if(rc) return rc;
   }
-  const int      pblk  = p->m > kFusedMax ? (p->block_log ? p->block_log : multi_pass_block(p->m, true, p->arith == NTT_ARITH_F64)) : p->m;
-  const PassList L     = make_passes(p->m, false, pblk);
-  uint64_t       chunk = batch;
-  if(L.n > 1) {
-    /* the chunk is what must still be in the Infinity Cache when the column pass reads c back; here the operands stream
-     * through that cache as well (two to 2k times the chunk), so a smaller chunk than the transforms' 256 MiB pays at
-     * N = 2^15 and 2^16 (measured: 128 MiB +4..7 %, 64 MiB the same for k = 3 and slower for k = 1, none at 2^17;
-     * profiles/r04/dot_chunk.txt).  An explicit NTT_OPT_CHUNK_MIB is honoured as given. */
-    const uint64_t mib = p->chunk_mib == 256 && p->m <= kFusedMax + 2 ? 128 : (uint64_t)p->chunk_mib;
-    chunk              = (mib << 20) / (p->N * sizeof(uint64_t) * (uint64_t)ls.n);
-    if(chunk < 1) chunk = 1;
-    if(chunk > batch) chunk = batch;
+  if(ctl) {
+    DotArgs da = dot_args(p, ls, d_c, k, a, b, batch, flags, bls, stream);
+    set_team(da, p, ctl, dot_team_lag(p, k, bcast));
+    return launched(dispatch_dot(p, da));
   }
-  const uint64_t *ca[kMaxDot], *cb[kMaxDot];
-  for(uint64_t first = 0; first < batch; first += chunk) {
-    const uint64_t nb  = batch - first < chunk ? batch - first : chunk;
-    const uint64_t off = first * poly_words(p, ls);
+  const int      pblk = p->m > kFusedMax ? (p->block_log ? p->block_log : multi_pass_block(p->m, true, p->arith == NTT_ARITH_F64)) : p->m;
+  const PassList L    = make_passes(p->m, false, pblk);
+  /* the chunk is what must still be in the Infinity Cache when the column pass reads c back; here the operands stream
+   * through that cache as well (two to 2k times the chunk), so a smaller chunk than the transforms' 256 MiB pays at
+   * N = 2^15 and 2^16 (measured: 128 MiB +4..7 %, 64 MiB the same for k = 3 and slower for k = 1, none at 2^17;
+   * profiles/r04/dot_chunk.txt).  An explicit NTT_OPT_CHUNK_MIB is honoured as given. */
+  const uint64_t mib = p->chunk_mib == 256 && p->m <= kFusedMax + 2 ? 128 : (uint64_t)p->chunk_mib;
+  return for_chunks(p, ls, batch, mib, L.n, [&](uint64_t, uint64_t nb, uint64_t off) -> int {
+    const uint64_t *ca[kMaxDot], *cb[kMaxDot];
     for(int i = 0; i < k; i++) {
       ca[i] = a[i] + off;
       cb[i] = bcast ? b[i] : b[i] + off;
     }
-    DotArgs da{};
-    da.out           = d_c + off;
-    da.a             = ca;
-    da.b             = cb;
-    da.npairs        = k;
-    da.lazy_in       = lazy;
-    da.b_bcast       = bcast;
-    da.limbs         = ls.d;
-    da.nlimbs        = ls.n;
-    da.limb_stride   = ls.stride;
-    da.poly_stride   = ls.pstride;
-    da.b_limb_stride = ls.n > 1 ? b_limb_stride : 0;
-    da.batch         = nb;
-    da.logn          = (uint32_t)p->m;
-    da.block_log     = (uint32_t)pblk;
-    da.max_grid      = p->max_grid;
-    da.num_cus       = p->num_cus;
-    da.oversub       = p->block_oversub;
-    da.stream        = (hipStream_t)stream;
-    hipError_t e = dispatch_dot(p, da);
-    if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    for(int j = L.n - 2; j >= 0; j--) { /* the inverse's column passes on c; the last one ends the transform (N^-1) */
-      int rc = launch_one_pass(p, L.p[j], d_c + off, nb, true, false, false, j == 0, stream, ls);
-      if(rc) return rc;
+    DotArgs da   = dot_args(p, ls, d_c + off, k, ca, cb, nb, flags, bls, stream);
+    da.block_log = (uint32_t)pblk;
+    da.oversub   = p->block_oversub;
+    int rc       = launched(dispatch_dot(p, da));
+    for(int j = L.n - 2; !rc && j >= 0; j--) { /* the inverse's column passes on c; the last one ends the transform (N^-1) */
+      rc = launch_one_pass(p, L.p[j], d_c + off, nb, true, false, false, j == 0, stream, ls);
     }
-  }
-  return NTT_OK;
+    return rc;
+  });
 }
 
 extern "C" int ntt_inv_dot_batch(const ntt_plan *p, uint64_t *d_c, int k, const uint64_t *const *d_ahat,
@@ -275,143 +228,44 @@ static int fwd_mul(const ntt_plan *p, uint64_t *d_c, uint64_t *d_a, const uint64
     if(ls.n != 1) return fail(NTT_ERR_UNSUPPORTED, "one launch over several limbs needs the FP64 policies or the wide integer policy");
     int rc = run_transform(p, d_a, batch, false, false, stream, false, &ls);
     if(rc) return rc;
-    const uint64_t n  = batch * p->N;
-    const dim3     g(grid_pw(n, p->max_grid)), t(256);
-    hipStream_t    st = (hipStream_t)stream;
-    const PwLayout lay{(uint32_t)p->m, poly_words(p, ls), bcast ? 0 : poly_words(p, ls)};
-#define NTT_PW_MUL(A, CONSTS)                                                                                              \
-  do {                                                                                                                     \
-    if(lazy) {                                                                                                             \
-      if(acc) hipLaunchKernelGGL((pointwise_acc_kernel<A, true, true>), g, t, 0, st, d_c, d_a, d_bhat, n, lay, p->q, CONSTS); \
-      else hipLaunchKernelGGL((pointwise_acc_kernel<A, true, false>), g, t, 0, st, d_c, d_a, d_bhat, n, lay, p->q, CONSTS);  \
-    } else {                                                                                                               \
-      if(acc) hipLaunchKernelGGL((pointwise_acc_kernel<A, false, true>), g, t, 0, st, d_c, d_a, d_bhat, n, lay, p->q, CONSTS); \
-      else hipLaunchKernelGGL((pointwise_acc_kernel<A, false, false>), g, t, 0, st, d_c, d_a, d_bhat, n, lay, p->q, CONSTS); \
-    }                                                                                                                      \
-  } while(0)
-    if(p->arith == NTT_ARITH_F64) NTT_PW_MUL(ArithF64, p->cf);
-    else NTT_PW_MUL(ArithU64, p->cu);
-#undef NTT_PW_MUL
-    HIP_TRY(hipGetLastError());
-    return NTT_OK;
+    return pointwise_acc(p, d_c, d_a, d_bhat, batch, ls, lazy, acc, bcast, stream);
   }
-  const int      pblk  = p->m > kFusedMax ? (p->block_log ? p->block_log : multi_pass_block(p->m, false, p->arith == NTT_ARITH_F64)) : p->m;
-  const PassList L     = make_passes(p->m, false, pblk);
-  uint64_t       chunk = batch;
-  if(L.n > 1) {
-    chunk = ((uint64_t)p->chunk_mib << 20) / (p->N * sizeof(uint64_t) * (uint64_t)ls.n);
-    if(chunk < 1) chunk = 1;
-    if(chunk > batch) chunk = batch;
-  }
-  const int ic = eff_int_cls(p), kc = eff_kcls(p);
-  const auto dispatch = [&](const MulArgs &ma) {
-    return p->arith == NTT_ARITH_U64 ? (ic == 3   ? launch_fwd_mul<ArithU64X<3>, 3>(ma)
-                                        : ic == 1 ? launch_fwd_mul<ArithU64X<1>, 1>(ma)
-                                        : ic == 0 ? launch_fwd_mul<ArithU64X<0>, 0>(ma)
-                                                  : launch_fwd_mul<ArithU64, 0>(ma))
-           : kc == kWideClass        ? launch_fwd_mul<ArithF64W, 0>(ma)
-           : kc == 18                ? launch_fwd_mul<ArithF64, 18>(ma)
-           : kc == 1                 ? launch_fwd_mul<ArithF64, 1>(ma)
-                                     : launch_fwd_mul<ArithF64, 0>(ma);
-  };
+  const uint64_t bls = ls.n > 1 ? b_limb_stride : 0;
   /* N = 2^15, FP64 policies: the one-pass transform with the product at its output (onepass_mul_kernel) -- a is left as it was.
-   * Same choice as the plain transform's (NTT_OPT_ONE_PASS; -1: batches that give every second CU a polynomial). */
+   * Same choice as the plain transform's (NTT_OPT_ONE_PASS; -1: batches that give every second CU a polynomial).  (The record names
+   * no block size and no oversubscription.) */
   if(p->m == kFusedMax + 1 && p->arith == NTT_ARITH_F64 && !p->generic && ls.n <= kMaxLimbs && !ls.ptab &&
      one_pass_pays(p, batch * (uint64_t)ls.n)) {
-    MulArgs ma{};
-    ma.a             = d_a;
-    ma.b             = d_bhat;
-    ma.out           = d_c;
-    ma.lazy_in       = lazy;
-    ma.b_bcast       = bcast;
-    ma.accumulate    = acc;
-    ma.limbs         = ls.d;
-    ma.nlimbs        = ls.n;
-    ma.limb_stride   = ls.stride;
-    ma.poly_stride   = ls.pstride;
-    ma.b_limb_stride = ls.n > 1 ? b_limb_stride : 0;
-    ma.batch         = batch;
-    ma.logn          = (uint32_t)p->m;
-    ma.max_grid      = p->max_grid;
-    ma.num_cus       = p->num_cus;
-    ma.one_pass      = 1;
-    ma.stream        = (hipStream_t)stream;
-    hipError_t e = dispatch(ma);
-    if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return NTT_OK;
+    MulArgs ma  = mul_args(p, ls, d_c, d_a, d_bhat, batch, flags, bls, stream);
+    ma.one_pass = 1;
+    return launched(dispatch_mul(p, ma));
   }
   /* N = 2^15..2^17, batches that keep the eight queues busy: the forward column stages of a and the blocks with the product as
    * the items of ONE launch (team_mul_kernel) instead of two launches per chunk.  NTT_OPT_XCD_LOCAL 1 / 0 forces either form; a
    * stream being captured without a control block of its own takes the per-chunk launches (team_buffer). */
-  {
-    const bool     int_wide = p->arith == NTT_ARITH_U64 && p->int_cls >= 0;
-    const uint64_t polys    = batch * (uint64_t)ls.n;
-    bool team = (p->arith == NTT_ARITH_F64 || int_wide) && p->m >= kTeamBlock + 3 && p->m <= kTeamBlock + 5 && !p->block_log && polys >= 64 &&
-                polys < (1ull << 29) && ls.n <= kMaxLimbs;
-    if(team && p->xcd_local >= 0) team = p->xcd_local == 1;
-    else if(team) team = mul_team_pays(p, polys, bcast, acc);
-    void *ctl = nullptr;
-    if(team) {
-      int rc = team_buffer(p, stream, polys, &ctl);
-      if(rc) return rc;
-    }
-    if(ctl) {
-      MulArgs ma{};
-      ma.a             = d_a;
-      ma.b             = d_bhat;
-      ma.out           = d_c;
-      ma.lazy_in       = lazy;
-      ma.b_bcast       = bcast;
-      ma.accumulate    = acc;
-      ma.limbs         = ls.d;
-      ma.nlimbs        = ls.n;
-      ma.limb_stride   = ls.stride;
-      ma.poly_stride   = ls.pstride;
-      ma.b_limb_stride = ls.n > 1 ? b_limb_stride : 0;
-      ma.batch         = batch;
-      ma.logn          = (uint32_t)p->m;
-      ma.block_log     = (uint32_t)kTeamBlock;
-      ma.max_grid      = p->max_grid;
-      ma.num_cus       = p->num_cus;
-      ma.team_ctl      = ctl;
-      ma.team_lag      = p->team_lag ? p->team_lag : mul_team_lag(p);
-      ma.team_wpc      = p->team_wpc;
-      ma.stream        = (hipStream_t)stream;
-      hipError_t e = dispatch(ma);
-      if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-      return NTT_OK;
-    }
+  const uint64_t polys = batch * (uint64_t)ls.n;
+  void *         ctl   = nullptr;
+  if(team_pays(p, polys, ls.n, [&] { return mul_team_pays(p, polys, bcast, acc); })) {
+    int rc = team_buffer(p, stream, polys, &ctl);
+    if(rc) return rc;
   }
-  for(uint64_t first = 0; first < batch; first += chunk) {
-    const uint64_t nb  = batch - first < chunk ? batch - first : chunk;
-    const uint64_t off = first * poly_words(p, ls);
+  if(ctl) {
+    MulArgs ma = mul_args(p, ls, d_c, d_a, d_bhat, batch, flags, bls, stream);
+    set_team(ma, p, ctl, mul_team_lag(p));
+    return launched(dispatch_mul(p, ma));
+  }
+  const int      pblk = p->m > kFusedMax ? (p->block_log ? p->block_log : multi_pass_block(p->m, false, p->arith == NTT_ARITH_F64)) : p->m;
+  const PassList L    = make_passes(p->m, false, pblk);
+  return for_chunks(p, ls, batch, (uint64_t)p->chunk_mib, L.n, [&](uint64_t, uint64_t nb, uint64_t off) -> int {
     for(int j = 0; j + 1 < L.n; j++) { /* forward column passes of a (every pass but the last, which is the block pass) */
       int rc = launch_one_pass(p, L.p[j], d_a + off, nb, false, false, false, false, stream, ls);
       if(rc) return rc;
     }
-    MulArgs ma{};
-    ma.a             = d_a + off;
-    ma.b             = bcast ? d_bhat : d_bhat + off;
-    ma.out           = d_c + off;
-    ma.lazy_in       = lazy;
-    ma.b_bcast       = bcast;
-    ma.accumulate    = acc;
-    ma.limbs         = ls.d;
-    ma.nlimbs        = ls.n;
-    ma.limb_stride   = ls.stride;
-    ma.poly_stride   = ls.pstride;
-    ma.b_limb_stride = ls.n > 1 ? b_limb_stride : 0;
-    ma.batch         = nb;
-    ma.logn          = (uint32_t)p->m;
-    ma.block_log     = (uint32_t)pblk;
-    ma.max_grid      = p->max_grid;
-    ma.num_cus       = p->num_cus;
-    ma.oversub       = p->block_oversub;
-    ma.stream        = (hipStream_t)stream;
-    hipError_t e = dispatch(ma);
-    if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-  }
-  return NTT_OK;
+    MulArgs ma   = mul_args(p, ls, d_c + off, d_a + off, bcast ? d_bhat : d_bhat + off, nb, flags, bls, stream);
+    ma.block_log = (uint32_t)pblk;
+    ma.oversub   = p->block_oversub;
+    return launched(dispatch_mul(p, ma));
+  });
 }
 
 extern "C" int ntt_fwd_mul_batch(const ntt_plan *p, uint64_t *d_c, uint64_t *d_a, const uint64_t *d_bhat, uint64_t batch,
@@ -423,22 +277,15 @@ extern "C" int ntt_fwd_mul_batch(const ntt_plan *p, uint64_t *d_c, uint64_t *d_a
 static int rns_fwd_mul(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, uint64_t *d_a, const uint64_t *d_bhat, uint64_t batch, unsigned flags,
                        void *stream, const Layout &lay)
 {
-  int rc = rns_check(nlimbs, plans);
-  if(rc || batch == 0) return rc;
-  if(!d_c || !d_a || !d_bhat) return fail(NTT_ERR_ARG, "null argument"); /* (before any limb offset is added) */
-  rc = layout_check(plans[0]->N, nlimbs, batch, lay);
-  if(rc) return rc;
-  const uint64_t bslab = (flags & NTT_MUL_B_BROADCAST) ? plans[0]->N : lay.limb; /* a broadcast operand is [limb][N] */
-  return rns_for_runs(
-    nlimbs, plans, lay, [&](const ntt_plan *p, int) { return rns_one_launch_pays(p, batch) && dot_kernel_applies(p); },
-    [&](int first, const LimbSet &ls) {
-      return fwd_mul(plans[first], d_c + (uint64_t)first * lay.limb, d_a + (uint64_t)first * lay.limb, d_bhat + (uint64_t)first * bslab, batch, flags,
-                     stream, &ls, bslab);
-    },
-    [&](int l) {
-      const LimbSet own = own_set(plans[l], lay);
-      return fwd_mul(plans[l], d_c + (uint64_t)l * lay.limb, d_a + (uint64_t)l * lay.limb, d_bhat + (uint64_t)l * bslab, batch, flags, stream, &own);
-    });
+  const auto call = [&](int first, const LimbSet &ls, bool run) {
+    const uint64_t bslab = b_slab(plans, lay, flags);
+    return fwd_mul(plans[first], d_c + (uint64_t)first * lay.limb, d_a + (uint64_t)first * lay.limb, d_bhat + (uint64_t)first * bslab, batch, flags, stream,
+                   &ls, run ? bslab : 0);
+  };
+  return rns_slab_runs(
+    nlimbs, plans, batch, lay, [&] { return all_given(d_c && d_a && d_bhat); },
+    [&](const ntt_plan *p, int) { return rns_one_launch_pays(p, batch) && dot_kernel_applies(p); },
+    [&](int first, const LimbSet &ls) { return call(first, ls, true); }, [&](int l) { return call(l, own_set(plans[l], lay), false); });
 }
 
 extern "C" int ntt_rns_fwd_mul_batch(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, uint64_t *d_a, const uint64_t *d_bhat,
@@ -456,17 +303,16 @@ extern "C" int ntt_rns_fwd_mul_batch_strided(int nlimbs, ntt_plan *const *plans,
 static int rns_inv_dot(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, int k, const uint64_t *const *d_ahat, const uint64_t *const *d_bhat,
                        uint64_t batch, unsigned flags, void *stream, const Layout &lay)
 {
-  int rc = rns_check(nlimbs, plans);
-  if(rc || batch == 0) return rc;
-  if(k < 1 || k > kMaxDot || !d_ahat || !d_bhat) return fail(NTT_ERR_ARG, "number of operand pairs must be 1 .. 32");
-  if(!d_c) return fail(NTT_ERR_ARG, "null argument");
-  for(int i = 0; i < k; i++) {
-    if(!d_ahat[i] || !d_bhat[i]) return fail(NTT_ERR_ARG, "null operand"); /* (before any limb offset is added) */
-  }
-  rc = layout_check(plans[0]->N, nlimbs, batch, lay);
-  if(rc) return rc;
-  const uint64_t bslab = (flags & NTT_MUL_B_BROADCAST) ? plans[0]->N : lay.limb; /* a broadcast operand is [limb][N] */
-  auto call = [&](int first, const LimbSet &ls, bool run) {
+  const auto operands = [&]() -> int {
+    if(k < 1 || k > kMaxDot || !d_ahat || !d_bhat) return fail(NTT_ERR_ARG, "number of operand pairs must be 1 .. 32");
+    if(!d_c) return fail(NTT_ERR_ARG, "null argument");
+    for(int i = 0; i < k; i++) {
+      if(!d_ahat[i] || !d_bhat[i]) return fail(NTT_ERR_ARG, "null operand");
+    }
+    return NTT_OK;
+  };
+  const auto call = [&](int first, const LimbSet &ls, bool run) {
+    const uint64_t  bslab = b_slab(plans, lay, flags);
     const uint64_t *la[kMaxDot], *lb[kMaxDot];
     for(int i = 0; i < k; i++) {
       la[i] = d_ahat[i] + (uint64_t)first * lay.limb;
@@ -474,8 +320,8 @@ static int rns_inv_dot(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, int k,
     }
     return inv_dot(plans[first], d_c + (uint64_t)first * lay.limb, k, la, lb, batch, flags, stream, &ls, run ? bslab : 0);
   };
-  return rns_for_runs(
-    nlimbs, plans, lay, [&](const ntt_plan *p, int) { return rns_one_launch_pays(p, batch) && dot_kernel_applies(p); },
+  return rns_slab_runs(
+    nlimbs, plans, batch, lay, operands, [&](const ntt_plan *p, int) { return rns_one_launch_pays(p, batch) && dot_kernel_applies(p); },
     [&](int first, const LimbSet &ls) { return call(first, ls, true); }, [&](int l) { return call(l, own_set(plans[l], lay), false); });
 }
 
@@ -495,15 +341,10 @@ extern "C" int ntt_rns_inv_dot_batch_strided(int nlimbs, ntt_plan *const *plans,
 static int rns_mul_transformed(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, uint64_t *d_a, const uint64_t *d_bhat, uint64_t batch,
                                unsigned flags, void *stream, const Layout &lay)
 {
-  int rc = rns_check(nlimbs, plans);
-  if(rc || batch == 0) return rc;
-  if(!d_c || !d_a || !d_bhat) return fail(NTT_ERR_ARG, "null argument"); /* (before any limb offset is added) */
-  rc = layout_check(plans[0]->N, nlimbs, batch, lay);
-  if(rc) return rc;
   /* one launch over a run: the fused product kernels (FP64 policies), or -- limbs of the wide integer policy -- the forward
    * transform and the products-inside-the-inverse launch, each over the whole run */
-  return rns_for_runs(
-    nlimbs, plans, lay,
+  return rns_slab_runs(
+    nlimbs, plans, batch, lay, [&] { return all_given(d_c && d_a && d_bhat); },
     [&](const ntt_plan *p, int) {
       const bool int_set = p->arith == NTT_ARITH_U64 && dot_kernel_applies(p) && d_a != d_bhat;
       return rns_one_launch_pays(p, batch) && (fused_product_applies(p, d_c, d_bhat, d_a, batch) || int_set);
@@ -791,12 +632,15 @@ static LimbSet with_table(const LimbSet &ls, const void *tab)
 static int ptrs_team(const ntt_plan *p, void *stream, uint64_t count, uint64_t entries, void **ctl)
 {
   *ctl = nullptr;
-  const bool int_wide = p->arith == NTT_ARITH_U64 && p->int_cls >= 0;
-  if(!(p->arith == NTT_ARITH_F64 || int_wide) || p->generic || !dot_kernel_applies(p) || p->m < kTeamBlock + 3 || p->m > kTeamBlock + 5 || p->block_log ||
-     count < 64 || count >= (1ull << 29) || p->xcd_local == 0) {
-    return NTT_OK;
-  }
+  /* (no measured rule here: the one-launch form wherever NTT_OPT_XCD_LOCAL does not switch it off) */
+  if(p->generic || !dot_kernel_applies(p) || !team_pays(p, count, 1, [] { return true; })) return NTT_OK;
   return team_buffer(p, stream, entries, ctl);
+}
+/* the limbs a *_ptrs_limb launch serves: a run's records, or p's own; hint: the typical spacing of the polynomials for the XCD-local
+ * launches' queue numbering (the limbs of a polynomial lie side by side) */
+static LimbSet ptrs_set(const ntt_plan *p, const LimbSet *run, bool hint)
+{
+  return LimbSet{run ? run->d : p->limbrec.data(), run ? run->n : 1, run ? run->stride : 0, run && hint ? (uint64_t)run->n * run->stride : 0};
 }
 
 /* the limbs of a run: blockIdx.y = the limb, its operands limb_stride (a broadcast b: b_limb_stride) words further behind every table
@@ -842,31 +686,21 @@ static int pointwise_ptrs(const ntt_plan *p, const uint64_t *const *ctab, const 
   uint64_t gx = grid_pw(n, p->max_grid);
   gx          = gx / (uint64_t)nrun > 0 ? gx / (uint64_t)nrun : 1;
   const dim3     g((unsigned)gx, (unsigned)nrun), t(256);
-  hipStream_t    st = (hipStream_t)stream;
   const uint64_t bls = bcast ? p->N : 0;
-#define NTT_PW_PTRS(A, CONSTS)                                                                                                                    \
-  do {                                                                                                                                            \
-    PwLimbs<A> L{};                                                                                                                               \
-    for(int l = 0; l < nrun; l++) {                                                                                                               \
-      const ntt_plan *pl = run ? run[l] : p;                                                                                                      \
-      L.q[l]             = pl->q;                                                                                                                 \
-      L.k[l]             = pl->CONSTS;                                                                                                            \
-    }                                                                                                                                             \
-    const int v = (lazy ? 4 : 0) | (acc ? 2 : 0) | (bcast ? 1 : 0);                                                                               \
-    switch(v) {                                                                                                                                   \
-      case 0: hipLaunchKernelGGL((pointwise_ptrs_kernel<A, false, false, false>), g, t, 0, st, ctab, atab, btab, n, (uint32_t)p->m, limb_off, b_limb_off, limb_stride, bls, L); break; \
-      case 1: hipLaunchKernelGGL((pointwise_ptrs_kernel<A, false, false, true>), g, t, 0, st, ctab, atab, btab, n, (uint32_t)p->m, limb_off, b_limb_off, limb_stride, bls, L); break;  \
-      case 2: hipLaunchKernelGGL((pointwise_ptrs_kernel<A, false, true, false>), g, t, 0, st, ctab, atab, btab, n, (uint32_t)p->m, limb_off, b_limb_off, limb_stride, bls, L); break;  \
-      case 3: hipLaunchKernelGGL((pointwise_ptrs_kernel<A, false, true, true>), g, t, 0, st, ctab, atab, btab, n, (uint32_t)p->m, limb_off, b_limb_off, limb_stride, bls, L); break;   \
-      case 4: hipLaunchKernelGGL((pointwise_ptrs_kernel<A, true, false, false>), g, t, 0, st, ctab, atab, btab, n, (uint32_t)p->m, limb_off, b_limb_off, limb_stride, bls, L); break;  \
-      case 5: hipLaunchKernelGGL((pointwise_ptrs_kernel<A, true, false, true>), g, t, 0, st, ctab, atab, btab, n, (uint32_t)p->m, limb_off, b_limb_off, limb_stride, bls, L); break;   \
-      case 6: hipLaunchKernelGGL((pointwise_ptrs_kernel<A, true, true, false>), g, t, 0, st, ctab, atab, btab, n, (uint32_t)p->m, limb_off, b_limb_off, limb_stride, bls, L); break;   \
-      default: hipLaunchKernelGGL((pointwise_ptrs_kernel<A, true, true, true>), g, t, 0, st, ctab, atab, btab, n, (uint32_t)p->m, limb_off, b_limb_off, limb_stride, bls, L); break;   \
-    }                                                                                                                                             \
-  } while(0)
-  if(p->arith == NTT_ARITH_F64) NTT_PW_PTRS(ArithF64, cf);
-  else NTT_PW_PTRS(ArithU64, cu);
-#undef NTT_PW_PTRS
+  (void)with_bools(
+    [&](auto f64, auto lazy_in, auto accumulate, auto b_bcast) {
+      using A = PwArith<decltype(f64)::value>;
+      PwLimbs<A> L{};
+      for(int l = 0; l < nrun; l++) {
+        const ntt_plan *pl = run ? run[l] : p;
+        L.q[l]             = pl->q;
+        L.k[l]             = pw_consts<A>(pl);
+      }
+      hipLaunchKernelGGL((pointwise_ptrs_kernel<A, decltype(lazy_in)::value, decltype(accumulate)::value, decltype(b_bcast)::value>), g, t, 0,
+                         (hipStream_t)stream, ctab, atab, btab, n, (uint32_t)p->m, limb_off, b_limb_off, limb_stride, bls, L);
+      return hipSuccess;
+    },
+    p->arith == NTT_ARITH_F64, lazy, acc, bcast);
   HIP_TRY(hipGetLastError());
   return NTT_OK;
 }
@@ -881,76 +715,30 @@ static int inv_dot_ptrs_limb(const ntt_plan *p, const uint64_t *const *d_c, int 
   USE_DEVICE(p->device);
   const bool lazy = (flags & NTT_MUL_LAZY_IN) != 0, bcast = (flags & NTT_MUL_B_BROADCAST) != 0;
   const uint64_t nrun = run ? (uint64_t)run->n : 1;
-  if(ptrs_fused(p)) {
-    /* dot_inv_kernel's PTRS form: the operand pointers ARE the tables (a broadcast b_i^: the polynomial, this limb of it) */
+  void *ctl = nullptr;
+  if(!ptrs_fused(p)) {
+    int rc = ptrs_team(p, stream, nrun * count, nrun * count, &ctl);
+    if(rc) return rc;
+  }
+  if(ptrs_fused(p) || ctl) {
+    /* dot_inv_kernel's PTRS form (up to 2^14): the operand pointers ARE the tables (a broadcast b_i^: the polynomial, this limb of
+     * it); team_dot_kernel's (above): products, block stages and the inverse's column stages as the items of one launch (a run: over
+     * all of its limbs) */
     const uint64_t *ta[kMaxDot], *tb[kMaxDot];
     for(int i = 0; i < k; i++) {
-      ta[i] = reinterpret_cast<const uint64_t *>(h_a[i]);
-      tb[i] = reinterpret_cast<const uint64_t *>(h_b[i]) + (bcast ? b_limb_off : 0);
+      ta[i] = as_words(h_a[i]);
+      tb[i] = as_words(h_b[i]) + (bcast ? b_limb_off : 0);
     }
-    DotArgs da{};
-    da.out          = reinterpret_cast<uint64_t *>(const_cast<uint64_t **>(reinterpret_cast<const uint64_t *const *>(d_c)));
-    da.a            = ta;
-    da.b            = tb;
-    da.npairs       = k;
-    da.lazy_in      = lazy;
-    da.b_bcast      = bcast;
-    da.limbs        = run ? run->d : p->limbrec.data();
-    da.nlimbs       = run ? run->n : 1;
-    da.limb_stride  = run ? run->stride : 0;
-    da.b_limb_stride = run && bcast ? p->N : 0; /* a broadcast operand is [limb][N] */
-    da.batch        = count;
-    da.logn         = (uint32_t)p->m;
-    da.block_log    = (uint32_t)p->m;
-    da.max_grid     = p->max_grid;
-    da.num_cus      = p->num_cus;
-    da.oversub      = p->block_oversub;
-    da.ptrs         = 1;
-    da.ptr_limb_off = limb_off;
-    da.stream       = (hipStream_t)stream;
-    hipError_t e = dispatch_dot(p, da);
-    if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return NTT_OK;
-  }
-  {
-    void *ctl = nullptr;
-    int   rc  = ptrs_team(p, stream, nrun * count, nrun * count, &ctl);
-    if(rc) return rc;
+    /* (a broadcast operand is [limb][N]) */
+    DotArgs da = dot_args(p, ptrs_set(p, run, ctl != nullptr), as_words(d_c), k, ta, tb, count, flags, run && bcast ? p->N : 0, stream);
+    set_ptrs(da, limb_off);
     if(ctl) {
-      /* team_dot_kernel's PTRS form: products, block stages and the inverse's column stages as the items of one launch (a run: over
-       * all of its limbs) */
-      const uint64_t *ta[kMaxDot], *tb[kMaxDot];
-      for(int i = 0; i < k; i++) {
-        ta[i] = reinterpret_cast<const uint64_t *>(h_a[i]);
-        tb[i] = reinterpret_cast<const uint64_t *>(h_b[i]) + (bcast ? b_limb_off : 0);
-      }
-      DotArgs da{};
-      da.out          = reinterpret_cast<uint64_t *>(const_cast<uint64_t **>(reinterpret_cast<const uint64_t *const *>(d_c)));
-      da.a            = ta;
-      da.b            = tb;
-      da.npairs       = k;
-      da.lazy_in      = lazy;
-      da.b_bcast      = bcast;
-      da.limbs        = run ? run->d : p->limbrec.data();
-      da.nlimbs       = (int)nrun;
-      da.limb_stride  = run ? run->stride : 0;
-      da.b_limb_stride = run && bcast ? p->N : 0;
-      da.poly_stride  = run ? nrun * run->stride : 0; /* (a hint: the limbs of a polynomial lie side by side -- queue numbering) */
-      da.batch        = count;
-      da.logn         = (uint32_t)p->m;
-      da.block_log    = (uint32_t)kTeamBlock;
-      da.max_grid     = p->max_grid;
-      da.num_cus      = p->num_cus;
-      da.team_ctl     = ctl;
-      da.team_lag     = p->team_lag ? p->team_lag : dot_team_lag(p, k, bcast);
-      da.team_wpc     = p->team_wpc;
-      da.ptrs         = 1;
-      da.ptr_limb_off = limb_off;
-      da.stream       = (hipStream_t)stream;
-      hipError_t e = dispatch_dot(p, da);
-      if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-      return NTT_OK;
+      set_team(da, p, ctl, dot_team_lag(p, k, bcast));
+    } else {
+      da.block_log = (uint32_t)p->m;
+      da.oversub   = p->block_oversub;
     }
+    return launched(dispatch_dot(p, da));
   }
   if(run) return kRunNotServed;
   for(int i = 0; i < k; i++) {
@@ -995,6 +783,25 @@ static int dot_ptrs_check(const void *d_c, int k, const void *const *a, const vo
   return NTT_OK;
 }
 
+static int mul_ptrs_check(bool operands, unsigned flags)
+{
+  if(!operands) return fail(NTT_ERR_ARG, "null argument");
+  if(flags & ~(unsigned)(NTT_MUL_LAZY_IN | NTT_MUL_B_BROADCAST | NTT_MUL_ACCUMULATE)) return fail(NTT_ERR_ARG, "unknown flag");
+  return NTT_OK;
+}
+
+/* The RNS pointer-batch products, from their arguments to their runs: the limb list, the entry point's own operand and flag checks
+ * (operands()), an empty batch (nothing to do), the limb stride; then rns_for_runs over tables whose entries are N words apart. */
+template <class Operands, class Pays, class SetFn, class OneFn>
+static int rns_ptrs_runs(int nlimbs, ntt_plan *const *plans, uint64_t count, uint64_t limb_stride, Operands operands, Pays pays, SetFn set_fn, OneFn one_fn)
+{
+  int rc = rns_check(nlimbs, plans);
+  if(!rc) rc = operands();
+  if(rc || count == 0) return rc;
+  if(limb_stride < plans[0]->N || limb_stride > (1ull << 40)) return fail(NTT_ERR_ARG, "layout: the limb stride must be at least N words");
+  return rns_for_runs(nlimbs, plans, Layout{limb_stride, plans[0]->N}, pays, set_fn, one_fn);
+}
+
 extern "C" int ntt_inv_dot_dev_ptrs(const ntt_plan *p, const uint64_t *const *d_c, int k, const uint64_t *const *const *h_ahat,
                                     const uint64_t *const *const *h_bhat, uint64_t count, unsigned flags, void *stream)
 {
@@ -1007,18 +814,16 @@ extern "C" int ntt_inv_dot_dev_ptrs(const ntt_plan *p, const uint64_t *const *d_
 extern "C" int ntt_rns_inv_dot_dev_ptrs(int nlimbs, ntt_plan *const *plans, const uint64_t *const *d_c, int k, const uint64_t *const *const *h_ahat,
                                         const uint64_t *const *const *h_bhat, uint64_t count, uint64_t limb_stride, unsigned flags, void *stream)
 {
-  int rc = rns_check(nlimbs, plans);
-  if(rc) return rc;
-  rc = dot_ptrs_check(d_c, k, reinterpret_cast<const void *const *>(h_ahat), reinterpret_cast<const void *const *>(h_bhat), flags);
-  if(rc || count == 0) return rc;
-  if(limb_stride < plans[0]->N || limb_stride > (1ull << 40)) return fail(NTT_ERR_ARG, "layout: the limb stride must be at least N words");
   /* a run of compatible limbs whose share of the batch cannot fill the chip limb by limb (a few ciphertexts x many primes): ONE launch
    * over the run -- the fused kernels' MULTI instances, the limb an index of the grid, as for the slab forms (rns_one_launch_pays) */
-  const uint64_t N = plans[0]->N;
-  return rns_for_runs(
-    nlimbs, plans, Layout{limb_stride, N}, [&](const ntt_plan *p, int) { return ptrs_run_pays(p, count); },
-    [&](int first, const LimbSet &ls) { return inv_dot_ptrs_run(plans + first, ls, d_c, k, h_ahat, h_bhat, count, flags, (uint64_t)first * limb_stride, (uint64_t)first * N, stream); },
-    [&](int l) { return inv_dot_ptrs_limb(plans[l], d_c, k, h_ahat, h_bhat, count, flags, (uint64_t)l * limb_stride, (uint64_t)l * N, stream); });
+  return rns_ptrs_runs(
+    nlimbs, plans, count, limb_stride,
+    [&] { return dot_ptrs_check(d_c, k, reinterpret_cast<const void *const *>(h_ahat), reinterpret_cast<const void *const *>(h_bhat), flags); },
+    [&](const ntt_plan *p, int) { return ptrs_run_pays(p, count); },
+    [&](int first, const LimbSet &ls) {
+      return inv_dot_ptrs_run(plans + first, ls, d_c, k, h_ahat, h_bhat, count, flags, (uint64_t)first * limb_stride, (uint64_t)first * plans[0]->N, stream);
+    },
+    [&](int l) { return inv_dot_ptrs_limb(plans[l], d_c, k, h_ahat, h_bhat, count, flags, (uint64_t)l * limb_stride, (uint64_t)l * plans[0]->N, stream); });
 }
 
 /* N = 2^15, FP64 plans: fwd(a) (.) b^ in ONE pass with the tables read at its output (the slab form's choice: batches that give every
@@ -1049,42 +854,17 @@ static int fwd_mul_ptrs_limb(const ntt_plan *p, const uint64_t *const *d_c, cons
     /* fwd_mul_kernel's (onepass_mul_kernel's) PTRS form: a is left as it was; team_mul_kernel's (2^15..2^17, a's column stages in
      * place: a is scratch) */
     const bool bcast = (flags & NTT_MUL_B_BROADCAST) != 0;
-    MulArgs ma{};
-    ma.a            = reinterpret_cast<uint64_t *>(const_cast<uint64_t **>(reinterpret_cast<const uint64_t *const *>(d_a)));
-    ma.b            = reinterpret_cast<const uint64_t *>(d_bhat) + (bcast ? b_limb_off : 0);
-    ma.out          = reinterpret_cast<uint64_t *>(const_cast<uint64_t **>(reinterpret_cast<const uint64_t *const *>(d_c)));
-    ma.lazy_in      = (flags & NTT_MUL_LAZY_IN) != 0;
-    ma.b_bcast      = bcast;
-    ma.accumulate   = (flags & NTT_MUL_ACCUMULATE) != 0;
-    ma.limbs        = run ? run->d : p->limbrec.data();
-    ma.nlimbs       = run ? run->n : 1;
-    ma.limb_stride  = run ? run->stride : 0;
-    ma.b_limb_stride = run && bcast ? p->N : 0; /* a broadcast operand is [limb][N] */
-    ma.poly_stride  = run ? nrun * run->stride : 0; /* (a hint for the XCD-local launch's queue numbering, as inv_dot_ptrs_limb) */
-    ma.batch        = count;
-    ma.logn         = (uint32_t)p->m;
-    ma.block_log    = ctl ? (uint32_t)kTeamBlock : (uint32_t)p->m;
-    ma.max_grid     = p->max_grid;
-    ma.num_cus      = p->num_cus;
-    ma.oversub      = p->block_oversub;
-    ma.team_ctl     = ctl;
-    ma.team_lag     = p->team_lag ? p->team_lag : mul_team_lag(p);
-    ma.team_wpc     = p->team_wpc;
-    ma.one_pass     = one_pass;
-    ma.ptrs         = 1;
-    ma.ptr_limb_off = limb_off;
-    ma.stream       = (hipStream_t)stream;
-    const int  ic = eff_int_cls(p), kc = eff_kcls(p);
-    hipError_t e  = p->arith == NTT_ARITH_U64 ? (ic == 3   ? launch_fwd_mul<ArithU64X<3>, 3>(ma)
-                                                 : ic == 1 ? launch_fwd_mul<ArithU64X<1>, 1>(ma)
-                                                 : ic == 0 ? launch_fwd_mul<ArithU64X<0>, 0>(ma)
-                                                           : launch_fwd_mul<ArithU64, 0>(ma))
-                    : kc == kWideClass        ? launch_fwd_mul<ArithF64W, 0>(ma)
-                    : kc == 18                ? launch_fwd_mul<ArithF64, 18>(ma)
-                    : kc == 1                 ? launch_fwd_mul<ArithF64, 1>(ma)
-                                              : launch_fwd_mul<ArithF64, 0>(ma);
-    if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return NTT_OK;
+    /* (a broadcast operand is [limb][N]; the spacing hint, the lag and the oversubscription on all three forms, as ever) */
+    MulArgs ma = mul_args(p, ptrs_set(p, run, true), as_words(d_c), as_words(d_a), as_words(d_bhat) + (bcast ? b_limb_off : 0), count, flags,
+                          run && bcast ? p->N : 0, stream);
+    set_ptrs(ma, limb_off);
+    /* (also without a control block -- the fused and one-pass forms: their record has always carried the lag and the workgroups per CU;
+     * set_team's block size is then replaced by the whole polynomial) */
+    set_team(ma, p, ctl, mul_team_lag(p));
+    if(!ctl) ma.block_log = (uint32_t)p->m;
+    ma.oversub  = p->block_oversub;
+    ma.one_pass = one_pass;
+    return launched(dispatch_mul(p, ma));
   }
   if(run) return kRunNotServed;
   const LimbSet set{p->limbrec.data(), 1, 0, 0, reinterpret_cast<const uint64_t *>(d_a)};
@@ -1097,27 +877,20 @@ static int fwd_mul_ptrs_limb(const ntt_plan *p, const uint64_t *const *d_c, cons
 extern "C" int ntt_fwd_mul_dev_ptrs(const ntt_plan *p, const uint64_t *const *d_c, const uint64_t *const *d_a, const uint64_t *const *d_bhat,
                                     uint64_t count, unsigned flags, void *stream)
 {
-  if(!p || !d_c || !d_a || !d_bhat) return fail(NTT_ERR_ARG, "null argument");
-  if(flags & ~(unsigned)(NTT_MUL_LAZY_IN | NTT_MUL_B_BROADCAST | NTT_MUL_ACCUMULATE)) return fail(NTT_ERR_ARG, "unknown flag");
-  if(count == 0) return NTT_OK;
+  const int rc = mul_ptrs_check(p && d_c && d_a && d_bhat, flags);
+  if(rc || count == 0) return rc;
   return fwd_mul_ptrs_limb(p, d_c, d_a, d_bhat, count, flags, 0, 0, stream);
 }
 
 extern "C" int ntt_rns_fwd_mul_dev_ptrs(int nlimbs, ntt_plan *const *plans, const uint64_t *const *d_c, const uint64_t *const *d_a,
                                         const uint64_t *const *d_bhat, uint64_t count, uint64_t limb_stride, unsigned flags, void *stream)
 {
-  int rc = rns_check(nlimbs, plans);
-  if(rc) return rc;
-  if(!d_c || !d_a || !d_bhat) return fail(NTT_ERR_ARG, "null argument");
-  if(flags & ~(unsigned)(NTT_MUL_LAZY_IN | NTT_MUL_B_BROADCAST | NTT_MUL_ACCUMULATE)) return fail(NTT_ERR_ARG, "unknown flag");
-  if(count == 0) return NTT_OK;
-  if(limb_stride < plans[0]->N || limb_stride > (1ull << 40)) return fail(NTT_ERR_ARG, "layout: the limb stride must be at least N words");
-  const uint64_t N = plans[0]->N;
-  return rns_for_runs(
-    nlimbs, plans, Layout{limb_stride, N}, [&](const ntt_plan *p, int) { return ptrs_run_pays(p, count) && !ptrs_one_pass_mul(p, count); },
+  return rns_ptrs_runs(
+    nlimbs, plans, count, limb_stride, [&] { return mul_ptrs_check(d_c && d_a && d_bhat, flags); },
+    [&](const ntt_plan *p, int) { return ptrs_run_pays(p, count) && !ptrs_one_pass_mul(p, count); },
     [&](int first, const LimbSet &ls) {
       const ntt_plan *p   = plans[first];
-      const uint64_t  off = (uint64_t)first * limb_stride;
+      const uint64_t  off = (uint64_t)first * limb_stride, N = p->N;
       for(int l = 0; l < ls.n; l++) {
         if(!plans[first + l]->has_fwd) return fail(NTT_ERR_ARG, "plan lacks the forward table");
       }
@@ -1134,7 +907,7 @@ extern "C" int ntt_rns_fwd_mul_dev_ptrs(int nlimbs, ntt_plan *const *plans, cons
       return pointwise_ptrs(p, d_c, d_a, d_bhat, count, (flags & NTT_MUL_LAZY_IN) != 0, (flags & NTT_MUL_ACCUMULATE) != 0, (flags & NTT_MUL_B_BROADCAST) != 0, off,
                             (uint64_t)first * N, stream, plans + first, ls.n, ls.stride);
     },
-    [&](int l) { return fwd_mul_ptrs_limb(plans[l], d_c, d_a, d_bhat, count, flags, (uint64_t)l * limb_stride, (uint64_t)l * N, stream); });
+    [&](int l) { return fwd_mul_ptrs_limb(plans[l], d_c, d_a, d_bhat, count, flags, (uint64_t)l * limb_stride, (uint64_t)l * plans[0]->N, stream); });
 }
 
 /* c = a * b in Z_q[X]/(X^N+1).  FP64 plans up to 2^14: fused_product_kernel's PTRS form -- both operands through the forward stages,
@@ -1153,27 +926,11 @@ static int negacyclic_mul_ptrs_limb(const ntt_plan *p, const uint64_t *const *d_
   const uint64_t nrun = run ? (uint64_t)run->n : 1;
   USE_DEVICE(p->device);
   if(ptrs_fused_product(p, d_a, d_b)) {
-    ProdArgs pa{};
-    pa.b            = reinterpret_cast<uint64_t *>(const_cast<uint64_t **>(reinterpret_cast<const uint64_t *const *>(d_b)));
-    pa.ahat         = reinterpret_cast<const uint64_t *>(d_a);
-    pa.out          = reinterpret_cast<uint64_t *>(const_cast<uint64_t **>(reinterpret_cast<const uint64_t *const *>(d_c)));
-    pa.limbs        = run ? run->d : p->limbrec.data();
-    pa.nlimbs       = run ? run->n : 1;
-    pa.limb_stride  = run ? run->stride : 0;
-    pa.batch        = count;
-    pa.logn         = (uint32_t)p->m;
-    pa.block_log    = (uint32_t)p->m;
-    pa.a_lazy       = 1;
-    pa.both         = 1;
-    pa.ptrs         = 1;
-    pa.ptr_limb_off = limb_off;
-    pa.max_grid     = p->max_grid;
-    pa.num_cus      = p->num_cus;
-    pa.oversub      = p->block_oversub;
-    pa.stream       = (hipStream_t)stream;
-    const hipError_t e = with_f64_class(eff_kcls(p), [&](auto k) { return launch_product<typename decltype(k)::A, decltype(k)::KSH>(pa); });
-    if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return NTT_OK;
+    ProdArgs pa  = prod_args(p, ptrs_set(p, run, false), as_words(d_c), as_words(d_a), as_words(d_b), count, stream);
+    pa.block_log = (uint32_t)p->m;
+    pa.both      = 1;
+    set_ptrs(pa, limb_off);
+    return launched(dispatch_product(p, pa));
   }
   if(d_a != d_b && p->fused_product == 1 && p->arith == NTT_ARITH_F64) {
     void *ctl = nullptr;
@@ -1182,30 +939,11 @@ static int negacyclic_mul_ptrs_limb(const ntt_plan *p, const uint64_t *const *d_
     if(ctl) {
       /* 2^15..2^17: team_product_kernel's PTRS form -- column stages of both operands, block products, inverse column stages of c
        * as the items of ONE launch; a and b are scratch (their column stages run in place) */
-      ProdArgs pa{};
-      pa.four         = 1;
-      pa.b            = reinterpret_cast<uint64_t *>(const_cast<uint64_t **>(reinterpret_cast<const uint64_t *const *>(d_b)));
-      pa.ahat         = reinterpret_cast<const uint64_t *>(d_a);
-      pa.out          = reinterpret_cast<uint64_t *>(const_cast<uint64_t **>(reinterpret_cast<const uint64_t *const *>(d_c)));
-      pa.limbs        = run ? run->d : p->limbrec.data();
-      pa.nlimbs       = (int)nrun;
-      pa.limb_stride  = run ? run->stride : 0;
-      pa.poly_stride  = run ? nrun * run->stride : 0; /* (a hint for the queue numbering, as inv_dot_ptrs_limb) */
-      pa.batch        = count;
-      pa.logn         = (uint32_t)p->m;
-      pa.a_lazy       = 1;
-      pa.max_grid     = p->max_grid;
-      pa.num_cus      = p->num_cus;
-      pa.oversub      = p->block_oversub;
-      pa.team_ctl     = ctl;
-      pa.team_lag     = p->team_lag ? p->team_lag : (p->m == kTeamBlock + 3 ? 20 : (p->m == kTeamBlock + 4 ? 14 : 8));
-      pa.team_wpc     = p->team_wpc;
-      pa.ptrs         = 1;
-      pa.ptr_limb_off = limb_off;
-      pa.stream       = (hipStream_t)stream;
-      const hipError_t e = with_f64_class(eff_kcls(p), [&](auto k) { return launch_team_product<typename decltype(k)::A, decltype(k)::KSH>(pa); });
-      if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-      return NTT_OK;
+      ProdArgs pa = prod_args(p, ptrs_set(p, run, true), as_words(d_c), as_words(d_a), as_words(d_b), count, stream);
+      pa.four     = 1;
+      set_ptrs(pa, limb_off);
+      set_team(pa, p, ctl, p->m == kTeamBlock + 3 ? 20 : (p->m == kTeamBlock + 4 ? 14 : 8)); /* (fused_product's lags with `four`) */
+      return launched(dispatch_product(p, pa));
     }
   }
   if(run) return kRunNotServed;
@@ -1236,13 +974,8 @@ extern "C" int ntt_negacyclic_mul_dev_ptrs(const ntt_plan *p, const uint64_t *co
 extern "C" int ntt_rns_negacyclic_mul_dev_ptrs(int nlimbs, ntt_plan *const *plans, const uint64_t *const *d_c, const uint64_t *const *d_a,
                                                const uint64_t *const *d_b, uint64_t count, uint64_t limb_stride, void *stream)
 {
-  int rc = rns_check(nlimbs, plans);
-  if(rc) return rc;
-  if(!d_c || !d_a || !d_b) return fail(NTT_ERR_ARG, "null argument");
-  if(count == 0) return NTT_OK;
-  if(limb_stride < plans[0]->N || limb_stride > (1ull << 40)) return fail(NTT_ERR_ARG, "layout: the limb stride must be at least N words");
-  return rns_for_runs(
-    nlimbs, plans, Layout{limb_stride, plans[0]->N}, [&](const ntt_plan *p, int) { return ptrs_run_pays(p, count); },
+  return rns_ptrs_runs(
+    nlimbs, plans, count, limb_stride, [&] { return all_given(d_c && d_a && d_b); }, [&](const ntt_plan *p, int) { return ptrs_run_pays(p, count); },
     [&](int first, const LimbSet &ls) {
       const ntt_plan *p   = plans[first];
       const uint64_t  off = (uint64_t)first * limb_stride;

@@ -102,14 +102,15 @@ __global__ void __launch_bounds__(256) records_r4_kernel(TwU64 *out, const uint6
 constexpr int kWideClass = -1; /* ntt_plan::kcls of the FP64 policy for 2^51(1+2^-10) < q < 2^52 (ArithF64W) */
 
 /* a headroom class as the template arguments of the FP64 kernel instances built for it, in the style of with_int:
- * f(F64Class<policy, class>{}), so that a launcher template L is reached as L<typename decltype(k)::A, decltype(k)::KSH> */
-template <class Arith, int K> struct F64Class {
+ * f(KernelClass<policy, class>{}), so that a launcher template L is reached as L<typename decltype(k)::A, decltype(k)::KSH>
+ * (with_class, host_transforms.inc: the same over a plan's policy, the integer ones included) */
+template <class Arith, int K> struct KernelClass {
   using A                  = Arith;
   static constexpr int KSH = K;
 };
 template <class F> static hipError_t with_f64_class(int kc, F &&f)
 {
-  return kc == kWideClass ? f(F64Class<ArithF64W, 0>{}) : kc == 18 ? f(F64Class<ArithF64, 18>{}) : kc == 1 ? f(F64Class<ArithF64, 1>{}) : f(F64Class<ArithF64, 0>{});
+  return kc == kWideClass ? f(KernelClass<ArithF64W, 0>{}) : kc == 18 ? f(KernelClass<ArithF64, 18>{}) : kc == 1 ? f(KernelClass<ArithF64, 1>{}) : f(KernelClass<ArithF64, 0>{});
 }
 
 struct ntt_plan {

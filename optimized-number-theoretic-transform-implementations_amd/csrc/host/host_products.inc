@@ -106,6 +106,16 @@ static unsigned grid_pw(uint64_t n, int max_grid)
   return (unsigned)(g ? g : 1);
 }
 
+/* The element-wise kernels are built for two policies -- FP64 plans multiply in FP64, every integer policy with the reference's
+ * Barrett product -- and take their run-time flags as template arguments: with_bools(f, p->arith == NTT_ARITH_F64, flags...) hands f
+ * the policy as its first constant (PwArith). */
+template <bool F64> using PwArith = std::conditional_t<F64, ArithF64, ArithU64>;
+template <class A> static const typename A::consts &pw_consts(const ntt_plan *p)
+{
+  if constexpr(std::is_same_v<A, ArithF64>) return p->cf;
+  else return p->cu;
+}
+
 /* pstride: words between consecutive polynomials of all three operands (0 = dense: N) */
 static int pointwise_launch(const ntt_plan *p, uint64_t *d_c, const uint64_t *d_a, const uint64_t *d_b, uint64_t batch,
                             void *stream, bool lazy_in, uint64_t pstride = 0)
@@ -115,15 +125,34 @@ static int pointwise_launch(const ntt_plan *p, uint64_t *d_c, const uint64_t *d_
   USE_DEVICE(p->device);
   const uint64_t n = batch * p->N;
   const dim3     g(grid_pw(n, p->max_grid)), t(256);
-  hipStream_t    st = (hipStream_t)stream;
   const PwLayout lay{(uint32_t)p->m, pstride ? pstride : p->N, pstride ? pstride : p->N};
-  if(p->arith == NTT_ARITH_F64) {
-    if(lazy_in) hipLaunchKernelGGL((pointwise_kernel<ArithF64, true>), g, t, 0, st, d_c, d_a, d_b, n, lay, p->cf);
-    else hipLaunchKernelGGL((pointwise_kernel<ArithF64, false>), g, t, 0, st, d_c, d_a, d_b, n, lay, p->cf);
-  } else {
-    if(lazy_in) hipLaunchKernelGGL((pointwise_kernel<ArithU64, true>), g, t, 0, st, d_c, d_a, d_b, n, lay, p->cu);
-    else hipLaunchKernelGGL((pointwise_kernel<ArithU64, false>), g, t, 0, st, d_c, d_a, d_b, n, lay, p->cu);
-  }
+  (void)with_bools(
+    [&](auto f64, auto lazy) {
+      using A = PwArith<decltype(f64)::value>;
+      hipLaunchKernelGGL((pointwise_kernel<A, decltype(lazy)::value>), g, t, 0, (hipStream_t)stream, d_c, d_a, d_b, n, lay, pw_consts<A>(p));
+      return hipSuccess;
+    },
+    p->arith == NTT_ARITH_F64, lazy_in);
+  HIP_TRY(hipGetLastError());
+  return NTT_OK;
+}
+
+/* c = (acc ? c : 0) + a (.) b, element by element over a slab of ls's (one) limb: the unfused form of the NTT-domain products.
+ * bcast: b is ONE polynomial shared by the batch. */
+static int pointwise_acc(const ntt_plan *p, uint64_t *d_c, const uint64_t *d_a, const uint64_t *d_b, uint64_t batch, const LimbSet &ls, bool lazy_in,
+                         bool acc, bool bcast, void *stream)
+{
+  const uint64_t n = batch * p->N;
+  const dim3     g(grid_pw(n, p->max_grid)), t(256);
+  const PwLayout lay{(uint32_t)p->m, poly_words(p, ls), bcast ? 0 : poly_words(p, ls)};
+  (void)with_bools(
+    [&](auto f64, auto lazy, auto accumulate) {
+      using A = PwArith<decltype(f64)::value>;
+      hipLaunchKernelGGL((pointwise_acc_kernel<A, decltype(lazy)::value, decltype(accumulate)::value>), g, t, 0, (hipStream_t)stream, d_c, d_a, d_b, n, lay,
+                         p->q, pw_consts<A>(p));
+      return hipSuccess;
+    },
+    p->arith == NTT_ARITH_F64, lazy_in, acc);
   HIP_TRY(hipGetLastError());
   return NTT_OK;
 }
@@ -139,33 +168,25 @@ extern "C" int ntt_pointwise_mul_batch_lazy(const ntt_plan *p, uint64_t *d_c, co
   return pointwise_launch(p, d_c, d_a, d_b, batch, stream, true);
 }
 
-/* one pass of a transform on nb polynomials starting at d (shared by run_transform's loop and the fused product) */
-static int launch_one_pass(const ntt_plan *p, const Pass &ps, uint64_t *d, uint64_t nb, bool inverse, bool wide, bool lazy,
-                           bool ends, void *stream, const LimbSet &ls)
+/* a ProdArgs record over ls: c = inv(fwd(b) (.) a^), a^ in lazy words -- or, its `both` / `four` set, inv(fwd(b) (.) fwd(a)) */
+static ProdArgs prod_args(const ntt_plan *p, const LimbSet &ls, uint64_t *out, const uint64_t *ahat, uint64_t *b, uint64_t batch, void *stream)
 {
-  PassArgs pa{};
-  pa.a        = d;
-  pa.limbs    = ls.d;
-  pa.nlimbs   = ls.n;
-  pa.limb_stride = ls.stride;
-  pa.poly_stride = ls.pstride;
-  pa.batch    = nb;
-  pa.logn     = (uint32_t)p->m;
-  pa.fused    = ps.fused;
-  pa.r        = ps.r;
-  pa.s        = ps.s;
-  pa.inverse  = inverse;
-  pa.wide     = wide;
-  pa.lastinv  = inverse && ps.s == 0;
-  pa.lazy     = lazy;
-  pa.ends     = ends;
-  pa.max_grid = p->max_grid;
-  pa.num_cus  = p->num_cus;
-  pa.oversub  = p->block_oversub;
-  pa.stream   = (hipStream_t)stream;
-  hipError_t e = dispatch_pass(p, pa);
-  if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-  return NTT_OK;
+  ProdArgs pa{};
+  launch_common(pa, p, ls, batch, stream);
+  pa.b       = b;
+  pa.ahat    = ahat;
+  pa.out     = out;
+  pa.a_lazy  = 1;
+  pa.oversub = p->block_oversub;
+  return pa;
+}
+/* (the product kernels are built for the FP64 policies; with a control block: the XCD-local one-launch form) */
+static hipError_t dispatch_product(const ntt_plan *p, const ProdArgs &pa)
+{
+  return with_f64_class(eff_kcls(p), [&](auto k) {
+    using K = decltype(k);
+    return pa.team_ctl ? launch_team_product<typename K::A, K::KSH>(pa) : launch_product<typename K::A, K::KSH>(pa);
+  });
 }
 
 /* c = a * b with the fused product kernels (FP64, N = 2^8 .. 2^17).
@@ -209,79 +230,35 @@ static int fused_product(const ntt_plan *p, uint64_t *d_c, uint64_t *d_a, uint64
     if(rc) return rc;
   }
   USE_DEVICE(p->device);
-  if(canonical_a && !p->block_log) {
-    if(ctl) {
-      ProdArgs pa{};
-      pa.four        = four;
-      pa.b           = d_b;
-      pa.ahat        = d_a;
-      pa.out         = d_c;
-      pa.limbs       = ls.d;
-      pa.nlimbs      = ls.n;
-      pa.limb_stride = ls.stride;
-      pa.poly_stride = ls.pstride;
-      pa.batch       = batch;
-      pa.logn        = (uint32_t)p->m;
-      pa.a_lazy      = 1;
-      pa.max_grid    = p->max_grid;
-      pa.num_cus     = p->num_cus;
-      pa.oversub     = p->block_oversub;
-      pa.team_ctl    = ctl;
-      /* three passes, four workgroups per CU: the lag that keeps second- and third-pass items from waiting is larger than
-       * the transform's (measured, profiles/r03/sweep_product_lag.txt: flat optimum 12-14 at 2^17, 12-20 at 2^16, 20-24 at 2^15;
-       * with both operands' column tiles in the first pass: 8 at 2^17, 12-16 at 2^16, 20-24 at 2^15) */
-      pa.team_lag    = p->team_lag ? p->team_lag : (p->m == kTeamBlock + 3 ? 20 : (p->m == kTeamBlock + 4 ? 14 : (four ? 8 : 12)));
-      pa.team_wpc    = p->team_wpc;
-      pa.stream      = (hipStream_t)stream;
-      const hipError_t e = with_f64_class(eff_kcls(p), [&](auto k) { return launch_team_product<typename decltype(k)::A, decltype(k)::KSH>(pa); });
-      if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-      return NTT_OK;
-    }
+  if(ctl) {
+    ProdArgs pa = prod_args(p, ls, d_c, d_a, d_b, batch, stream);
+    pa.four     = four;
+    /* three passes, four workgroups per CU: the lag that keeps second- and third-pass items from waiting is larger than
+     * the transform's (measured, profiles/r03/sweep_product_lag.txt: flat optimum 12-14 at 2^17, 12-20 at 2^16, 20-24 at 2^15;
+     * with both operands' column tiles in the first pass: 8 at 2^17, 12-16 at 2^16, 20-24 at 2^15) */
+    set_team(pa, p, ctl, p->m == kTeamBlock + 3 ? 20 : (p->m == kTeamBlock + 4 ? 14 : (four ? 8 : 12)));
+    return launched(dispatch_product(p, pa));
   }
   /* blocks of the fused launch for N > 2^14: as for the transforms, stages are cheaper in the memory-bound column
    * passes than in the FP64-bound fused launch -- 2^12-point blocks where 4 column stages reach (measured +3..5 % at
    * 2^15 and 2^16; 2^13-point blocks at 2^17: -1 %, not used) */
   const int      pblk   = p->m > kFusedMax ? (p->block_log ? p->block_log : (p->m <= kFusedSmallBlock + 4 ? kFusedSmallBlock : kFusedLarge)) : p->m;
   const PassList L     = make_passes(p->m, false, pblk);
-  uint64_t       chunk = batch;
-  if(L.n > 1) {
-    chunk = ((uint64_t)p->chunk_mib << 20) / (p->N * sizeof(uint64_t) * (uint64_t)ls.n);
-    if(chunk < 1) chunk = 1;
-    if(chunk > batch) chunk = batch;
-  }
-  for(uint64_t first = 0; first < batch; first += chunk) {
-    const uint64_t nb  = batch - first < chunk ? batch - first : chunk;
-    const uint64_t off = first * poly_words(p, ls);
+  return for_chunks(p, ls, batch, (uint64_t)p->chunk_mib, L.n, [&](uint64_t, uint64_t nb, uint64_t off) -> int {
     for(int k = 0; k + 1 < L.n; k++) { /* forward column passes of b (every pass but the last, which is the block pass) */
       rc = launch_one_pass(p, L.p[k], d_b + off, nb, false, false, false, false, stream, ls);
       if(!rc && both) rc = launch_one_pass(p, L.p[k], d_a + off, nb, false, false, false, false, stream, ls); /* ... and of a */
       if(rc) return rc;
     }
-    ProdArgs pa{};
-    pa.b        = d_b + off;
-    pa.ahat     = d_a + off;
-    pa.out      = d_c + off;
-    pa.limbs    = ls.d;
-    pa.nlimbs   = ls.n;
-    pa.limb_stride = ls.stride;
-    pa.poly_stride = ls.pstride;
-    pa.batch    = nb;
-    pa.logn     = (uint32_t)p->m;
+    ProdArgs pa  = prod_args(p, ls, d_c + off, d_a + off, d_b + off, nb, stream);
     pa.block_log = (uint32_t)pblk;
-    pa.a_lazy   = 1;
-    pa.both     = both;
-    pa.max_grid = p->max_grid;
-    pa.num_cus  = p->num_cus;
-    pa.oversub  = p->block_oversub;
-    pa.stream   = (hipStream_t)stream;
-    const hipError_t e = with_f64_class(eff_kcls(p), [&](auto k) { return launch_product<typename decltype(k)::A, decltype(k)::KSH>(pa); });
-    if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    for(int k = L.n - 2; k >= 0; k--) { /* inverse column passes of c, the last one ends the transform (N^-1) */
+    pa.both      = both;
+    rc           = launched(dispatch_product(p, pa));
+    for(int k = L.n - 2; !rc && k >= 0; k--) { /* inverse column passes of c, the last one ends the transform (N^-1) */
       rc = launch_one_pass(p, L.p[k], d_c + off, nb, true, false, false, k == 0, stream, ls);
-      if(rc) return rc;
     }
-  }
-  return NTT_OK;
+    return rc;
+  });
 }
 
 static bool fused_product_applies(const ntt_plan *p, const uint64_t *d_c, const uint64_t *d_a, const uint64_t *d_b, uint64_t batch)
@@ -427,6 +404,22 @@ static int rns_for_runs(int nlimbs, ntt_plan *const *plans, const Layout &lay, P
   return rc;
 }
 
+/* The slab drivers of the RNS products, from their arguments to their runs: the limb list, an empty batch (nothing to do), the
+ * driver's own operand checks -- operands(), before any limb offset is added --, the layout; then rns_for_runs. */
+static int all_given(bool operands) { return operands ? NTT_OK : fail(NTT_ERR_ARG, "null argument"); }
+template <class Operands, class Pays, class SetFn, class OneFn>
+static int rns_slab_runs(int nlimbs, ntt_plan *const *plans, uint64_t batch, const Layout &lay, Operands operands, Pays pays, SetFn set_fn, OneFn one_fn)
+{
+  int rc = rns_check(nlimbs, plans);
+  if(rc || batch == 0) return rc;
+  rc = operands();
+  if(!rc) rc = layout_check(plans[0]->N, nlimbs, batch, lay);
+  if(rc) return rc;
+  return rns_for_runs(nlimbs, plans, lay, pays, set_fn, one_fn);
+}
+/* the words between the limbs of a b operand: a broadcast one is [limb][N] */
+static uint64_t b_slab(ntt_plan *const *plans, const Layout &lay, unsigned flags) { return (flags & NTT_MUL_B_BROADCAST) ? plans[0]->N : lay.limb; }
+
 /* One launch for all limbs pays when a single limb's share cannot fill the chip by itself (a ciphertext: a few
  * polynomials x tens of primes); with thousands of polynomials per limb every per-limb launch fills it, and the
  * single-set kernels are the faster ones (no run-time limb index: ntt_kernels.h, MULTI).  NTT_OPT_RNS_LAUNCH 0 / 1 on the
@@ -518,18 +511,13 @@ extern "C" int ntt_rns_inv_batch_strided(int nlimbs, ntt_plan *const *plans, uin
 static int rns_negacyclic_mul(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, uint64_t *d_a, uint64_t *d_b, uint64_t batch, void *stream,
                               const Layout &lay)
 {
-  int rc = rns_check(nlimbs, plans);
-  if(rc || batch == 0) return rc;
-  if(!d_c || !d_a || !d_b) return fail(NTT_ERR_ARG, "null argument");
-  rc = layout_check(plans[0]->N, nlimbs, batch, lay);
-  if(rc) return rc;
   /* a run of the wide integer policy: both forward transforms (lazy words, in place -- the operands are scratch on this path as
    * they are for a single plan) and the products inside the inverse transform's first pass, each ONE launch over the run */
   auto int_run = [&](const ntt_plan *p) {
     return p->arith == NTT_ARITH_U64 && dot_kernel_applies(p) && p->has_fwd && p->has_inv;
   };
-  return rns_for_runs(
-    nlimbs, plans, lay,
+  return rns_slab_runs(
+    nlimbs, plans, batch, lay, [&] { return all_given(d_c && d_a && d_b); },
     [&](const ntt_plan *p, int n) {
       if(fused_product_applies(p, d_c, d_a, d_b, batch)) {
         return rns_one_launch_pays(p, batch) || (rns_team_launch(p, n, batch, false, true) && !p->block_log);

@@ -1,4 +1,4 @@
-/* host/host_transforms.inc -- batched transforms: dispatch over policies and classes, the launch choice (one pass / XCD-local / two-phase / per-pass chunks), the ntt_*_batch entry points.
+/* host/host_transforms.inc -- batched transforms: dispatch over policies and classes, what every route shares (launch records, the XCD-local decision, the chunk walk), the launch choice (one pass / XCD-local / two-phase / per-pass chunks), the ntt_*_batch entry points.
  * A section of ntt_host.hip (one translation unit, included from there in order); not compiled by itself. */
 
 /* ------------------------------------------------------------------ */
@@ -11,23 +11,42 @@ static thread_local int t_run_kcls = INT_MIN, t_run_int_cls = INT_MIN;
 static int eff_kcls(const ntt_plan *p) { return (t_run_kcls != INT_MIN && p->kcls != kWideClass) ? t_run_kcls : p->kcls; }
 static int eff_int_cls(const ntt_plan *p) { return (t_run_int_cls != INT_MIN && p->int_cls >= 0) ? t_run_int_cls : p->int_cls; }
 
+/* The plan's radix-2 policy and (effective) headroom class as the template arguments of a launcher: f(KernelClass<A, KSH>{}) for the eight
+ * pairs every launcher of a plain transform or an NTT-domain product is built for (with_f64_class: the FP64 half by itself).  The
+ * radix-4 policy is not among them: only launch_pass has it (dispatch_pass). */
+template <class F> static hipError_t with_class(const ntt_plan *p, F &&f)
+{
+  if(p->arith != NTT_ARITH_U64) return with_f64_class(eff_kcls(p), f);
+  switch(eff_int_cls(p)) { /* (same tables; the wide policy's stages around its Barrett products) */
+    case 3: return f(KernelClass<ArithU64X<3>, 3>{});
+    case 1: return f(KernelClass<ArithU64X<1>, 1>{});
+    case 0: return f(KernelClass<ArithU64X<0>, 0>{});
+    default: return f(KernelClass<ArithU64, 0>{});
+  }
+}
+
 static hipError_t dispatch_pass(const ntt_plan *p, const PassArgs &pa)
 {
-  if(p->arith == NTT_ARITH_U64) {
-    switch(p->generic ? -1 : eff_int_cls(p)) { /* (generic = the column-pass cross-check path: the reference's butterflies) */
-      case 3: return launch_pass<ArithU64X<3>, 3>(pa);
-      case 1: return launch_pass<ArithU64X<1>, 1>(pa);
-      case 0: return launch_pass<ArithU64X<0>, 0>(pa);
-      default: return launch_pass<ArithU64, 0>(pa);
-    }
-  }
+  /* (generic = the column-pass cross-check path: the reference's butterflies) */
+  if(p->arith == NTT_ARITH_U64 && p->generic) return launch_pass<ArithU64, 0>(pa);
   if(p->arith == NTT_ARITH_U64_R4) return launch_pass<ArithU64R4, 0>(pa);
-  switch(eff_kcls(p)) {
-    case kWideClass: return launch_pass<ArithF64W, 0>(pa);
-    case 18: return launch_pass<ArithF64, 18>(pa);
-    case 1: return launch_pass<ArithF64, 1>(pa);
-    default: return launch_pass<ArithF64, 0>(pa);
-  }
+  return with_class(p, [&](auto k) { return launch_pass<typename decltype(k)::A, decltype(k)::KSH>(pa); });
+}
+
+/* Where the XCD-local one-launch kernels (team_kernel and its product forms) are built: the FP64 policies and the wide integer policy,
+ * N = 2^15..2^17, from 64 polynomials of the launch on (the eight queues) */
+static bool team_window(const ntt_plan *p, uint64_t polys)
+{
+  const bool int_wide = p->arith == NTT_ARITH_U64 && p->int_cls >= 0;
+  return (p->arith == NTT_ARITH_F64 || int_wide) && p->m >= kTeamBlock + 3 && p->m <= kTeamBlock + 5 && polys >= 64 && polys < (1ull << 29);
+}
+
+/* The one-launch form or the per-chunk launches, for the NTT-domain products: inside the window NTT_OPT_XCD_LOCAL 1 / 0 forces either,
+ * the automatic choice (-1) is the route's own measured rule `pays` */
+template <class Pays> static bool team_pays(const ntt_plan *p, uint64_t polys, int nlimbs, Pays pays)
+{
+  if(!team_window(p, polys) || p->block_log || nlimbs > kMaxLimbs) return false;
+  return p->xcd_local >= 0 ? p->xcd_local == 1 : pays();
 }
 
 /* XCD-local two-pass launches: FP64 policies and the wide integer policy, N = 2^15..2^17, plain calls (canonical in,
@@ -43,10 +62,7 @@ static bool team_applies(const ntt_plan *p, uint64_t batch, bool inverse, bool w
   batch *= (uint64_t)nlimbs; /* polynomials of the launch */
   /* the FP64 policies; transforms (not the product launch) also for the wide integer policy */
   const bool int_wide = p->arith == NTT_ARITH_U64 && p->int_cls >= 0 && !product;
-  if((p->arith != NTT_ARITH_F64 && !int_wide) || p->generic || p->m < kTeamBlock + 3 || p->m > kTeamBlock + 5 || wide || lazy ||
-     batch < 64 || batch >= (1ull << 29)) {
-    return false;
-  }
+  if(!team_window(p, batch) || (p->arith != NTT_ARITH_F64 && !int_wide) || p->generic || wide || lazy) return false;
   const int on = p->xcd_local;
   if(on >= 0) return on == 1;
   /* the wide integer policy (profiles/r04/ab_xcd_int.txt): forward +18..23 % at all three sizes; inverse +15 % at 2^17, none at
@@ -148,6 +164,81 @@ static uint64_t *advance(uint64_t *base, uint64_t words) { return reinterpret_ca
 /* the words between consecutive polynomials of a limb */
 static uint64_t poly_words(const ntt_plan *p, const LimbSet &ls) { return ls.pstride ? ls.pstride : p->N; }
 
+/* ---- launch records (PassArgs, ProdArgs, DotArgs, MulArgs: ntt_kernels_launch.h) ----
+ * What every route sets goes by the same member names in all four: launch_common fills it.  Each kind has ONE builder (launch_one_pass
+ * here, prod_args, dot_args, mul_args beside their routes) that starts from a zeroed record, calls it and adds the kind's operands; a
+ * route then sets only what distinguishes it -- with set_team / set_ptrs, or a plain assignment (block_log, oversub). */
+template <class Args> static void launch_common(Args &x, const ntt_plan *p, const LimbSet &ls, uint64_t batch, void *stream)
+{
+  x.limbs       = ls.d;
+  x.nlimbs      = ls.n;
+  x.limb_stride = ls.stride;
+  x.poly_stride = ls.pstride;
+  x.batch       = batch;
+  x.logn        = (uint32_t)p->m;
+  x.max_grid    = p->max_grid;
+  x.num_cus     = p->num_cus;
+  x.stream      = (hipStream_t)stream;
+}
+/* the XCD-local one-launch form: the stream's control block, `lag` polynomials between the passes of a queue unless NTT_OPT_XCD_LOCAL_LAG
+ * says otherwise, and -- the records that name a block size -- the team kernels' 2^12-point blocks */
+template <class Args> static void set_team(Args &x, const ntt_plan *p, void *ctl, int lag)
+{
+  x.team_ctl = ctl;
+  x.team_lag = p->team_lag ? p->team_lag : lag;
+  x.team_wpc = p->team_wpc;
+  if constexpr(std::is_same_v<Args, DotArgs> || std::is_same_v<Args, MulArgs>) x.block_log = (uint32_t)kTeamBlock;
+}
+/* a pointer batch: the record's operand pointers are DEVICE tables of polynomial addresses, this launch's (first) limb limb_off words
+ * behind every entry */
+template <class Args> static void set_ptrs(Args &x, uint64_t limb_off)
+{
+  x.ptrs         = 1;
+  x.ptr_limb_off = limb_off;
+}
+/* a table where a record has an operand pointer */
+static uint64_t *as_words(const void *table) { return const_cast<uint64_t *>(static_cast<const uint64_t *>(table)); }
+
+/* One pass of a transform -- or a whole transform as one launch (ps.fused 2, 3, 4: PassArgs) -- on nb polynomials starting at d.
+ * team_ctl: the XCD-local launch's control block, with its lag. */
+static int launch_one_pass(const ntt_plan *p, const Pass &ps, uint64_t *d, uint64_t nb, bool inverse, bool wide, bool lazy,
+                           bool ends, void *stream, const LimbSet &ls, bool oversub = true, void *team_ctl = nullptr, int team_lag = 0)
+{
+  PassArgs pa{};
+  launch_common(pa, p, ls, nb, stream);
+  pa.a       = d;
+  pa.ptab    = ls.ptab; /* (a set with a table only ever reaches run_transform: null on the products' column passes, as ever) */
+  pa.fused   = ps.fused;
+  pa.r       = ps.r;
+  pa.s       = ps.s;
+  pa.inverse = inverse;
+  pa.wide    = wide;
+  pa.lastinv = inverse && ps.s == 0;
+  pa.lazy    = lazy;
+  pa.ends    = ends;
+  if(oversub) pa.oversub = p->block_oversub;
+  if(team_ctl) set_team(pa, p, team_ctl, team_lag);
+  return launched(dispatch_pass(p, pa));
+}
+
+/* Multi-pass routes (N > 2^14) run chunk by chunk so that what one pass writes is still in the 256 MiB Infinity Cache when
+ * the next pass reads it: only the first read and the last write of a chunk have to reach HBM.  A chunk of `mib` MiB holds
+ * that many polynomials of EVERY limb; fn(first, nb, off): nb polynomials from the first-th on, off words into every operand. */
+template <class Fn> static int for_chunks(const ntt_plan *p, const LimbSet &ls, uint64_t batch, uint64_t mib, int npasses, Fn fn)
+{
+  uint64_t chunk = batch;
+  if(npasses > 1) {
+    chunk = (mib << 20) / (p->N * sizeof(uint64_t) * (uint64_t)ls.n);
+    if(chunk < 1) chunk = 1;
+    if(chunk > batch) chunk = batch;
+  }
+  for(uint64_t first = 0; first < batch; first += chunk) {
+    const int rc = fn(first, batch - first < chunk ? batch - first : chunk, first * poly_words(p, ls));
+    if(rc) return rc;
+  }
+  return NTT_OK;
+}
+
 static int run_transform(const ntt_plan *p, uint64_t *d_a, uint64_t batch, bool inverse, bool wide, void *stream,
                          bool lazy = false, const LimbSet *set = nullptr)
 {
@@ -165,31 +256,10 @@ static int run_transform(const ntt_plan *p, uint64_t *d_a, uint64_t batch, bool 
    * onepass_small_batches.txt): 64..96 polynomials even, 128 +11 % forward, 192 +11 / +7 %, 255 +25 / +20 %; 32 polynomials -40 % --;
    * smaller batches spread over the chip as 2^12-point blocks through the per-pass launches.  A call that asks for lazy outputs gets this
    * kernel's canonical words: they satisfy the lazy contract ([0,4q) forward, [0,2q) inverse), and one pass with the final reduction
-   * beats two passes without it. */
+   * beats two passes without it (the record's lazy stays 0; so does its oversub). */
   if(p->m == kFusedMax + 1 && p->arith == NTT_ARITH_F64 && !p->generic && ls.n <= kMaxLimbs &&
      one_pass_pays(p, batch * (uint64_t)ls.n)) {
-    PassArgs pa{};
-    pa.a           = d_a;
-    pa.limbs       = ls.d;
-    pa.nlimbs      = ls.n;
-    pa.limb_stride = ls.stride;
-    pa.poly_stride = ls.pstride;
-    pa.ptab        = ls.ptab;
-    pa.batch       = batch;
-    pa.logn        = (uint32_t)p->m;
-    pa.fused       = 4;
-    pa.r           = 1;
-    pa.s           = 0;
-    pa.inverse     = inverse;
-    pa.wide        = wide;
-    pa.lastinv     = inverse;
-    pa.ends        = 1;
-    pa.max_grid    = p->max_grid;
-    pa.num_cus     = p->num_cus;
-    pa.stream      = (hipStream_t)stream;
-    hipError_t e   = dispatch_pass(p, pa);
-    if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return NTT_OK;
+    return launch_one_pass(p, Pass{4, 1, 0}, d_a, batch, inverse, wide, /* lazy */ false, /* ends */ true, stream, ls, /* oversub */ false);
   }
   /* both passes as items of ONE launch with the intermediate kept in each XCD's L2 (ntt_kernels_team.h: team_kernel) */
   void *ctl = nullptr;
@@ -201,36 +271,15 @@ static int run_transform(const ntt_plan *p, uint64_t *d_a, uint64_t batch, bool 
     if(rc) return rc;
   }
   if(ctl) {
-    PassArgs pa{};
-    pa.a           = d_a;
-    pa.limbs       = ls.d;
-    pa.nlimbs      = ls.n;
-    pa.limb_stride = ls.stride;
-    pa.poly_stride = ls.pstride;
-    pa.ptab        = ls.ptab;
-    pa.batch       = batch;
-    pa.logn        = (uint32_t)p->m;
-    pa.fused       = 3;
-    pa.r           = p->m - kTeamBlock;
-    pa.s           = 0;
-    pa.inverse     = inverse;
-    pa.lastinv     = inverse;
-    pa.ends        = 1;
-    pa.max_grid    = p->max_grid;
-    pa.num_cus     = p->num_cus;
-    pa.oversub     = p->block_oversub;
-    pa.team_ctl    = ctl;
     /* polynomials between the two passes of a queue.  The L2 keeps the intermediate while lag x polynomial size stays
      * below about 2.5 MiB (measured, FETCH_SIZE 1.0x the data: 2^15 up to lag 10, 2^16 up to 5, 2^17 not even at 2;
      * profiles/r03/team_kernel_l2_retention.txt), but with four workgroups per CU a lag below 8 makes second-pass items
      * wait: 2^15 gets both (lag 10: 0.43 of the roofline against 0.40-0.41 beyond), 2^16 and 2^17 run fastest at 8-10
      * with the second pass served by the Infinity Cache (profiles/r03/sweep_xcd_local_lag.txt) */
-    pa.team_lag    = p->team_lag ? p->team_lag : (p->m == kTeamBlock + 4 ? 8 : 10);
-    pa.team_wpc    = p->team_wpc;
-    pa.stream      = (hipStream_t)stream;
-    hipError_t e   = dispatch_pass(p, pa);
-    if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return NTT_OK;
+    const int lag = p->m == kTeamBlock + 4 ? 8 : 10;
+    /* (team_applies: canonical in, canonical out) */
+    return launch_one_pass(p, Pass{3, p->m - kTeamBlock, 0}, d_a, batch, inverse, /* wide */ false, /* lazy */ false, /* ends */ true, stream, ls,
+                           /* oversub */ true, ctl, lag);
   }
   /* the one-launch two-phase kernel owns a CU per polynomial: it only pays when the batch fills the chip (measured +3 % at
    * batch ~30k; a batch below the CU count would leave CUs idle where the per-pass launches spread one polynomial
@@ -240,73 +289,22 @@ static int run_transform(const ntt_plan *p, uint64_t *d_a, uint64_t batch, bool 
   if((p->two_phase == 1 || tp_auto) && ls.n == 1 && !p->generic && p->arith == NTT_ARITH_F64 && p->m >= kFusedMax + 2 &&
      p->m <= kFusedMax + 3) {
     /* one launch, one workgroup per polynomial, both passes back to back (ntt_kernels_block.h: twophase_kernel) */
-    PassArgs pa{};
-    pa.a        = d_a;
-    pa.limbs    = ls.d;
-    pa.nlimbs   = ls.n;
-    pa.limb_stride = ls.stride;
-    pa.poly_stride = ls.pstride;
-    pa.ptab     = ls.ptab;
-    pa.batch    = batch;
-    pa.logn     = (uint32_t)p->m;
-    pa.fused    = 2;
-    pa.r        = p->m - kFusedMax;
-    pa.s        = 0;
-    pa.inverse  = inverse;
-    pa.wide     = wide;
-    pa.lastinv  = inverse;
-    pa.lazy     = lazy;
-    pa.ends     = 1;
-    pa.max_grid = p->max_grid;
-    pa.num_cus  = p->num_cus;
-    pa.oversub  = p->block_oversub;
-    pa.stream   = (hipStream_t)stream;
-    hipError_t e = dispatch_pass(p, pa);
-    if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return NTT_OK;
+    return launch_one_pass(p, Pass{2, p->m - kFusedMax, 0}, d_a, batch, inverse, wide, lazy, /* ends */ true, stream, ls);
   }
-  /* Multi-pass transforms (N > 2^14) are run chunk by chunk so that what one pass
-   * writes is still in the 256 MiB Infinity Cache when the next pass reads it:
-   * only the first read and the last write of a chunk have to reach HBM. */
-  uint64_t chunk = batch;
-  if(L.n > 1) {
-    const uint64_t budget = (uint64_t)p->chunk_mib << 20;
-    chunk                 = budget / (p->N * sizeof(uint64_t) * (uint64_t)ls.n); /* a chunk holds this many polynomials of EVERY limb */
-    if(chunk < 1) chunk = 1;
-    if(chunk > batch) chunk = batch;
-  }
-  for(uint64_t first = 0; first < batch; first += chunk) {
-    const uint64_t nb = batch - first < chunk ? batch - first : chunk;
+  return for_chunks(p, ls, batch, (uint64_t)p->chunk_mib, L.n, [&](uint64_t first, uint64_t nb, uint64_t off) -> int {
+    /* a chunk starts `first` polynomials in: that many strides -- or table entries, the data pointer unmoved -- further */
+    LimbSet cs = ls;
+    if(ls.ptab) cs.ptab = ls.ptab + first;
+    uint64_t *const d = ls.ptab ? d_a : d_a + off;
     for(int k = 0; k < L.n; k++) {
       const Pass &ps = L.p[inverse ? L.n - 1 - k : k];
-      PassArgs    pa{};
-      /* a chunk starts `first` polynomials in: that many strides -- or table entries -- further */
-      pa.a        = ls.ptab ? d_a : d_a + first * poly_words(p, ls);
-      pa.ptab     = ls.ptab ? ls.ptab + first : nullptr;
       /* (radix-4 inverse: a pass that does not end the transform multiplies by 1, not by N^-1) */
-      pa.limbs    = p->arith == NTT_ARITH_U64_R4 && inverse && ps.s != 0 ? (const void *)p->limbrec_mid.data() : ls.d;
-      pa.nlimbs   = ls.n;
-      pa.limb_stride = ls.stride;
-      pa.poly_stride = ls.pstride;
-      pa.lazy     = lazy;
-      pa.ends     = k == L.n - 1;
-      pa.batch    = nb;
-      pa.logn     = (uint32_t)p->m;
-      pa.fused    = ps.fused;
-      pa.r        = ps.r;
-      pa.s        = ps.s;
-      pa.inverse  = inverse;
-      pa.wide     = wide && k == 0;
-      pa.lastinv  = inverse && ps.s == 0;
-      pa.max_grid = p->max_grid;
-      pa.num_cus  = p->num_cus;
-      pa.oversub  = p->block_oversub;
-      pa.stream   = (hipStream_t)stream;
-      hipError_t e = dispatch_pass(p, pa);
-      if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+      cs.d = p->arith == NTT_ARITH_U64_R4 && inverse && ps.s != 0 ? (const void *)p->limbrec_mid.data() : ls.d;
+      const int rc = launch_one_pass(p, ps, d, nb, inverse, wide && k == 0, lazy, k == L.n - 1, stream, cs);
+      if(rc) return rc;
     }
-  }
-  return NTT_OK;
+    return NTT_OK;
+  });
 }
 
 extern "C" int ntt_fwd_batch(const ntt_plan *p, uint64_t *d_a, uint64_t batch, void *stream)

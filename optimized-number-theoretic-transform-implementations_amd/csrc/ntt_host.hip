@@ -88,6 +88,12 @@ static int fail(int code, const std::string &msg)
   g_err = msg;
   return code;
 }
+/* what a launcher returned, as the status of the call */
+static int launched(hipError_t e)
+{
+  if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+  return NTT_OK;
+}
 
 #define HIP_TRY(expr)                                                                         \
   do {                                                                                        \
