@@ -19,6 +19,7 @@ OBJS     = $(CSRC)/inst_f64k0.o $(CSRC)/inst_f64k1.o $(CSRC)/inst_f64k18.o $(CSR
            $(CSRC)/inst_team_f64k0.o $(CSRC)/inst_team_f64k1.o $(CSRC)/inst_team_f64k18.o $(CSRC)/inst_team_f64w.o \
            $(CSRC)/rescale_f64k0.o $(CSRC)/rescale_f64k1.o $(CSRC)/rescale_f64k18.o $(CSRC)/rescale_f64w.o $(CSRC)/rescale_coef.o \
            $(CSRC)/lift_f64k0.o $(CSRC)/lift_f64k1.o $(CSRC)/lift_f64k18.o $(CSRC)/lift_f64w.o $(CSRC)/lift.o \
+           $(CSRC)/sample_f64k0.o $(CSRC)/sample_f64k1.o $(CSRC)/sample_f64k18.o $(CSRC)/sample_f64w.o $(CSRC)/sample.o \
            $(CSRC)/slots_f64k0.o $(CSRC)/slots_f64k1.o $(CSRC)/slots_f64k18.o $(CSRC)/slots_f64w.o $(CSRC)/slots.o \
            $(CSRC)/keyswitch_f64k0.o $(CSRC)/keyswitch_f64k1.o $(CSRC)/keyswitch_f64k18.o $(CSRC)/keyswitch_f64w.o $(CSRC)/keyswitch_coef.o \
            $(CSRC)/modup_mul_f64k0.o $(CSRC)/modup_mul_f64k1.o $(CSRC)/modup_mul_f64k18.o $(CSRC)/modup_mul_f64w.o \

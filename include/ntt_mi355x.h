@@ -157,6 +157,11 @@ typedef enum ntt_option {
                           * policies, N = 2^6..2^14): ONE launch, the slot permutation applied by the transform's own loads / stores;
                           * 0 = the composition everywhere (the element-wise permutation launch and the plan's transform in place);
                           * -1 (default) = the rule quoted at ntt_slots_encode_batch.  Results are identical */
+  NTT_OPT_SAMPLE_FUSED = 24, /* ntt_rns_sample_batch with NTT_SAMPLE_TRANSFORMED: 1 = every run of limbs the fused kernel is built for (FP64
+                          * policies, N = 2^6..2^14) takes it: one forward-transform launch with the generator in its prologue; 0 = every
+                          * run takes the composition (the element-wise launch, then the forward transform; accumulating, the inverse
+                          * transform first); -1 (default) = the rule quoted at ntt_rns_sample_batch.  Read from plans[0]; results are
+                          * identical */
   NTT_OPT_FUSED_PRODUCT = 5 /* N = 2^8..2^17, FP64: 1 (default) = ntt_negacyclic_mul_batch as ONE launch that takes both
                           * operands through the forward stages, multiplies in registers and runs the inverse: 24N bytes up to
                           * 2^14; from 2^23 coefficients per operand of N >= 2^15 on likewise one launch (all limbs of an RNS set
@@ -819,7 +824,10 @@ NTT_API int ntt_rns_to_double_batch_strided(int nlimbs, ntt_plan *const *plans, 
  * polynomial) ranges overlap, or a plaintext stride below N; the overlap above; NTT_LIFT_TRANSFORMED with a plan that lacks the
  * forward table (composition with NTT_LIFT_ACCUMULATE: or the inverse table).
  *
- * Recipes (Delta = floor(Q / t) for BFV, the scale for CKKS; u, e0, e1 sampled by the caller; pk^ in the NTT domain):
+ * Recipes (Delta = floor(Q / t) for BFV, the scale for CKKS; pk^ in the NTT domain; u^, e0^, e1^ drawn by ntt_rns_sample_batch below --
+ * u^: NTT_SAMPLE_TERNARY with NTT_SAMPLE_TRANSFORMED; + e0^: NTT_SAMPLE_CBD21 with NTT_SAMPLE_TRANSFORMED | NTT_SAMPLE_ACCUMULATE onto
+ * pk0^ (.) u^ (BGV: mult = t), each under a seed or a first_poly range of its own -- or sampled by a caller that needs a CSPRNG and
+ * uploaded through the lifts):
  *     BFV encrypt    c0^ = pk0^ (.) u^ + e0^ by the products above, then
  *                    ntt_rns_from_plain_batch(L, plans, d_c0, d_m, t, batch, NTT_LIFT_SCALE | NTT_LIFT_TRANSFORMED | NTT_LIFT_ACCUMULATE, s)
  *     BGV encrypt    c0^ = pk0^ (.) u^ + t e0^, then from_plain(.., NTT_LIFT_TRANSFORMED | NTT_LIFT_ACCUMULATE, s)
@@ -843,6 +851,65 @@ NTT_API int ntt_rns_from_double_batch(int nlimbs, ntt_plan *const *plans, uint64
 NTT_API int ntt_rns_from_double_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, const double *d_y, double scale,
                                               uint64_t c_limb_stride, uint64_t c_poly_stride, uint64_t y_poly_stride, uint64_t batch,
                                               unsigned flags, void *stream);
+
+/* ---- random polynomials in the RNS, drawn on the device: secrets, masks and noise of key generation and encryption without a host
+ * round trip per polynomial.  d_c ([limb][batch][N]) receives one canonical word per limb and coefficient; nothing is read.  Any limb
+ * count (16 limbs per launch), every q_l < 2^61.  Integer arithmetic only: the definition (csrc/ntt_sample.h) fixes every output word
+ * on every route.
+ *
+ * NOT A CRYPTOGRAPHIC GENERATOR: Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3") is a statistical,
+ * counter-based generator.  The calls serve reproducible workloads, benchmarks, tests and simulation; a deployment that needs a CSPRNG
+ * keeps sampling on its side and uses the lifts above.
+ *
+ * ONE 128-bit block per output coefficient, independent of layout, batch split, launch chunking and route:
+ *     key = (seed & 0xffffffff, seed >> 32),   counter = (s, P & 0xffffffff, P >> 32, tag)
+ *   s the coefficient's position in [0, N); P = first_poly + p mod 2^64, p the polynomial's index in the call; tag = the kind for the
+ *   small kinds, 2 | (l << 8) for the uniform kind, l the limb's index in plans.  A batch of 5 at first_poly = F is the batch of 2 at F
+ *   followed by the batch of 3 at F + 2.  Callers separate u, e0, e1, ... by seed or by disjoint first_poly ranges.  out0..out3: the block.
+ *     NTT_SAMPLE_TERNARY   v = mulhi64(out0 | out1 << 32, 3) - 1 in {-1, 0, 1}, each with probability 1/3 within 2^-64
+ *     NTT_SAMPLE_CBD21     v = popcount(out0 & 0x1FFFFF) - popcount(out1 & 0x1FFFFF): centred binomial, eta = 21, sigma = sqrt(10.5) = 3.24
+ *                          (the HE-standard error width), |v| <= 21
+ *                          both: c_l = [mult v]_{q_l}, the SAME v in every limb; 1 <= mult < 2^61 (1: plain noise; t: BGV's t e)
+ *     NTT_SAMPLE_UNIFORM   c_l = (out0 | out1 << 32 | out2 << 64 | out3 << 96) mod q_l, the limbs independent through the tag; the bias
+ *                          is below 2^-67; mult must be 1.  Uniform is uniform in either domain: NTT_SAMPLE_TRANSFORMED is accepted
+ *                          and changes nothing.
+ * Flags:
+ *     NTT_SAMPLE_TRANSFORMED   the output is in the NTT domain, canonical words (the small kinds: the forward transform of the sample)
+ *     NTT_SAMPLE_ACCUMULATE    c_l <- c_l + the sample (mod q_l); c canonical and in the domain the call writes
+ * _strided: d_c's limbs c_limb_stride and polynomials c_poly_stride words apart (any strides the other RNS forms accept).
+ * Routes: coefficients (and the uniform kind always) -- one element-wise launch per 16 limbs, sample_coef_kernel (every policy, every
+ * N >= 2, NTT_OPT_MAX_GRID of plans[0] honoured), 8NL bytes per polynomial (16NL accumulating).  NTT_SAMPLE_TRANSFORMED with a small
+ * kind -- per run of compatible limbs ONE launch of the forward transform with the generator in its prologue and the addition in its
+ * epilogue (sample_fwd_kernel; FP64 policies, N = 2^6..2^14), or the composition: the element-wise launch and the run's forward
+ * transform in place; accumulating: the run's inverse transform, the accumulating element-wise launch, the forward transform.  Both
+ * give the same words.  NTT_OPT_SAMPLE_FUSED on plans[0]: 1 / 0 force the fused kernel (where built) / the composition for every run;
+ * the default, -1, follows the measurement (profiles/r23/sample_bench.txt; the rule with its figures: csrc/host/host_sample.inc):
+ * 2^13 and 2^14, L = 1, 4, 16 of 24 50-bit primes, 64 / 1024 polynomials, composition time / fused time as ranges over five rounds, a
+ * figure's own spread 1.00-1.08): the fused kernel when accumulating (1.46-2.34 x the composition's rate) and, storing, for every run of
+ * two or more limbs (1.05-1.38 x; 0.98-1.02 x, not different, at 2^14 x 16 limbs x 64 polynomials) and for a single limb at 2^14
+ * (1.09-1.44 x); a single-limb run through N = 2^13 stores through the composition (1.47-1.53 x at 1024 polynomials but 0.94-0.97 x at 64).
+ * The coefficient kernel reaches 0.28-0.93 (uniform: 0.23-0.74) of ntt_copy_probe's rate at 8NL bytes per polynomial, the fused kernel
+ * 0.14-0.49 at its own; against small values drawn with torch and lifted by ntt_rns_from_plain_batch the fused kernel takes
+ * 1/1.11-1/2.43 (ternary) and 1/2.27-1/20.4 (centred binomial) of the time.
+ * Allocates nothing, does not synchronise the host, issues no memset: capturable.
+ * NTT_ERR_ARG, nothing written: plans that differ in N or device; a prime >= 2^61; an unknown kind or flag; mult = 0 or >= 2^61;
+ * mult != 1 with the uniform kind; a null d_c with batch > 0; strides under which two (limb, polynomial) ranges overlap;
+ * NTT_SAMPLE_TRANSFORMED with a small kind and a plan that lacks the forward table (composition with NTT_SAMPLE_ACCUMULATE: or the
+ * inverse table).
+ *
+ * Recipe, key generation (RLWE):  s^ = sample(TERNARY, NTT_SAMPLE_TRANSFORMED),  a^ = sample(UNIFORM),  then b^ = -a^ (.) s^ + e^:
+ *     ntt_rns_lincomb_batch / the NTT-domain products for -a^ (.) s^, then sample(CBD21, NTT_SAMPLE_TRANSFORMED | NTT_SAMPLE_ACCUMULATE)
+ * (examples/rns_sample.c). ---- */
+enum { NTT_SAMPLE_TERNARY = 0, NTT_SAMPLE_CBD21 = 1, NTT_SAMPLE_UNIFORM = 2 };
+enum {
+  NTT_SAMPLE_TRANSFORMED = 2, /* the output is in the NTT domain (the NTT_LIFT_* bit values) */
+  NTT_SAMPLE_ACCUMULATE  = 4  /* c_l <- c_l + the sample */
+};
+NTT_API int ntt_rns_sample_batch(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, int kind, uint64_t mult, uint64_t seed,
+                                 uint64_t first_poly, uint64_t batch, unsigned flags, void *stream);
+NTT_API int ntt_rns_sample_batch_strided(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, int kind, uint64_t mult, uint64_t seed,
+                                         uint64_t first_poly, uint64_t c_limb_stride, uint64_t c_poly_stride, uint64_t batch,
+                                         unsigned flags, void *stream);
 
 /* ---- BFV / BGV slots: encode and decode, fused with the transform mod t.  Everything above speaks of a plaintext as N coefficients
  * mod t; a BFV / BGV user holds N SLOTS, a 2 x N/2 matrix of values mod t.  pt is a plan for (N, t, psi): t prime, 2N | t - 1, psi its

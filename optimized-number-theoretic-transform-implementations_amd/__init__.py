@@ -50,6 +50,7 @@ OPT_MODDOWN_ADD_FUSED = 20
 OPT_BGV_FUSED = 21
 OPT_LIFT_FUSED = 22
 OPT_SLOTS_FUSED = 23
+OPT_SAMPLE_FUSED = 24
 RESCALE_TRANSFORMED, RESCALE_FLOOR = 1, 2
 MODUP_TRANSFORMED = 1
 MODDOWN_TRANSFORMED, MODDOWN_FLOOR, MODDOWN_ACCUMULATE = 1, 2, 4
@@ -57,6 +58,8 @@ GALOIS_TRANSFORMED, GALOIS_ACCUMULATE, GALOIS_KEY_BROADCAST = 1, 2, 4
 LINCOMB_ACCUMULATE, LINCOMB_M_BROADCAST, LINCOMB_LAZY_IN = 1, 2, 4
 PLAIN_SCALE = 1
 LIFT_SCALE, LIFT_TRANSFORMED, LIFT_ACCUMULATE = 1, 2, 4
+SAMPLE_TERNARY, SAMPLE_CBD21, SAMPLE_UNIFORM = 0, 1, 2
+SAMPLE_TRANSFORMED, SAMPLE_ACCUMULATE = 2, 4
 
 #: every symbol include/ntt_mi355x.h and the reference-named headers declare
 EXPORTED_SYMBOLS = [
@@ -80,6 +83,7 @@ EXPORTED_SYMBOLS = [
     "ntt_rns_galois_dot_batch_strided", "ntt_rns_lincomb_batch", "ntt_rns_lincomb_batch_strided",
     "ntt_rns_to_plain_batch", "ntt_rns_to_plain_batch_strided", "ntt_rns_to_double_batch", "ntt_rns_to_double_batch_strided",
     "ntt_rns_from_plain_batch", "ntt_rns_from_plain_batch_strided", "ntt_rns_from_double_batch", "ntt_rns_from_double_batch_strided",
+    "ntt_rns_sample_batch", "ntt_rns_sample_batch_strided",
     "ntt_plan_enable_slots", "ntt_slot_position", "ntt_slots_encode_batch", "ntt_slots_encode_batch_strided", "ntt_slots_decode_batch",
     "ntt_slots_decode_batch_strided",
     "ntt_transform_batch_strided", "ntt_transform_ptrs", "ntt_rns_transform_ptrs", "ntt_transform_dev_ptrs", "ntt_rns_transform_dev_ptrs", "ntt_inv_dot_dev_ptrs", "ntt_fwd_mul_dev_ptrs", "ntt_negacyclic_mul_dev_ptrs",
@@ -226,6 +230,9 @@ _sig("ntt_rns_from_plain_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOI
 _sig("ntt_rns_from_double_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_double, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_from_double_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, VOIDP, C.c_double, C.c_uint64, C.c_uint64, C.c_uint64,
      C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_sample_batch", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
+_sig("ntt_rns_sample_batch_strided", C.c_int, C.c_int, C.POINTER(VOIDP), VOIDP, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+     C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_transform_batch_strided", C.c_int, VOIDP, VOIDP, C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_transform_ptrs", C.c_int, VOIDP, C.POINTER(VOIDP), C.c_uint64, C.c_uint, VOIDP)
 _sig("ntt_rns_transform_ptrs", C.c_int, C.c_int, C.POINTER(VOIDP), C.POINTER(VOIDP), C.c_uint64, C.c_uint64, C.c_uint, VOIDP)
@@ -862,6 +869,18 @@ def rns_from_double(plans, dc, dy, scale, batch, flags=0, stream=None, layout=No
         _check(_lib.ntt_rns_from_double_batch_strided(len(plans), _plan_array(plans), dc, dy, scale, layout[0], layout[1], layout[2], batch,
                                                       flags, stream))
     else: _check(_lib.ntt_rns_from_double_batch(len(plans), _plan_array(plans), dc, dy, scale, batch, flags, stream))
+
+
+def rns_sample(plans, dc, kind, seed, batch, first_poly=0, mult=1, flags=0, stream=None, layout=None):
+    """random polynomials drawn on the device: dc ([limb][batch][N], canonical) = one word per limb and coefficient from the Philox4x32-10
+    block of (seed, first_poly + polynomial, position) -- a statistical generator, not a cryptographic one.  SAMPLE_TERNARY / SAMPLE_CBD21:
+    [mult v]_q of the same small v in every limb; SAMPLE_UNIFORM: the block mod q, independent per limb (mult = 1).  SAMPLE_TRANSFORMED:
+    dc in the NTT domain; SAMPLE_ACCUMULATE: dc += the sample.  layout = (c_limb_stride, c_poly_stride) in words for any other
+    placement; OPT_SAMPLE_FUSED on plans[0] selects the NTT-domain route"""
+    a = (len(plans), _plan_array(plans), dc, kind, mult, seed & (2 ** 64 - 1), first_poly & (2 ** 64 - 1))
+    if layout:
+        _check(_lib.ntt_rns_sample_batch_strided(*a, layout[0], layout[1], batch, flags, stream))
+    else: _check(_lib.ntt_rns_sample_batch(*a, batch, flags, stream))
 
 
 def slot_position(n, i):

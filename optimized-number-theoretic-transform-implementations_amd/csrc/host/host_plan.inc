@@ -183,6 +183,8 @@ struct ntt_plan {
                                       * everywhere, -1 = the default rule (lift_fused_applies); plans[0] */
   int              slots_fused = -1; /* ntt_slots_encode_batch, ntt_slots_decode_batch: 1 = slots_inv_kernel / slots_fwd_kernel where they are
                                       * built, 0 = the composition everywhere, -1 = the default rule (slots_fused_applies) */
+  int              sample_fused = -1; /* ntt_rns_sample_batch with NTT_SAMPLE_TRANSFORMED: 1 = sample_fwd_kernel where it is built, 0 = the
+                                      * composition everywhere, -1 = the default rule (sample_fused_applies); plans[0] */
   uint32_t *       d_pos  = nullptr; /* slot tables (ntt_plan_enable_slots; ntt_slots.h): pos and its inverse, N words each; null */
   uint32_t *       d_ipos = nullptr; /* until enabled */
   int              block_oversub = 0; /* persistent block kernels: workgroups per resident slot (0 = the kernels' defaults) */
@@ -613,6 +615,9 @@ extern "C" int ntt_plan_set_option(ntt_plan *p, int option, int64_t value)
     case NTT_OPT_SLOTS_FUSED:
       p->slots_fused = value < 0 ? -1 : (value != 0);
       return NTT_OK;
+    case NTT_OPT_SAMPLE_FUSED:
+      p->sample_fused = value < 0 ? -1 : (value != 0);
+      return NTT_OK;
     case NTT_OPT_MAX_BATCH_HINT:
       if(value < 0) return fail(NTT_ERR_ARG, "batch hint must be >= 0");
       {
@@ -713,6 +718,7 @@ extern "C" int ntt_plan_get_option(const ntt_plan *p, int option, int64_t *value
     case NTT_OPT_BGV_FUSED: *value = p->bgv_fused; return NTT_OK;
     case NTT_OPT_LIFT_FUSED: *value = p->lift_fused; return NTT_OK;
     case NTT_OPT_SLOTS_FUSED: *value = p->slots_fused; return NTT_OK;
+    case NTT_OPT_SAMPLE_FUSED: *value = p->sample_fused; return NTT_OK;
     case NTT_OPT_MAX_BATCH_HINT: *value = (int64_t)p->batch_hint; return NTT_OK;
     case NTT_OPT_CTL_ALLOCATIONS: {
       std::lock_guard<std::mutex> lock(p->team_mu);

@@ -29,6 +29,7 @@
 #include "ntt_lincomb.h"
 #include "ntt_plain.h"
 #include "ntt_lift.h"
+#include "ntt_sample.h"
 #include "ntt_slots.h"
 #include "ntt_rescale.h"
 #include "ntt_tables.h"
@@ -158,6 +159,7 @@ static int check_device(int device)
 #include "host/host_lincomb.inc"
 #include "host/host_plain.inc"
 #include "host/host_lift.inc"
+#include "host/host_sample.inc"
 #include "host/host_slots.inc"
 #include "host/host_runtime.inc"
 #include "host/host_compat.inc"

@@ -1,0 +1,6 @@
+/* sample_f64k0.hip -- instantiates the fused sampling kernels (sample_fwd_kernel, N = 2^6..2^14) for (ArithF64, headroom class 0). */
+#include "ntt_kernels_sample.h"
+
+namespace ntt {
+NTT_DEFINE_LAUNCH_SAMPLE_FWD(ArithF64, 0)
+} /* namespace ntt */
