@@ -3,19 +3,9 @@
  * compiled by itself.  The kernels are in lift.hip and the lift_f64*.hip units; this section sees their launchers and argument records
  * only (ntt_lift.h, which states the arithmetic).
  *
- *   coefficients   lift_coef_kernel, one launch per 16 limbs (the plaintext word read once per launch): 8N(L + 1) bytes, 8N(2L + 1)
- *                  accumulating; integer arithmetic of its own for every policy and every N >= 2.
- *   NTT domain     per run of compatible limbs (rns_runs):
- *                  fused        FP64 policies at N = 2^6..2^14, where NTT_OPT_LIFT_FUSED on plans[0] allows it: ONE lift_fwd_kernel
- *                               launch, 8N + 8NL bytes (16NL accumulating);
- *                  composition  anything else (integer or radix-4 plans, N < 2^6, N >= 2^15, NTT_OPT_LIFT_FUSED 0): lift_coef_kernel and
- *                               the forward transform over the run in place; accumulating, the inverse transform over the run first
- *                               (c is canonical on both sides of every step, so the words are those of the fused kernel).
- * Everything is checked before the first launch.  Nothing is allocated, the host is not synchronised and no memset is issued: the calls
- * can be captured into a graph. */
-
-/* where the fused kernel is built */
-static bool lift_fused_built(const ntt_plan *p) { return p->arith == NTT_ARITH_F64 && !p->generic && p->m >= kFusedMin && p->m <= kFusedMax; }
+ * The route is produce_route (host_produce.inc) with lift_coef_kernel -- the plaintext word read once per launch: 8N(L + 1) bytes,
+ * 8N(2L + 1) accumulating -- and lift_fwd_kernel, 8N + 8NL bytes (16NL accumulating), where NTT_OPT_LIFT_FUSED on plans[0] allows it.
+ * This section keeps the lifts' own checks, the rule of that option and the constants. */
 
 /* The automatic choice (NTT_OPT_LIFT_FUSED -1), from profiles/r19/lift_bench.txt (a): 50-bit primes, t = 65537, 2^13 and 2^14, L = 1, 4, 16,
  * 64 and 1024 polynomials, composition time / fused time as ranges over five rounds of alternating processes; a figure's own spread over
@@ -32,7 +22,7 @@ static bool lift_fused_built(const ntt_plan *p) { return p->arith == NTT_ARITH_F
  * prologue's integer work is not hidden behind the stages.  That is what the storing rows lose on, and it is untuned. */
 static bool lift_fused_applies(const ntt_plan *p0, const ntt_plan *p, uint32_t mode, bool acc)
 {
-  if(!lift_fused_built(p)) return false;
+  if(!produce_fused_built(p)) return false;
   if(p0->lift_fused >= 0) return p0->lift_fused == 1;
   return acc || (mode == kLiftCentred && p->m <= 13);
 }
@@ -50,51 +40,6 @@ static LiftLimb lift_limb(uint64_t q, uint32_t mode, uint64_t t, uint64_t r)
   return l;
 }
 
-static int lift_coef_launch(ntt_plan *const *plans, int first, int n, uint64_t *d_c, const uint64_t *d_m, const LiftCall &call,
-                            const LiftLimb *ll, uint64_t batch, void *stream, const Layout &lay, uint64_t m_poly_stride)
-{
-  LiftCoefArgs la{};
-  la.c             = d_c + (uint64_t)first * lay.limb;
-  la.m             = d_m;
-  la.limb_stride   = lay.limb;
-  la.poly_stride   = lay.poly;
-  la.m_poly_stride = m_poly_stride;
-  la.batch         = batch;
-  la.logn          = (uint32_t)plans[0]->m;
-  la.nlimbs        = n;
-  la.call          = call;
-  for(int i = 0; i < n; i++) la.limbs[i] = ll[first + i];
-  la.max_grid = plans[0]->max_grid;
-  la.stream   = (hipStream_t)stream;
-  const hipError_t e = launch_lift_coef(la);
-  if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("lift_coef_kernel: ") + hipGetErrorString(e));
-  return NTT_OK;
-}
-
-static int lift_fwd_launch(ntt_plan *const *plans, int first, int n, uint64_t *d_c, const uint64_t *d_m, const LiftCall &call,
-                           const LiftLimb *ll, uint64_t batch, void *stream, const Layout &lay, uint64_t m_poly_stride)
-{
-  const std::vector<unsigned char> recs = rns_records(plans, first, n);
-  LiftFwdArgs                      la{};
-  la.c             = d_c + (uint64_t)first * lay.limb;
-  la.m             = d_m;
-  la.limbs         = recs.data();
-  la.nlimbs        = n;
-  la.limb_stride   = lay.limb;
-  la.poly_stride   = lay.poly;
-  la.m_poly_stride = m_poly_stride;
-  la.batch         = batch;
-  la.logn          = (uint32_t)plans[first]->m;
-  la.call          = call;
-  for(int i = 0; i < n; i++) la.ll[i] = ll[first + i];
-  la.max_grid = plans[first]->max_grid;
-  la.num_cus  = plans[first]->num_cus;
-  la.stream   = (hipStream_t)stream;
-  const hipError_t e = with_f64_class(run_class(plans, first, n), [&](auto k) { return launch_lift_fwd<typename decltype(k)::A, decltype(k)::KSH>(la); });
-  if(e != hipSuccess) return fail(NTT_ERR_HIP, std::string("lift_fwd_kernel: ") + hipGetErrorString(e));
-  return NTT_OK;
-}
-
 /* both calls: d_m is the plaintext as words (the double mode's are bit patterns) */
 static int rns_lift(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, const uint64_t *d_m, uint32_t mode, uint64_t t, double scale,
                     uint64_t batch, unsigned flags, void *stream, const Layout &lay, uint64_t m_poly_stride)
@@ -102,72 +47,49 @@ static int rns_lift(int nlimbs, ntt_plan *const *plans, uint64_t *d_c, const uin
   const unsigned known = NTT_LIFT_TRANSFORMED | NTT_LIFT_ACCUMULATE | (mode == kLiftDouble ? 0u : (unsigned)NTT_LIFT_SCALE);
   if(flags & ~known) return fail(NTT_ERR_ARG, mode == kLiftDouble && (flags & NTT_LIFT_SCALE) ? "from_double: NTT_LIFT_SCALE is from_plain's" : "unknown flag");
   if(mode != kLiftDouble && (t < 2 || t >= (1ull << 61))) return fail(NTT_ERR_ARG, "from_plain: the plaintext modulus must satisfy 2 <= t < 2^61");
-  int rc = rns_check(nlimbs, plans);
-  if(rc) return rc;
-  if(plans[0]->m < 1 || plans[0]->m > 30) return fail(NTT_ERR_ARG, "lift: N out of range");
   if(flags & NTT_LIFT_SCALE) mode = kLiftScaled;
-  for(int l = 0; l < nlimbs; l++) {
-    if(plans[l]->q >= (1ull << 61)) return fail(NTT_ERR_ARG, "lift: every prime must be below 2^61");
-    if(mode == kLiftScaled && t % plans[l]->q == 0) return fail(NTT_ERR_ARG, "from_plain: NTT_LIFT_SCALE needs every prime coprime to t");
-  }
-  if(batch > 0 && (!d_c || !d_m)) return fail(NTT_ERR_ARG, "null argument");
-  const uint64_t N = plans[0]->N;
-  rc               = layout_check(N, nlimbs, batch, lay);
+  const int rc = produce_check("lift", nlimbs, plans, d_c && d_m, batch, lay, [&](int l) {
+    return mode == kLiftScaled && t % plans[l]->q == 0 ? "from_plain: NTT_LIFT_SCALE needs every prime coprime to t" : nullptr;
+  });
   if(rc) return rc;
+  const uint64_t N = plans[0]->N;
   if(m_poly_stride < N || m_poly_stride > (1ull << 40)) return fail(NTT_ERR_ARG, "layout: the plaintext's polynomial stride must be N .. 2^40 words");
-  const bool ntt_dom = (flags & NTT_LIFT_TRANSFORMED) != 0;
-  const bool acc     = (flags & NTT_LIFT_ACCUMULATE) != 0;
-  const std::vector<std::pair<int, int>> runs = rns_runs(nlimbs, plans);
-  if(ntt_dom) {
-    /* every table the call will need, before anything is written */
-    for(const std::pair<int, int> &run : runs) {
-      const bool fused = lift_fused_applies(plans[0], plans[run.first], mode, acc);
-      for(int l = run.first; l < run.first + run.second; l++) {
-        if(!plans[l]->has_fwd) return fail(NTT_ERR_ARG, "lift: a limb's plan lacks the forward table");
-        if(!fused && acc && !plans[l]->has_inv) return fail(NTT_ERR_ARG, "lift: a limb's plan lacks the inverse table (composed accumulation)");
-      }
-    }
-  }
-  if(batch == 0) return NTT_OK;
+  const bool acc = (flags & NTT_LIFT_ACCUMULATE) != 0;
   /* in the fused route another limb's workgroup may still be reading the plaintext: no overlap at all */
-  if(galois_overlap(galois_span(d_m, N, 1, batch, 0, m_poly_stride), galois_span(d_c, N, nlimbs, batch, lay.limb, lay.poly)))
-    return fail(NTT_ERR_ARG, "lift: the plaintext overlaps the output");
-  LiftCall call{};
-  call.mode       = mode;
-  call.accumulate = acc ? 1u : 0u;
-  call.scale      = scale;
-  call.td         = plain_dst(mode == kLiftDouble ? 2 : t, 0);
+  const bool overlap = batch > 0 && galois_overlap(galois_span(d_m, N, 1, batch, 0, m_poly_stride), galois_span(d_c, N, nlimbs, batch, lay.limb, lay.poly));
+  LiftArgs la{};
+  la.m               = d_m;
+  la.m_poly_stride   = m_poly_stride;
+  la.call.mode       = mode;
+  la.call.accumulate = acc ? 1u : 0u;
+  la.call.scale      = scale;
+  la.call.td         = plain_dst(mode == kLiftDouble ? 2 : t, 0);
   if(mode != kLiftDouble) {
-    call.half_dn = t / 2;
-    call.half_up = t - t / 2;
-    uint64_t r   = 1 % t;
+    la.call.half_dn = t / 2;
+    la.call.half_up = t - t / 2;
+    uint64_t r      = 1 % t;
     for(int l = 0; l < nlimbs; l++) r = (uint64_t)((unsigned __int128)r * (plans[l]->q % t) % t);
-    call.r = r; /* Q mod t */
+    la.call.r = r; /* Q mod t */
   }
   std::vector<LiftLimb> ll((size_t)nlimbs);
-  for(int l = 0; l < nlimbs; l++) ll[(size_t)l] = lift_limb(plans[l]->q, mode, t, call.r);
-  USE_DEVICE(plans[0]->device);
-  if(!ntt_dom) {
-    for(int first = 0; !rc && first < nlimbs; first += kLiftLimbs) {
-      rc = lift_coef_launch(plans, first, nlimbs - first < kLiftLimbs ? nlimbs - first : kLiftLimbs, d_c, d_m, call, ll.data(), batch, stream, lay,
-                            m_poly_stride);
-    }
-    return rc;
-  }
-  const Layout one{lay.limb, lay.poly};
-  for(const std::pair<int, int> &run : runs) {
-    if(rc) break;
-    const int first = run.first, n = run.second;
-    if(lift_fused_applies(plans[0], plans[first], mode, acc)) {
-      rc = lift_fwd_launch(plans, first, n, d_c, d_m, call, ll.data(), batch, stream, lay, m_poly_stride);
-      continue;
-    }
-    uint64_t *c = d_c + (uint64_t)first * lay.limb;
-    if(acc) rc = rns_transform(n, plans + first, c, batch, true, stream, one);
-    if(!rc) rc = lift_coef_launch(plans, first, n, d_c, d_m, call, ll.data(), batch, stream, lay, m_poly_stride);
-    if(!rc) rc = rns_transform(n, plans + first, c, batch, false, stream, one);
-  }
-  return rc;
+  for(int l = 0; l < nlimbs; l++) ll[(size_t)l] = lift_limb(plans[l]->q, mode, t, la.call.r);
+  return produce_route(
+    "lift", nlimbs, plans, d_c, batch, (flags & NTT_LIFT_TRANSFORMED) != 0, acc, stream, lay, overlap ? "lift: the plaintext overlaps the output" : nullptr,
+    [&](const std::pair<int, int> &run) { return lift_fused_applies(plans[0], plans[run.first], mode, acc); },
+    [&](int first, int n) {
+      LiftArgs a = la;
+      produce_args(a, plans[0], first, n, d_c, ll.data(), batch, stream, lay);
+      return produce_launched("lift_coef_kernel", launch_lift_coef(a));
+    },
+    [&](int first, int n) {
+      const std::vector<unsigned char> recs = rns_records(plans, first, n);
+      LiftArgs                         a    = la;
+      produce_args(a, plans[first], first, n, d_c, ll.data(), batch, stream, lay);
+      a.limbs = recs.data();
+      return produce_launched("lift_fwd_kernel", with_f64_class(run_class(plans, first, n), [&](auto k) {
+                                return launch_lift_fwd<typename decltype(k)::A, decltype(k)::KSH>(a);
+                              }));
+    });
 }
 
 static uint64_t lift_n(int nlimbs, ntt_plan *const *plans) { return (nlimbs > 0 && plans && plans[0]) ? plans[0]->N : 0; }

@@ -65,19 +65,10 @@ __global__ void __launch_bounds__(256) lift_coef_kernel(const KLiftCoef k)
 
 hipError_t launch_lift_coef(const LiftCoefArgs &la)
 {
-  if(la.nlimbs < 1 || la.nlimbs > kLiftLimbs || la.logn < 1 || la.logn > 30) return hipErrorInvalidValue;
   KLiftCoef k{};
-  k.c             = la.c;
-  k.m             = la.m;
-  k.limb_stride   = la.limb_stride;
-  k.poly_stride   = la.poly_stride ? la.poly_stride : (1ull << la.logn);
-  k.m_poly_stride = la.m_poly_stride ? la.m_poly_stride : (1ull << la.logn);
-  k.batch         = la.batch;
-  k.logn          = la.logn;
-  k.nlimbs        = la.nlimbs;
-  k.call[0]       = la.call;
-  k.accumulate    = la.call.accumulate;
-  for(int l = 0; l < la.nlimbs; l++) k.limbs[l] = la.limbs[l];
+  if(!produce_coef_record(k, la)) return hipErrorInvalidValue;
+  k.m              = la.m;
+  k.m_poly_stride  = la.m_poly_stride ? la.m_poly_stride : (1ull << la.logn);
   const uint64_t n = la.batch << la.logn;
   if(n == 0) return hipSuccess;
   hipLaunchKernelGGL(lift_coef_kernel, dim3(coef_grid(n, la.max_grid)), dim3(256), 0, la.stream, k);

@@ -158,6 +158,7 @@ static int check_device(int device)
 #include "host/host_bgv.inc"
 #include "host/host_lincomb.inc"
 #include "host/host_plain.inc"
+#include "host/host_produce.inc"
 #include "host/host_lift.inc"
 #include "host/host_sample.inc"
 #include "host/host_slots.inc"

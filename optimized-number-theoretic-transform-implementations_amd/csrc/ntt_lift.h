@@ -21,11 +21,11 @@
  * in a conditional subtraction, so the word lies in [0, q_l).
  */
 #pragma once
-#include "ntt_keyswitch.h"
+#include "ntt_produce.h"
 
 namespace ntt {
 
-constexpr int kLiftLimbs = 16; /* limbs of one launch (= kMaxLimbs) */
+constexpr int kLiftLimbs = kProduceLimbs; /* limbs of one launch */
 
 enum LiftMode : uint32_t { kLiftCentred = 0, kLiftScaled = 1, kLiftDouble = 2 };
 
@@ -137,34 +137,18 @@ NTT_HD uint64_t lift_digit(const LiftWord &w, uint32_t mode, const LiftLimb &l)
   return lift_centred(w.a, w.neg, l);
 }
 
-/* coefficients: c_l (+)= the lift for up to kLiftLimbs limbs, the plaintext word read once (lift_coef_kernel; lift.hip) */
-struct LiftCoefArgs {
-  uint64_t *      c; /* limb 0 of the chunk                                                       */
-  const uint64_t *m; /* the plaintext: words mod t, or the bit patterns of doubles ([batch][N])   */
-  uint64_t        limb_stride, poly_stride, m_poly_stride, batch;
-  uint32_t        logn;
-  int             nlimbs;
-  LiftCall        call;
-  LiftLimb        limbs[kLiftLimbs];
-  int             max_grid;
-  hipStream_t     stream;
+struct LiftArgs : ProduceArgs<LiftCall> {
+  const uint64_t *m; /* the plaintext: words mod t, or the bit patterns of doubles ([batch][N]) */
+  uint64_t        m_poly_stride;
 };
+
+/* coefficients: c_l (+)= the lift for up to kLiftLimbs limbs, the plaintext word read once (lift_coef_kernel; lift.hip) */
+using LiftCoefArgs = LiftArgs;
 hipError_t launch_lift_coef(const LiftCoefArgs &la);
 
 /* NTT domain, FP64 policies, N = 2^6..2^14: c_l^ (+)= fwd(the lift) in ONE launch over a run of limbs (lift_fwd_kernel;
  * lift_f64*.hip) */
-struct LiftFwdArgs {
-  uint64_t *      c;      /* limb 0 of the run (NTT domain, canonical)      */
-  const uint64_t *m;      /* the plaintext                                  */
-  const void *    limbs;  /* HOST array of the run's LimbRec<A>             */
-  int             nlimbs; /* 1 .. kLiftLimbs                                */
-  uint64_t        limb_stride, poly_stride, m_poly_stride, batch;
-  uint32_t        logn;
-  LiftCall        call;
-  LiftLimb        ll[kLiftLimbs];
-  int             max_grid, num_cus;
-  hipStream_t     stream;
-};
+using LiftFwdArgs = LiftArgs;
 template <class A, int KSH> hipError_t launch_lift_fwd(const LiftFwdArgs &la);
 template <> hipError_t launch_lift_fwd<ArithF64, 0>(const LiftFwdArgs &);
 template <> hipError_t launch_lift_fwd<ArithF64, 1>(const LiftFwdArgs &);

@@ -116,31 +116,12 @@ NTT_HD uint64_t sample_digit(const SampleCall &c, uint64_t P, uint32_t s, uint32
 }
 
 /* coefficients: c_l (+)= the sample for up to kSampleLimbs limbs, nothing read (sample_coef_kernel; sample.hip) */
-struct SampleCoefArgs {
-  uint64_t *  c; /* limb 0 of the chunk */
-  uint64_t    limb_stride, poly_stride, batch;
-  uint32_t    logn;
-  int         nlimbs;
-  SampleCall  call;
-  SampleLimb  limbs[kSampleLimbs];
-  int         max_grid;
-  hipStream_t stream;
-};
+using SampleCoefArgs = ProduceArgs<SampleCall>;
 hipError_t launch_sample_coef(const SampleCoefArgs &sa);
 
 /* NTT domain, FP64 policies, N = 2^6..2^14: c_l^ (+)= fwd(the sample) in ONE launch over a run of limbs (sample_fwd_kernel;
  * sample_f64*.hip) */
-struct SampleFwdArgs {
-  uint64_t *  c;      /* limb 0 of the run (NTT domain, canonical) */
-  const void *limbs;  /* HOST array of the run's LimbRec<A>        */
-  int         nlimbs; /* 1 .. kSampleLimbs                         */
-  uint64_t    limb_stride, poly_stride, batch;
-  uint32_t    logn;
-  SampleCall  call;
-  SampleLimb  ll[kSampleLimbs];
-  int         max_grid, num_cus;
-  hipStream_t stream;
-};
+using SampleFwdArgs = ProduceArgs<SampleCall>;
 template <class A, int KSH> hipError_t launch_sample_fwd(const SampleFwdArgs &sa);
 template <> hipError_t launch_sample_fwd<ArithF64, 0>(const SampleFwdArgs &);
 template <> hipError_t launch_sample_fwd<ArithF64, 1>(const SampleFwdArgs &);

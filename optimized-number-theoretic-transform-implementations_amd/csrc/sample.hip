@@ -64,17 +64,8 @@ __global__ void __launch_bounds__(256) sample_coef_kernel(const KSampleCoef k)
 
 hipError_t launch_sample_coef(const SampleCoefArgs &sa)
 {
-  if(sa.nlimbs < 1 || sa.nlimbs > kSampleLimbs || sa.logn < 1 || sa.logn > 30) return hipErrorInvalidValue;
   KSampleCoef k{};
-  k.c           = sa.c;
-  k.limb_stride = sa.limb_stride;
-  k.poly_stride = sa.poly_stride ? sa.poly_stride : (1ull << sa.logn);
-  k.batch       = sa.batch;
-  k.logn        = sa.logn;
-  k.nlimbs      = sa.nlimbs;
-  k.call[0]     = sa.call;
-  k.accumulate  = sa.call.accumulate;
-  for(int l = 0; l < sa.nlimbs; l++) k.limbs[l] = sa.limbs[l];
+  if(!produce_coef_record(k, sa)) return hipErrorInvalidValue;
   const uint64_t n = sa.batch << sa.logn;
   if(n == 0) return hipSuccess;
   hipLaunchKernelGGL(sample_coef_kernel, dim3(coef_grid(n, sa.max_grid)), dim3(256), 0, sa.stream, k);
